@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
-  (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  (N > 1: launched by torch.distributed.run, one rank per GPU; --dump-outputs: see dump_outputs below)
 
 Workload (config.workload): BASELINE.json configs[1] -- sphere-stack x4096:
 4096 independent instances of /root/reference/example/stacks/sphere-stack.xml
@@ -663,6 +663,27 @@ def long_horizon_leg(torch, wb, stream, B, args):
         return {"error": repr(e)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, state, aux, first, rank, world_size):
+    """--dump-outputs: what the timed launch handed its caller (WorldBatchDevice.download() after the last timed step) as
+    float64 .npy files -- `state` (worlds x bodies*13) and one `aux_<field>` per solver-state field of mh_world_aux (integer
+    fields are exact in float64) -- with `world_index`, the global id of every row.  At most 64 MB over all ranks: a larger
+    batch is cut to a fixed, seeded sample of its worlds.  Ranks of an N-GPU run write their shards as <name>_rank<r>.npy."""
+    fields = [f for f in aux.dtype.names if not f.startswith("pad")]
+    per_world = 8 * (1 + state.shape[1] + sum(int(np.prod(aux.dtype[f].shape, dtype=np.int64)) for f in fields))
+    B = state.shape[0]
+    keep = min(B, (DUMP_LIMIT_BYTES // world_size - 4096 * (len(fields) + 2)) // per_world)     # 4096: room for each file's .npy header
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(12345).choice(B, keep, replace=False))
+    arrays = {"world_index": first + rows, "state": state[rows]}
+    arrays.update(("aux_" + f, aux[f][rows]) for f in fields)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world_size > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -681,7 +702,11 @@ def main():
     ap.add_argument("--config4-tall-worlds", type=int, default=64)
     ap.add_argument("--no-long-horizon", action="store_true")
     ap.add_argument("--long-horizon-start", type=int, default=4000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (body states and per-world solver state of the last step) as float64 .npy files under DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  The ranks are CHILD processes started before this
@@ -754,7 +779,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kern_s = ev0.elapsed_time(ev1) * 1e-3
-    _, aux1 = wb.download()
+    st1, aux1 = wb.download()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st1, aux1, first, rank, world_size)
     d = lambda f: int(aux1[f].astype(np.int64).sum() - aux0[f].astype(np.int64).sum())
     tot = mdist.counter_vector(aux0, aux1, (aux1["status"] & ~S.MH_WORLD_IMPACT_TOL) != 0)
     # the per-interval reduction of SURVEY 8e: one MAX + one SUM all-reduce (RCCL over xGMI)

@@ -1,6 +1,5 @@
 """CPU: the Moby-XML reader for one fixed-base RCArticulatedBody (include/moby_hip_io.h: mh_io_load_xml_artic) -- the numbers it
-derives from tests/scenes/arm_on_table.xml, the reference's own example files when the reference tree is present, what it rejects,
-and the loaded model stepped by the oracle."""
+derives from tests/scenes/arm_on_table.xml, what it rejects, and the loaded model stepped by the oracle."""
 import os
 
 import numpy as np
@@ -12,7 +11,6 @@ from moby_amd import scene as S
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ARM = os.path.join(HERE, "scenes", "arm_on_table.xml")
-REF = "/root/reference/example"
 
 
 def test_arm_on_table_loads_to_the_numbers_of_the_file():
@@ -41,32 +39,23 @@ def test_arm_on_table_loads_to_the_numbers_of_the_file():
     assert (m.cp_epsilon, m.cp_mu_coulomb, m.cp_nk) == (0.0, 100.0, 4) and m.contact_dist_thresh == 1e-6 and m.min_step_size == S.NEAR_ZERO
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-def test_reference_example_files_load():
-    m, links, joints, q0, qd0, dt = A.load_xml(os.path.join(REF, "joint-limits", "limit-double-pendulum.xml"))
-    assert (m.nj, links, joints, dt) == (2, ["l1", "l2"], ["q", "q2"], 0.01)
-    assert np.allclose(q0, [1.57079632679, 0.0]) and list(m.lolimit[:2]) == [-1.0, -0.1] and list(m.hilimit[:2]) == [3.14, 0.1]
-    assert list(m.trel[1]) == [0.0, -5.0, 0.0] and list(m.com[0]) == [0.0, -2.5, 0.0] and m.mass[0] == pytest.approx(np.pi * 5.0) and m.nspheres == 0
-    m5 = A.load_xml(os.path.join(REF, "joint-limits", "chain.xml"))[0]
-    assert m5.nj == 5 and list(m5.parent[:5]) == [-1, 0, 1, 2, 3]
-    m1 = A.load_xml(os.path.join(REF, "reduced-coords", "pendulum.xml"))[0]
-    assert m1.nj == 1 and m1.algorithm == A.MH_ARTIC_FSAB
-    for bad, why in (("reduced-coords/pendulum-gears-impact.xml", "q-tare"), ("fixed-joint/fixed-articulated-table.xml", "only Sphere collision geometry"), ("tare/pendulum.xml", "q-tare"), ("reduced-coords/chain.xml", "Plane")):
-        with pytest.raises(mio.SceneError, match=why):
-            A.load_xml(os.path.join(REF, bad))
-
-
 def test_unsupported_files_are_rejected(tmp_path):
     src = open(ARM).read()
     cases = {"floating": src.replace('floating-base="false"', 'floating-base="true"'),
              "link-link": src.replace('<DisabledPair object1-id="arm" object2-id="arm" />', ""),
              "only Sphere": src.replace('<DisabledPair object1-id="l1" object2-id="ground" />', ""),
              "revolute, prismatic and fixed": src.replace("<PrismaticJoint", "<SphericalJoint"),
-             "1-DOF": src.replace('lower-limits="-2"', 'lower-limits="-2 0"')}
+             "1-DOF": src.replace('lower-limits="-2"', 'lower-limits="-2 0"'),
+             "q-tare": src.replace('<RevoluteJoint id="elbow"', '<RevoluteJoint id="elbow" q-tare="0.1"'),
+             "must carry a Plane": src.replace('<CollisionGeometry primitive-id="table" />', '<CollisionGeometry primitive-id="ball" />')}
     for why, text in cases.items():
+        assert text != src, why
         p = tmp_path / "x.xml"; p.write_text(text)
         with pytest.raises(mio.SceneError, match=why):
             A.load_xml(str(p))
+    # a zero q-tare is the default and changes nothing
+    p = tmp_path / "tare0.xml"; p.write_text(src.replace('<RevoluteJoint id="elbow"', '<RevoluteJoint id="elbow" q-tare="0"'))
+    assert bytes(A.load_xml(str(p))[0]) == bytes(A.load_xml(ARM)[0])
 
 
 def test_loaded_arm_steps_in_the_oracle(oracle):

@@ -1,6 +1,6 @@
 """CPU: the URDF reader (include/moby_hip_io.h: mh_io_load_urdf, and urdf-filename on <RCArticulatedBody> in mh_io_load_xml_artic) -- the
-numbers it derives from tests/scenes/arm_on_table.urdf against the same arm written as Moby XML and put together by hand, the reference's
-own example/urdf files when the reference tree is present, what it rejects, and the loaded model stepped by the oracle."""
+numbers it derives from tests/scenes/arm_on_table.urdf against the same arm written as Moby XML and put together by hand, what it rejects,
+and the loaded model stepped by the oracle."""
 import os
 
 import numpy as np
@@ -14,7 +14,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 URDF = os.path.join(HERE, "scenes", "arm_on_table.urdf")
 URDF_XML = os.path.join(HERE, "scenes", "arm_on_table_urdf.xml")
 ARM_XML = os.path.join(HERE, "scenes", "arm_on_table.xml")
-REF = "/root/reference/example/urdf"
 
 
 def welded(parts):
@@ -66,21 +65,6 @@ def test_urdf_through_the_xml_file():
     assert (m.cp_epsilon, m.cp_mu_coulomb, m.cp_nk, m.cstab_max_iterations, m.algorithm) == (0.0, 100.0, 4, 0, A.MH_ARTIC_CRB)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-def test_reference_pendulum_urdf_loads():
-    """example/urdf/pendulum.urdf read in place: a continuous joint at (0, 0.18, 0) about z, the rod welded to the pendulum link"""
-    m, links, joints = A.load_urdf(os.path.join(REF, "pendulum.urdf"), gravity=(0.0, -9.81, 0.0))
-    assert (m.nj, links, joints) == (1, ["pendulum_link"], ["pendulum_joint"]) and m.parent[0] == -1 and m.jtype[0] == A.MH_JOINT_REVOLUTE
-    assert list(m.trel[0]) == [0.0, 0.18, 0.0] and list(m.Rrel[0]) == [1, 0, 0, 0, 1, 0, 0, 0, 1] and list(m.axis[0]) == [0.0, 0.0, 1.0]
-    assert (m.lolimit[0], m.hilimit[0]) == (-10000.0, 10000.0)          # URDFReader.cpp:334-337 (effort = 0 alone sets neither limit)
-    M, c, I = welded([(0.05, (0.25, 0, 0), np.diag([1e-3] * 3)), (0.001, (0, 0, 0), np.diag([1e-3] * 3))])
-    assert m.mass[0] == pytest.approx(M, rel=1e-15) and list(m.com[0]) == pytest.approx(list(c), abs=1e-16)
-    assert np.array(m.inertia[0]).reshape(3, 3) == pytest.approx(I, abs=1e-18)
-    # the scene file next to it: the rod's cylinder could meet the ground plane -- outside the sphere / plane pair this build generates contacts for
-    with pytest.raises(mio.SceneError, match="only Sphere"):
-        A.load_xml(os.path.join(REF, "pendulum-urdf.xml"))
-
-
 def test_unsupported_urdf_files_are_rejected(tmp_path):
     src = open(URDF).read()
     cases = {"not supported": src.replace('type="prismatic"', 'type="floating"'),
@@ -124,6 +108,21 @@ def test_revolute_joints_without_limits_get_a_quarter_turn(tmp_path):
     p = tmp_path / "x.urdf"; p.write_text(open(URDF).read().replace('<limit lower="-2" upper="2" effort="0" />', '<limit velocity="1" />'))
     m = A.load_urdf(str(p))[0]
     assert (m.lolimit[0], m.hilimit[0]) == (-np.pi / 2, np.pi / 2)       # URDFReader.cpp:326-331; a <limit> with velocity alone does not count (:549)
+    p.write_text(open(URDF).read().replace('<limit lower="-2" upper="2" effort="0" />', '<limit effort="0" />'))
+    m = A.load_urdf(str(p))[0]
+    assert (m.lolimit[0], m.hilimit[0]) == (-np.pi / 2, np.pi / 2)       # effort alone ends the search (:549) but sets neither limit
+
+
+def test_continuous_joints_are_revolute_without_limits(tmp_path):
+    """type="continuous" is a revolute joint with limits -10000 .. 10000 (URDFReader.cpp:334-337), whether its <limit> carries an effort
+    alone or it has none"""
+    src = open(URDF).read().replace('<joint name="shoulder" type="revolute">', '<joint name="shoulder" type="continuous">')
+    for limit in ('<limit effort="0" />', ""):
+        p = tmp_path / "x.urdf"; p.write_text(src.replace('<limit lower="-2" upper="2" effort="0" />', limit))
+        m, links, joints = A.load_urdf(str(p))
+        assert joints[0] == "shoulder" and m.jtype[0] == A.MH_JOINT_REVOLUTE, limit
+        assert (m.lolimit[0], m.hilimit[0]) == (-10000.0, 10000.0), limit
+        assert (m.lolimit[1], m.hilimit[1]) == (-0.5, 1.5)              # the other joints keep their own limits
 
 
 def test_loaded_urdf_arm_steps_in_the_oracle(oracle):

@@ -10,7 +10,6 @@ import pytest
 from moby_amd import artic as A
 from moby_amd import scene as S
 
-REF_SDF = "/root/reference/example/ur10/model.sdf"
 HERE = os.path.dirname(os.path.abspath(__file__))
 UR10 = os.path.join(HERE, "scenes", "ten_joint_arm.sdf")
 
@@ -146,10 +145,9 @@ def test_joint_limit_stops_the_joint_and_follows_the_reference_rules(oracle):
 
 
 def test_sdf_loader_reads_the_ur10_model():
-    """The numbers of example/ur10/model.sdf: 10 joints -- 8 revolute (two of them +-1e-5 'fixed'), 2
+    """The numbers of example/ur10/model.sdf, as tests/scenes/ten_joint_arm.sdf carries them: 10 joints -- 8 revolute (two of them +-1e-5 'fixed'), 2
     prismatic fingers --, a chain to the hand, then the two fingers as siblings."""
-    path = REF_SDF if os.path.exists(REF_SDF) else UR10
-    m, links, joints = A.load_sdf(path)
+    m, links, joints = A.load_sdf(UR10)
     assert m.nj == 10
     assert links == ["base_link", "shoulder_link", "upper_arm_link", "forearm_link", "wrist_1_link", "wrist_2_link", "wrist_3_link",
                      "hand", "l_finger", "r_finger"]

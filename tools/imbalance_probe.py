@@ -1,5 +1,5 @@
-import sys,time,numpy as np
-sys.path.insert(0,'/root/repo')
+import os,sys,time,numpy as np
+sys.path.insert(0,os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from moby_amd import scene as S
 from moby_amd.world import WorldBatchDevice
 import torch
