@@ -22,8 +22,8 @@
  * positive definite, a failed compute_X -- is caught nowhere in the reference; the state stays where the throw left it and later steps pass the world over.
  *
  * Scope: config 5 is the robot alone (self-collision disabled as in ur10.xml:12: no contact rows, one mini-step per step);
- * optionally sphere primitives on links against a static plane (mh_artic_model.nspheres, no-slip contacts), no actuator torques (controller plugins stay on the host side of the seam: add them
- * through qdd = H^-1 (tau - C) by passing tau).  Constraint stabilisation with joint-limit rows and, for bodies with link spheres, contact
+ * optionally sphere primitives on links against a static plane (mh_artic_model.nspheres, no-slip contacts); joint forces and PD joint servos
+ * through a drive (mh_artic_drive below: what controller plugins hand in as tau, evaluated inside the step).  Constraint stabilisation with joint-limit rows and, for bodies with link spheres, contact
  * rows: mh_artic_model.cstab_max_iterations (ur10.xml:11 sets constraint-stabilization-max-iterations = 0 = off).
  */
 #ifndef MOBY_HIP_ARTIC_H
@@ -126,6 +126,41 @@ int mh_artic_batch_link_poses(mh_artic_batch* ab, double* poses);
  * link multiplies its direction row [d, r x d] with (ImpactConstraintHandler::add_contact_dir_to_Jacobian, ICH:1817-1845).
  * J_out: B x 6 x nj, row-major. */
 int mh_artic_batch_jacobian(mh_artic_batch* ab, int link, const double* points, double* J_out);
+
+/* Drives: joint forces and PD joint servos inside the step -- what the reference's controller plugins do (example/ur10/controller.cpp), called
+ * once per mini-step from precalc_fwd_dyn (TimeSteppingSimulator.cpp:173 -> Simulator.cpp:319-350, ArticulatedBody.cpp:95-115).
+ * A drive gives every world a generalized force per joint, evaluated inside the step ONCE PER MINI-STEP, immediately before that mini-step's
+ * forward dynamics: q has already been advanced by the mini-step's position update, qd is still the mini-step's starting velocity,
+ *   tau_j = (kp_j * (q_des_j - q_j) + kv_j * (qd_des_j - qd_j)) + tau_ff_j
+ * every operation rounded on its own (no FMA); a term whose bit is not set is ABSENT (MH_DRIVE_FORCE alone: tau = tau_ff; MH_DRIVE_PD alone:
+ * tau = the bracket).  The forward dynamics then solve H qdd = tau - C, as mh_artic_batch_fwd_dyn does.  The virtual joints of a floating
+ * base are driven like any other column.  tau does NOT enter compute_X / the generalized inertia: impulses, restitution and constraint
+ * stabilisation are unchanged, as in the reference.  A world carrying MH_WORLD_LCP_FAILED is passed over as by mh_artic_batch_step.
+ * Arrays are row-major with the batch's joint order; world b, joint j of schedule row r is element (r B + b) nj + j. */
+#define MH_DRIVE_FORCE 1      /* tau_ff */
+#define MH_DRIVE_PD    2      /* kp, kv, q_des, qd_des */
+typedef struct mh_artic_drive {
+  int terms;                  /* MH_DRIVE_* bits; 0 = undriven (nothing else is read) */
+  int rows;                   /* schedule rows R: 1 = row 0 held for the whole launch; R >= nsteps = step s of the launch (all its mini-steps) reads row s */
+  const double* kp;           /* B x nj */
+  const double* kv;           /* B x nj */
+  const double* q_des;        /* R x B x nj */
+  const double* qd_des;       /* R x B x nj */
+  const double* tau_ff;       /* R x B x nj */
+} mh_artic_drive;
+/* nsteps x TimeSteppingSimulator::step(dt) in one launch with a drive.  The drive's pointers are DEVICE pointers on the batch's device, read in
+ * stream order; drive == NULL: the drive stored by mh_artic_batch_set_drive (none stored: exactly mh_artic_batch_step).  MH_ERR_INVALID_ARG:
+ * unknown bits in terms, a NULL pointer for a requested term, rows < 1, 1 < rows < nsteps.  The kernel is the one mh_artic_batch_step picks
+ * (spheres -> contacts, cstab -> the stabilising kernel, otherwise MH_ARTIC_WAVES); the two-worlds-per-wave kernel (mh_debug_set key 9,
+ * MH_ARTIC_PACK) has no driven form: a driven launch takes the one-world kernels whatever it is set to. */
+int mh_artic_batch_step_driven(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* drive);
+/* HOST arrays, copied into batch-owned device storage (synchronously, after the work in flight on the device) and used by
+ * mh_artic_batch_step_driven(..., NULL) until replaced; host_drive == NULL or terms == 0 clears it.  rows >= 1 is checked here, rows against
+ * nsteps at each step. */
+int mh_artic_batch_set_drive(mh_artic_batch* ab, const mh_artic_drive* host_drive);
+/* the resident q / qd into caller DEVICE buffers (B x nj each, either may be NULL), stream-ordered (hipMemcpyAsync on `stream`): the
+ * observation half of a GPU-resident control loop (state_dev -> a policy on the device -> step_driven with device pointers) */
+int mh_artic_batch_state_dev(mh_artic_batch* ab, void* stream, double* q_dst, double* qd_dst);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,9 @@ SYMBOLS = {
     "mh_artic_batch_download": (_i, [_vp, _vp, _vp, _vp]),
     "mh_artic_batch_link_poses": (_i, [_vp, _vp]),
     "mh_artic_batch_jacobian": (_i, [_vp, _i, _vp, _vp]),
+    "mh_artic_batch_step_driven": (_i, [_vp, _vp, _d, _i, _vp]),
+    "mh_artic_batch_set_drive": (_i, [_vp, _vp]),
+    "mh_artic_batch_state_dev": (_i, [_vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """Host-side mirror of the articulated-body stepper (include/moby_hip_artic.h).
 
 ``ArticBatch(model, q, qd)`` plays the role of B simulators that each hold one fixed-base ``RCArticulatedBody``
-(``step``), and of ``RCArticulatedBodyd::calc_fwd_dyn`` / ``get_generalized_inertia`` on their states (``fwd_dyn``);
+(``step``, driven by joint forces and PD servos through a ``Drive``), and of ``RCArticulatedBodyd::calc_fwd_dyn`` / ``get_generalized_inertia`` on their states (``fwd_dyn``);
 ``load_sdf`` reads example/ur10/model.sdf through the C++ loader of libmoby_hip_io.so; ``model_from_links`` builds a
 model from global link poses the way that loader does (synthetic chains for the tests).
 """
@@ -35,6 +35,45 @@ class mh_artic_model(ctypes.Structure):
 
 
 MH_ARTIC_CRB, MH_ARTIC_FSAB = 0, 1      # moby_hip_artic.h: RCArticulatedBody::algorithm_type
+MH_DRIVE_FORCE, MH_DRIVE_PD = 1, 2       # moby_hip_artic.h: mh_artic_drive.terms
+
+
+class mh_artic_drive(ctypes.Structure):
+    _fields_ = [("terms", ctypes.c_int), ("rows", ctypes.c_int), ("kp", ctypes.c_void_p), ("kv", ctypes.c_void_p),
+                ("q_des", ctypes.c_void_p), ("qd_des", ctypes.c_void_p), ("tau_ff", ctypes.c_void_p)]
+
+
+class Drive:
+    """Joint forces and PD joint servos evaluated inside the step, once per mini-step (include/moby_hip_artic.h, mh_artic_drive):
+        tau = (kp * (q_des - q) + kv * (qd_des - qd)) + tau_ff
+    PD (kp, kv, q_des, qd_des: all four or none) and the feed-forward force tau_ff are independent terms; an absent term is not in the sum.
+    kp, kv: (B, nj).  q_des, qd_des, tau_ff: (B, nj) held for the whole launch, or (R, B, nj) schedules whose row s drives step s of the
+    launch (R >= nsteps).  Arrays are numpy (staged to the device) or float64 contiguous torch tensors on the batch's device (zero-copy)."""
+    _PD = ("kp", "kv", "q_des", "qd_des")
+    _SCHED = ("q_des", "qd_des", "tau_ff")
+
+    def __init__(self, kp=None, kv=None, q_des=None, qd_des=None, tau_ff=None):
+        self.arrays = dict(kp=kp, kv=kv, q_des=q_des, qd_des=qd_des, tau_ff=tau_ff)
+        given = [self.arrays[k] is not None for k in self._PD]
+        if any(given) and not all(given):
+            raise ValueError("Drive: PD needs kp, kv, q_des and qd_des")
+        self.terms = (MH_DRIVE_PD if all(given) else 0) | (MH_DRIVE_FORCE if tau_ff is not None else 0)
+        shapes = {k: tuple(a.shape) for k, a in self.arrays.items() if a is not None}
+        sched = {shapes[k][0] if len(shapes[k]) == 3 else 1 for k in self._SCHED if k in shapes}
+        if len(sched) > 1:
+            raise ValueError("Drive: q_des, qd_des and tau_ff must have the same number of schedule rows: %r" % shapes)
+        self.rows = sched.pop() if sched else 1
+        self.shapes = shapes
+
+    def check(self, B, nj):
+        for k, sh in self.shapes.items():
+            want = [(B, nj)] + ([(self.rows, B, nj)] if k in self._SCHED else [])
+            if sh not in want:
+                raise ValueError("Drive.%s: shape %r, expected %s" % (k, sh, " or ".join(map(str, want))))
+
+
+def _is_tensor(a):
+    return type(a).__module__.startswith("torch")
 
 
 class mh_io_artic(ctypes.Structure):
@@ -177,6 +216,7 @@ class ArticBatch:
         self.B = q.shape[0]
         assert q.shape == (self.B, self.nj) and qd.shape == q.shape
         self.handle = ctypes.c_void_p()
+        self._staged = None
         _lib.check(lib.mh_artic_batch_create(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
         self.upload(q, qd, aux)
 
@@ -184,8 +224,61 @@ class ArticBatch:
         P = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data
         _lib.check(_lib.load().mh_artic_batch_upload(self.handle, P(q), P(qd), P(aux)))
 
-    def step(self, dt, nsteps=1, stream=None):
-        _lib.check(_lib.load().mh_artic_batch_step(self.handle, stream, float(dt), int(nsteps)))
+    def _device(self):
+        import torch
+        return torch.device("cuda", _lib.load().mh_artic_batch_device(self.handle))
+
+    def _tensor_ptr(self, t, shape):
+        import torch
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.device != self._device() or tuple(t.shape) != tuple(shape):
+            raise ValueError("expected a contiguous float64 tensor of shape %r on %s, got %s %r on %s" % (tuple(shape), self._device(), t.dtype, tuple(t.shape), t.device))
+        return t.data_ptr()
+
+    def step(self, dt, nsteps=1, stream=None, drive=None):
+        """nsteps x TimeSteppingSimulator::step(dt) in one launch on `stream` (a raw HIP stream handle; None = the null stream).
+        drive: a Drive for this launch; None = the drive stored by set_drive (none: undriven).  A torch loop passes
+        torch.cuda.current_stream().cuda_stream here and to state_into, so that both run in order with its own kernels."""
+        lib = _lib.load()
+        if self._staged is not None:               # numpy arrays staged by the previous launch: free them once it has read them
+            import torch
+            torch.cuda.synchronize(self._device())
+            self._staged = None
+        d = None
+        if drive is not None:
+            drive.check(self.B, self.nj)
+            d = mh_artic_drive(terms=drive.terms, rows=drive.rows)
+            staged = []
+            for k, a in drive.arrays.items():
+                if a is None:
+                    continue
+                if not _is_tensor(a):
+                    import torch
+                    a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self._device())
+                    staged.append(a)
+                setattr(d, k, self._tensor_ptr(a, a.shape))
+            self._staged = staged or None
+        _lib.check(lib.mh_artic_batch_step_driven(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d)))
+
+    def set_drive(self, drive=None):
+        """Store a Drive (host copies of its arrays on the device) for every later step(..., drive=None); None clears it."""
+        if drive is None:
+            _lib.check(_lib.load().mh_artic_batch_set_drive(self.handle, None))
+            return
+        drive.check(self.B, self.nj)
+        d = mh_artic_drive(terms=drive.terms, rows=drive.rows)
+        keep = []
+        for k, a in drive.arrays.items():
+            if a is None:
+                continue
+            h = np.ascontiguousarray(a.detach().cpu().numpy() if _is_tensor(a) else a, dtype=np.float64)
+            keep.append(h)
+            setattr(d, k, h.ctypes.data)
+        _lib.check(_lib.load().mh_artic_batch_set_drive(self.handle, ctypes.byref(d)))
+
+    def state_into(self, q_t=None, qd_t=None, stream=None):
+        """The resident q / qd into float64 contiguous (B, nj) torch tensors on the batch's device, stream-ordered (no host sync)."""
+        P = lambda t: None if t is None else self._tensor_ptr(t, (self.B, self.nj))
+        _lib.check(_lib.load().mh_artic_batch_state_dev(self.handle, stream, P(q_t), P(qd_t)))
 
     def fwd_dyn(self, tau=None, want_H=True):
         qdd = np.zeros((self.B, self.nj)); H = np.zeros((self.B, self.nj, self.nj)) if want_H else None
@@ -215,6 +308,7 @@ class ArticBatch:
         if self.handle:
             _lib.load().mh_artic_batch_destroy(self.handle)
             self.handle = None
+        self._staged = None
 
     def __del__(self):
         try:

@@ -7,6 +7,8 @@
 //   robots.calc_fwd_dyn(tau, qdd);                 // qdd = H^-1 (tau - C) for every copy (tau may be NULL)
 //   robots.get_generalized_inertia(H);             // B x nj x nj, row-major
 //   robots.step(5e-4, 200);                        // TimeSteppingSimulator::step x 200 in one launch (joint limits included)
+//   mh_artic_drive servo = { MH_DRIVE_PD, 1, kp, kv, q_des, qd_des, NULL };   // host arrays, B x nj (a controller plugin's PD law)
+//   robots.set_drive(servo); robots.step(5e-4, 200);   // ... now driven once per mini-step
 //
 // Collision geometry (sphere primitives on links against one static plane, contacts with mu-coulomb >= 100 as ur10.xml:19 has
 // them) is part of the model: fill it before constructing the batch, e.g.
@@ -64,7 +66,10 @@ class BatchedArticulatedBody {
   void set_generalized_velocity(const double* qd) { _qd.assign(qd, qd + _qd.size()); if (mh_artic_batch_upload(_ab, NULL, _qd.data(), NULL) != MH_OK) throw std::runtime_error(mh_last_error()); }
   void calc_fwd_dyn(const double* tau /* B x nj or NULL */, double* qdd /* B x nj */) { if (mh_artic_batch_fwd_dyn(_ab, tau, qdd, NULL) != MH_OK) throw std::runtime_error(mh_last_error()); }
   void get_generalized_inertia(double* H /* B x nj x nj */) { std::vector<double> qdd((size_t)_B * _nj); if (mh_artic_batch_fwd_dyn(_ab, NULL, qdd.data(), H) != MH_OK) throw std::runtime_error(mh_last_error()); }
-  double step(double dt, int nsteps = 1) { if (mh_artic_batch_step(_ab, NULL, dt, nsteps) != MH_OK) throw std::runtime_error(mh_last_error()); _dirty = true; return dt; }
+  // joint forces / PD servos evaluated inside every mini-step (mh_artic_drive: HOST arrays, copied to the device); terms = 0 clears
+  void set_drive(const mh_artic_drive& drive) { if (mh_artic_batch_set_drive(_ab, &drive) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  // with the drive of set_drive when one is set
+  double step(double dt, int nsteps = 1) { if (mh_artic_batch_step_driven(_ab, NULL, dt, nsteps, NULL) != MH_OK) throw std::runtime_error(mh_last_error()); _dirty = true; return dt; }
   const std::vector<double>& q() { sync(); return _q; }
   const std::vector<double>& qd() { sync(); return _qd; }
   int status(int w) { sync(); return _aux[(size_t)w].status; }

@@ -621,9 +621,37 @@ __device__ __noinline__ void stabilize_limits(const Model& M, const Lay& Y, doub
   wave_sync();
 }
 
+#ifdef MH_ARTIC_DRIVE_TU
+// The drive (moby_hip_artic.h, mh_artic_drive): lane j < nj evaluates tau_j of step s from q / qd in LDS -- q already advanced by the
+// mini-step's position update, qd still its starting velocity -- and leaves it in the qdd slot of the image: dynamics() reads
+// tau_w[lane] there before the same lane writes b[lane] (CRB), dynamics_aba() reads every tau_w[i] on lane 0 in its inward pass,
+// before the outward pass writes qdd.  No LDS of its own; kp / kv come from L2 at every mini-step.
+MH_DEV void drive_tau(const mh_artic_drive& D, int B, int b, int s, const Lay& Y, double* g)
+{
+  const int nj = Y.nj, lane = lane_id();
+  if (lane < nj) {
+    const size_t o = (size_t)b * nj + lane;
+    const size_t r = (size_t)(D.rows == 1 ? 0 : s) * (size_t)B * nj + o;
+    double t = 0.0;
+    if (D.terms & MH_DRIVE_PD) {
+      const double ep = D.q_des[r] - g[Y.q + lane], ev = D.qd_des[r] - g[Y.qd + lane];
+      const double tp = D.kp[o] * ep, tv = D.kv[o] * ev;
+      t = tp + tv;
+      if (D.terms & MH_DRIVE_FORCE) t = t + D.tau_ff[r];
+    } else t = D.tau_ff[r];
+    g[Y.qdd + lane] = t;
+  }
+}
+#endif
+
+// MH_ARTIC_DRIVE_TU (mh_artic_drive.hip): the same step with a drive -- the undriven kernels are compiled from exactly the code they had before drives existed
 template <bool STAB>
 MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                            mh_world_aux* __restrict__ auxg)
+                            mh_world_aux* __restrict__ auxg
+#ifdef MH_ARTIC_DRIVE_TU
+                            , const mh_artic_drive& D
+#endif
+                            )
 {
   extern __shared__ double g[];
   const int b = blockIdx.x;
@@ -645,8 +673,14 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
     if (status & MH_WORLD_LCP_FAILED) break;
     // positions with the OLD velocity (TSS:156-164)
     if (lane < nj) { double qn = g[Y.qd + lane] * dt; qn = qn + g[Y.q + lane]; g[Y.q + lane] = qn; }
+#ifdef MH_ARTIC_DRIVE_TU
+    drive_tau(D, B, b, s, Y, g);                                      // precalc_fwd_dyn's controller (Simulator.cpp:319-350): lane j reads the q it just wrote
+    wave_sync();
+    const bool ok = (M.m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, g + Y.qdd) : dynamics(M, Y, g, g + Y.qdd);
+#else
     wave_sync();
     const bool ok = (M.m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, nullptr) : dynamics(M, Y, g, nullptr);
+#endif
     if (!ok) { status |= MH_WORLD_LCP_FAILED; break; }
     if (lane < nj) g[Y.qd + lane] = g[Y.qd + lane] + g[Y.qdd + lane] * dt;   // TSS:182-192
     wave_sync();
@@ -669,6 +703,7 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
   }
 }
 
+#ifndef MH_ARTIC_DRIVE_TU
 // The same step at three register budgets: 128 VGPRs (4 waves per SIMD = the 16 worlds per CU the 10 KB LDS image allows; 95 spilled
 // VGPRs), 168 (3 per SIMD, 14 spilled) and 193 (2 per SIMD, none).  The kernel waits on ~250 LDS round trips per step, so
 // resident waves win over spills: ur10 x 8192, 200 steps: 25.6 / 31.2 / 39.0 ms (profiles/r02_c_artic_occupancy.jsonl).
@@ -812,6 +847,27 @@ void k_artic_jacobian(const Model* __restrict__ Mg, int B, const double* __restr
   }
 }
 
+#else   // the driven step kernels: their own code object (mh_artic_drive.hip)
+// the four budgets of k_artic_step_w{2..5} with a drive (mh_artic_batch_step_driven)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void k_artic_step_w3_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                           mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_artic_step_w4_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                           mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void k_artic_step_w5_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                           mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
+__global__ __launch_bounds__(64)
+void k_artic_step_w2_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                           mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
+
+// k_artic_step_stab with a drive
+__global__ __launch_bounds__(64)
+void k_artic_step_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                             mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
+#endif
+
 #include "mh_artic_contacts.inc"
 
 }} // namespace mh::artic
@@ -822,8 +878,22 @@ struct mh_artic_batch {
   mh::artic::Model* d_model;
   double* d_q; double* d_qd; mh_world_aux* d_aux;
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
+  mh_artic_drive drive;   // the drive of mh_artic_batch_set_drive (terms 0 = none); its arrays live in d_drive
+  double* d_drive;
 };
 
+// the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
+static int check_drive(const mh_artic_drive* d, int nsteps)
+{
+  if (d->terms & ~(MH_DRIVE_FORCE | MH_DRIVE_PD)) return fail(MH_ERR_INVALID_ARG, "drive: unknown bits 0x%x in terms", d->terms & ~(MH_DRIVE_FORCE | MH_DRIVE_PD));
+  if ((d->terms & MH_DRIVE_FORCE) && !d->tau_ff) return fail(MH_ERR_INVALID_ARG, "drive: MH_DRIVE_FORCE with a NULL tau_ff");
+  if ((d->terms & MH_DRIVE_PD) && (!d->kp || !d->kv || !d->q_des || !d->qd_des)) return fail(MH_ERR_INVALID_ARG, "drive: MH_DRIVE_PD with a NULL kp, kv, q_des or qd_des");
+  if (d->rows < 1) return fail(MH_ERR_INVALID_ARG, "drive: rows = %d < 1", d->rows);
+  if (nsteps >= 0 && d->rows > 1 && d->rows < nsteps) return fail(MH_ERR_INVALID_ARG, "drive: %d schedule rows for %d steps (1 = held, or at least one per step)", d->rows, nsteps);
+  return MH_OK;
+}
+
+#ifndef MH_ARTIC_DRIVE_TU
 extern "C" {
 
 int mh_artic_batch_device(const mh_artic_batch* ab) { return ab ? ab->device : fail(MH_ERR_INVALID_ARG, "null batch"); }
@@ -833,7 +903,7 @@ int mh_artic_batch_destroy(mh_artic_batch* ab)
   if (!ab) return MH_OK;
   MH_ON_DEVICE(ab);
   (void)hipDeviceSynchronize();
-  void* ps[] = { ab->d_model, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws };
+  void* ps[] = { ab->d_model, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws, ab->d_drive };
   for (void* p : ps) if (p) (void)hipFree(p);
   delete ab;
   return MH_OK;
@@ -908,6 +978,7 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
   ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   const size_t sB = (size_t)B;
   bool ok = hipMalloc((void**)&ab->d_model, sizeof(ar::Model)) == hipSuccess && hipMalloc((void**)&ab->d_q, sB * nj * 8) == hipSuccess
          && hipMalloc((void**)&ab->d_qd, sB * nj * 8) == hipSuccess && hipMalloc((void**)&ab->d_aux, sB * sizeof(mh_world_aux)) == hipSuccess;
@@ -972,6 +1043,42 @@ int mh_artic_batch_step(mh_artic_batch* ab, void* stream, double dt, int nsteps)
   hipLaunchKernelGGL(waves == 5 ? ar::k_artic_step_w5 : waves == 4 ? ar::k_artic_step_w4 : (waves == 2 ? ar::k_artic_step_w2 : ar::k_artic_step_w3), dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)stream,
                      (const ar::Model*)ab->d_model, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux);
   MH_HIP(hipGetLastError());
+  return MH_OK;
+}
+
+int mh_artic_batch_set_drive(mh_artic_batch* ab, const mh_artic_drive* host_drive)
+{
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  MH_ON_DEVICE(ab);
+  if (host_drive) { const int rc = check_drive(host_drive, -1); if (rc != MH_OK) return rc; }
+  MH_HIP(hipDeviceSynchronize());                              // a driven step may be reading the stored arrays on a caller's stream
+  if (ab->d_drive) (void)hipFree(ab->d_drive);
+  ab->d_drive = nullptr; std::memset(&ab->drive, 0, sizeof(ab->drive));
+  if (!host_drive || host_drive->terms == 0) return MH_OK;
+  const mh_artic_drive& h = *host_drive;
+  const size_t per = (size_t)ab->B * ab->nj, R = (size_t)h.rows;
+  const bool pd = (h.terms & MH_DRIVE_PD) != 0, ff = (h.terms & MH_DRIVE_FORCE) != 0;
+  const size_t n = (pd ? 2 * per + 2 * R * per : 0) + (ff ? R * per : 0);
+  double* d = nullptr;
+  MH_HIP(hipMalloc((void**)&d, n * sizeof(double)));
+  mh_artic_drive s; std::memset(&s, 0, sizeof(s)); s.terms = h.terms; s.rows = h.rows;
+  double* o = d;
+  hipError_t e = hipSuccess;
+  auto put = [&](const double* src, size_t cnt) -> const double* { double* at = o; o += cnt; if (e == hipSuccess) e = hipMemcpy(at, src, cnt * sizeof(double), hipMemcpyHostToDevice); return at; };
+  if (pd) { s.kp = put(h.kp, per); s.kv = put(h.kv, per); s.q_des = put(h.q_des, R * per); s.qd_des = put(h.qd_des, R * per); }
+  if (ff) s.tau_ff = put(h.tau_ff, R * per);
+  if (e != hipSuccess) { (void)hipFree(d); return fail(MH_ERR_HIP, "drive upload failed: %s", hipGetErrorString(e)); }
+  ab->d_drive = d; ab->drive = s;
+  return MH_OK;
+}
+
+int mh_artic_batch_state_dev(mh_artic_batch* ab, void* stream, double* q_dst, double* qd_dst)
+{
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  MH_ON_DEVICE(ab);
+  const size_t n = (size_t)ab->B * ab->nj * sizeof(double);
+  if (q_dst) MH_HIP(hipMemcpyAsync(q_dst, ab->d_q, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (qd_dst) MH_HIP(hipMemcpyAsync(qd_dst, ab->d_qd, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return MH_OK;
 }
 
@@ -1055,3 +1162,4 @@ int mh_artic_batch_download(mh_artic_batch* ab, double* q, double* qd, mh_world_
 }
 
 } // extern "C"
+#endif

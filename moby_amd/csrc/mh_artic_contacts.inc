@@ -536,9 +536,14 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   if (ballot(tol) != 0ull) status |= MH_WORLD_IMPACT_TOL;
 }
 
-// TimeSteppingSimulator::do_mini_step (TSS:114-222); returns h (uniform)
+// TimeSteppingSimulator::do_mini_step (TSS:114-222); returns h (uniform).  MH_ARTIC_DRIVE_TU: the drive's row of step s (world b of B) is
+// evaluated after the position update, before the forward dynamics (precalc_fwd_dyn, Simulator.cpp:319-350)
 MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* g, double* ws, mh_world_aux* aux, WaveRand& rng, double dt, bool& kin_ok, int& status,
-                           unsigned long long& solves, unsigned long long& rows, unsigned long long& pivs, unsigned long long& bytes)
+                           unsigned long long& solves, unsigned long long& rows, unsigned long long& pivs, unsigned long long& bytes
+#ifdef MH_ARTIC_DRIVE_TU
+                           , const mh_artic_drive& D, int B, int b, int s
+#endif
+                           )
 {
   const mh_artic_model& m = M.m;
   const int nj = Y.nj, lane = lane_id();
@@ -565,7 +570,12 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
     wave_sync();
   }
   wave_sync();
+#ifdef MH_ARTIC_DRIVE_TU
+  drive_tau(D, B, b, s, Y, g);                                    // (read by the dynamics after kin_inertia's barriers)
+  const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, g + Y.qdd) : dynamics(M, Y, g, g + Y.qdd);
+#else
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, nullptr) : dynamics(M, Y, g, nullptr);
+#endif
   kin_ok = true;                                                  // kin_inertia ran first thing in there, whatever came after
   if (!ok) { status |= MH_WORLD_LCP_FAILED; wave_sync(); return h; }   // an exception ends the run (oracle Artic::do_mini_step): nothing below happens
   if (lane < nj) g[Y.qd + lane] = g[Y.qd + lane] + g[Y.qdd + lane] * h;   // TSS:182-192
@@ -828,7 +838,11 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
 // allocation 187 spilled registers and half its speed -- 116 ms against 60 on the ur10 with link spheres -- even when it never runs)
 template <bool STAB>
 MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                mh_world_aux* __restrict__ auxg, double* __restrict__ wsg)
+                                mh_world_aux* __restrict__ auxg, double* __restrict__ wsg
+#ifdef MH_ARTIC_DRIVE_TU
+                                , const mh_artic_drive& D
+#endif
+                                )
 {
   extern __shared__ double g[];
   const int b = blockIdx.x;
@@ -852,7 +866,11 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
     if (status & (FROZEN | MH_WORLD_LCP_FAILED)) break;           // as in the oracle: the reference would have thrown out of step() / never returned from it
     double h = 0.0; unsigned guard = 0;
     while (h < dt) {
+#ifdef MH_ARTIC_DRIVE_TU
+      const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, D, B, b, s));
+#else
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes));
+#endif
       if (status & MH_WORLD_LCP_FAILED) break;                    // thrown out of the mini-step: current_time += h (TSS:215) is not reached, the mini-step not counted
       h += hh; tm += hh; minis++;
       if (status & FROZEN) break;
@@ -882,6 +900,7 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   }
 }
 
+#ifndef MH_ARTIC_DRIVE_TU
 // 2 waves per SIMD = the 8 worlds per CU the 18 KB LDS image allows
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
@@ -890,3 +909,12 @@ void k_artic_step_contacts(const Model* __restrict__ Mg, int B, double dt, int n
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg); }
+#else
+// the same two with a drive (mh_artic_batch_step_driven)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_artic_step_contacts_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, D); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_artic_step_contacts_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                      mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, D); }
+#endif
