@@ -69,8 +69,9 @@ typedef struct mh_artic_model {
                             link's own x, y, z through that COM, links 0..4 massless, link 5 the base link; the body's own joints follow (what
                             mh_io_load_xml_artic builds).  The dynamics, calc_jacobian and the contact rows need no special case -- six more 1-DOF columns;
                             the one place that reads the flag is conservative advancement, which adds the base's linear velocity along the direction of
-                            approach as CCD::calc_max_dist does for a moving base (CCD.cpp:547-555).  NOT Ravelin's base coordinates (spatial velocity +
-                            unit quaternion): the orientation is integrated in three angles, singular when joint 4 reaches +-pi/2.  0 = fixed base */
+                            approach as CCD::calc_max_dist does for a moving base (CCD.cpp:547-555).  By default NOT Ravelin's base coordinates (spatial
+                            velocity + unit quaternion): the orientation is integrated in three angles, singular when joint 4 reaches +-pi/2; a batch in
+                            pose coordinates (mh_artic_batch_set_base_coords below) has no such point.  0 = fixed base */
   /* Collision geometry (optional; nspheres = 0 is the robot alone: no pairs, one mini-step per step).  Sphere primitives fixed to
    * links against ONE static plane -- the closed-form pair of CCD.inl:804-847; the body's own pairs are disabled as ur10.xml:12
    * does.  With spheres the step is TimeSteppingSimulator::step in full: conservative advancement over the pairs
@@ -161,6 +162,38 @@ int mh_artic_batch_set_drive(mh_artic_batch* ab, const mh_artic_drive* host_driv
 /* the resident q / qd into caller DEVICE buffers (B x nj each, either may be NULL), stream-ordered (hipMemcpyAsync on `stream`): the
  * observation half of a GPU-resident control loop (state_dev -> a policy on the device -> step_driven with device pointers) */
 int mh_artic_batch_state_dev(mh_artic_batch* ab, void* stream, double* q_dst, double* qd_dst);
+
+/* Base coordinates of a floating base (mh_artic_model.floating_base = 1).  MH_ARTIC_BASE_ANGLES, the default: the six virtual joints carry the
+ * base's whole configuration, the orientation as three angles from the model's start pose, singular when joint 4 reaches +-pi/2.
+ * MH_ARTIC_BASE_POSE: every world also carries a base pose P = (p, Q) -- p the base link's COM in the model frame, Q a unit quaternion (w, x, y, z)
+ * -- that stands in for the model's trel[0] and Rrel[3] wherever the kinematics reads them; the virtual joints measure the motion from P.  After
+ * every step that ran to its end (after the stabiliser) the step FOLDS them into P, which changes coordinates only -- configuration and link
+ * velocities stay the same up to round-off:
+ *   p += q[0..2];   Q = normalize(Q (x) Qx(q3) (x) Qy(q4) (x) Qz(q5));
+ *   qd[3..5] = Rh' (e_x qd3 + Rx(q3) e_y qd4 + Rx(q3) Ry(q4) e_z qd5), Rh = Rx(q3) Ry(q4) Rz(q5): the base's angular velocity in its new axes;
+ *   q[0..5] = 0;  qd[0..2] (the COM velocity, global axes) and the body's own joints unchanged.
+ * So after a completed step q[0..5] are exactly 0, and the middle hinge only ever turns by one step's rotation.  A world whose step throws
+ * (MH_WORLD_LCP_FAILED) is not folded: (P, q) still describe where the throw left it.  Everything else is the step of angle coordinates:
+ * dynamics, limits, contacts, conservative advancement, the stabiliser, the drive.  A drive works on every column: tau_ff on the virtual
+ * columns is a global force at the COM and a torque about the base's own axes; a PD target on a virtual column is measured against the
+ * re-zeroed q -- rarely what a caller wants.  Side effect on conservative advancement: q[0..2] return to zero every step, so the slider terms of
+ * calc_max_dist no longer grow with the distance from the origin.  Every step route (mh_artic_batch_step, _step_driven; spheres, the stabiliser)
+ * has a pose form; MH_ARTIC_WAVES and MH_ARTIC_PACK (key 9) do not apply (the default four-waves budget).  link_poses, jacobian and fwd_dyn read
+ * each world's P.  upload / download keep their shapes: uploaded virtual q are relative to the current P.  A checkpoint of a pose batch is
+ * download + base_pose; restore is upload + set_base_pose. */
+#define MH_ARTIC_BASE_ANGLES 0
+#define MH_ARTIC_BASE_POSE   1
+/* ANGLES -> POSE: every world's P from the model (p = trel[0], Q = the quaternion of Rrel[3]), then the resident q / qd folded into it (a world
+ * carrying MH_WORLD_LCP_FAILED is not: its q still hold its configuration against the model's pose).  POSE -> POSE does nothing.
+ * MH_ERR_INVALID_ARG: a fixed base, a finite limit on one of joints 0..5, POSE -> ANGLES, an unknown value. */
+int mh_artic_batch_set_base_coords(mh_artic_batch* ab, int coords);
+int mh_artic_batch_base_coords(const mh_artic_batch* ab, int* coords);   /* the batch's MH_ARTIC_BASE_* */
+/* the poses as HOST arrays, B x 7 (px py pz qw qx qy qz), synchronously; pose coordinates only.  The setter normalises each Q and refuses a zero or
+ * non-finite quaternion (nothing is written then). */
+int mh_artic_batch_base_pose(mh_artic_batch* ab, double* pose);
+int mh_artic_batch_set_base_pose(mh_artic_batch* ab, const double* pose);
+/* the poses into a caller DEVICE buffer (B x 7), stream-ordered: the pose counterpart of mh_artic_batch_state_dev */
+int mh_artic_batch_base_pose_dev(mh_artic_batch* ab, void* stream, double* dst);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,11 @@ SYMBOLS = {
     "mh_artic_batch_step_driven": (_i, [_vp, _vp, _d, _i, _vp]),
     "mh_artic_batch_set_drive": (_i, [_vp, _vp]),
     "mh_artic_batch_state_dev": (_i, [_vp, _vp, _vp, _vp]),
+    "mh_artic_batch_set_base_coords": (_i, [_vp, _i]),
+    "mh_artic_batch_base_coords": (_i, [_vp, ctypes.POINTER(_i)]),
+    "mh_artic_batch_base_pose": (_i, [_vp, _vp]),
+    "mh_artic_batch_set_base_pose": (_i, [_vp, _vp]),
+    "mh_artic_batch_base_pose_dev": (_i, [_vp, _vp, _vp]),
 }
 
 _lib = None

@@ -36,6 +36,8 @@ class mh_artic_model(ctypes.Structure):
 
 MH_ARTIC_CRB, MH_ARTIC_FSAB = 0, 1      # moby_hip_artic.h: RCArticulatedBody::algorithm_type
 MH_DRIVE_FORCE, MH_DRIVE_PD = 1, 2       # moby_hip_artic.h: mh_artic_drive.terms
+MH_ARTIC_BASE_ANGLES, MH_ARTIC_BASE_POSE = 0, 1     # moby_hip_artic.h: mh_artic_batch_set_base_coords
+_BASE_COORDS = {"angles": MH_ARTIC_BASE_ANGLES, "pose": MH_ARTIC_BASE_POSE}
 
 
 class mh_artic_drive(ctypes.Structure):
@@ -208,7 +210,11 @@ def chain_model(n, length=0.5, mass=1.0, lo=-1.0, hi=1.0, restitution=0.0, gravi
 
 
 class ArticBatch:
-    def __init__(self, model, q, qd, aux=None):
+    """B worlds of one articulated body on the GPU.  base_coords ("angles", the default, or "pose"): how a floating base's configuration is
+    carried -- three Euler-like angles in the virtual joints, or a per-world pose (p, Q) the virtual joints are folded into after every step
+    (include/moby_hip_artic.h, MH_ARTIC_BASE_POSE: no singularity at a quarter turn of the middle hinge).  "pose" folds q / qd as given."""
+
+    def __init__(self, model, q, qd, aux=None, base_coords="angles"):
         lib = _lib.load()
         self.model = model
         self.nj = model.nj
@@ -219,6 +225,36 @@ class ArticBatch:
         self._staged = None
         _lib.check(lib.mh_artic_batch_create(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
         self.upload(q, qd, aux)
+        if base_coords != "angles":
+            self.set_base_coords(base_coords)
+
+    def set_base_coords(self, coords):
+        """"pose" (or MH_ARTIC_BASE_POSE): switch to pose coordinates -- every world's pose from the model, the resident q / qd folded into it.
+        Floating bases without finite limits on the virtual joints only; there is no way back to angles."""
+        c = _BASE_COORDS.get(coords, coords)
+        _lib.check(_lib.load().mh_artic_batch_set_base_coords(self.handle, int(c)))
+
+    @property
+    def base_coords(self):
+        c = ctypes.c_int(-1)
+        _lib.check(_lib.load().mh_artic_batch_base_coords(self.handle, ctypes.byref(c)))
+        return {v: k for k, v in _BASE_COORDS.items()}[c.value]
+
+    def base_pose(self):
+        """(B, 7): px py pz (the base COM, model frame), qw qx qy qz (unit quaternion of the base's orientation); pose coordinates only"""
+        P = np.zeros((self.B, 7))
+        _lib.check(_lib.load().mh_artic_batch_base_pose(self.handle, P.ctypes.data))
+        return P
+
+    def set_base_pose(self, pose):
+        """(B, 7) as base_pose returns it; each quaternion is normalised, a zero or non-finite one refused.  With download / upload this is a
+        pose batch's checkpoint / restore."""
+        P = np.ascontiguousarray(pose, dtype=np.float64); assert P.shape == (self.B, 7)
+        _lib.check(_lib.load().mh_artic_batch_set_base_pose(self.handle, P.ctypes.data))
+
+    def base_pose_into(self, pose_t, stream=None):
+        """The poses into a float64 contiguous (B, 7) torch tensor on the batch's device, stream-ordered (no host sync)."""
+        _lib.check(_lib.load().mh_artic_batch_base_pose_dev(self.handle, stream, self._tensor_ptr(pose_t, (self.B, 7))))
 
     def upload(self, q=None, qd=None, aux=None):
         P = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data

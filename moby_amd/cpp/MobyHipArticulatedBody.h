@@ -9,6 +9,8 @@
 //   robots.step(5e-4, 200);                        // TimeSteppingSimulator::step x 200 in one launch (joint limits included)
 //   mh_artic_drive servo = { MH_DRIVE_PD, 1, kp, kv, q_des, qd_des, NULL };   // host arrays, B x nj (a controller plugin's PD law)
 //   robots.set_drive(servo); robots.step(5e-4, 200);   // ... now driven once per mini-step
+//   floater.set_base_coords(MH_ARTIC_BASE_POSE);     // a floating base carried as a pose per copy (no singular middle hinge)
+//   floater.base_pose(P); floater.set_base_pose(P);   // B x 7: COM px py pz, unit quaternion qw qx qy qz (checkpoint = q(), qd(), base_pose)
 //
 // Collision geometry (sphere primitives on links against one static plane, contacts with mu-coulomb >= 100 as ur10.xml:19 has
 // them) is part of the model: fill it before constructing the batch, e.g.
@@ -68,6 +70,11 @@ class BatchedArticulatedBody {
   void get_generalized_inertia(double* H /* B x nj x nj */) { std::vector<double> qdd((size_t)_B * _nj); if (mh_artic_batch_fwd_dyn(_ab, NULL, qdd.data(), H) != MH_OK) throw std::runtime_error(mh_last_error()); }
   // joint forces / PD servos evaluated inside every mini-step (mh_artic_drive: HOST arrays, copied to the device); terms = 0 clears
   void set_drive(const mh_artic_drive& drive) { if (mh_artic_batch_set_drive(_ab, &drive) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  // floating bases: MH_ARTIC_BASE_POSE folds the virtual joints into a per-copy base pose after every step (include/moby_hip_artic.h); one way
+  void set_base_coords(int coords) { if (mh_artic_batch_set_base_coords(_ab, coords) != MH_OK) throw std::runtime_error(mh_last_error()); _dirty = true; }
+  int base_coords() const { int c = 0; if (mh_artic_batch_base_coords(_ab, &c) != MH_OK) throw std::runtime_error(mh_last_error()); return c; }
+  void base_pose(double* pose /* B x 7 */) { if (mh_artic_batch_base_pose(_ab, pose) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  void set_base_pose(const double* pose /* B x 7 */) { if (mh_artic_batch_set_base_pose(_ab, pose) != MH_OK) throw std::runtime_error(mh_last_error()); }
   // with the drive of set_drive when one is set
   double step(double dt, int nsteps = 1) { if (mh_artic_batch_step_driven(_ab, NULL, dt, nsteps, NULL) != MH_OK) throw std::runtime_error(mh_last_error()); _dirty = true; return dt; }
   const std::vector<double>& q() { sync(); return _q; }

@@ -72,6 +72,9 @@ MH_DEV double crf_c(const double* v, const double* f, int k) { return (k < 3) ? 
 struct Lay {
   int nj;
   int q, qd, qdd, C, R, x, Rl, tl, S, I6, v, a, f, F, Iv, H, L, X, MM, A, art, Lv, l, idx, total;
+#ifdef MH_ARTIC_POSE_TU
+  int pR, pp, pQ;       // pose coordinates (mh_artic_pose.hip): the base pose R(Q) (9), p (3), Q (4), alive for the whole launch, behind everything else
+#endif
   // q, qd, qdd, C and H, L, X live for the whole step; the link quantities of dynamics() (R .. Iv) and the limit LCP's
   // storage (MM .. idx) are never alive together -- handle_limits reads q, qd, L, X only and the next dynamics() call
   // rebuilds everything from q, qd -- so they share one region: 10 KB per world at 10 joints = 16 worlds per CU
@@ -90,14 +93,31 @@ struct Lay {
     MM = o; o += nlcap * nlcap; A = o; o += nlcap * nlcap; art = o; o += nlcap; Lv = o; o += nlcap; l = o; o += nlcap;
     idx = o; o += nlcap;           // ints stored as doubles' slots (one int each, low half)
     total = (o > end_dyn) ? o : end_dyn;
+#ifdef MH_ARTIC_POSE_TU
+    pR = total; pp = pR + 9; pQ = pp + 3; total += 16;
+#endif
   }
 };
 constexpr int NLSTAB = 2 * NJ;      // the stabiliser's LCP has a row for every finite limit (CStab:257-304): up to two per joint
 static size_t lds_bytes(int nj, int nlcap = NLMAX) {
   const int n = nj;
   const int dyn = 78 * n + 12, lim = 2 * nlcap * nlcap + 4 * nlcap;
+#ifdef MH_ARTIC_POSE_TU
+  return sizeof(double) * (size_t)(4 * n + 3 * n * n + (dyn > lim ? dyn : lim) + 16);     // + Lay's pose slots
+#else
   return sizeof(double) * (size_t)(4 * n + 3 * n * n + (dyn > lim ? dyn : lim));
+#endif
 }
+
+// pose coordinates (MH_ARTIC_POSE_TU): the floating base's pose in LDS stands in for the model's trel[0] (the sliders' origin, the base COM) and
+// Rrel[3] (the first hinge's frame) -- exactly where the reference's per-world model copy puts them
+#ifdef MH_ARTIC_POSE_TU
+#define MH_RREL(i) (((i) == 3) ? (const double*)(g + Y.pR) : (const double*)m.Rrel[i])
+#define MH_TREL(i) (((i) == 0) ? (const double*)(g + Y.pp) : (const double*)m.trel[i])
+#else
+#define MH_RREL(i) m.Rrel[i]
+#define MH_TREL(i) m.trel[i]
+#endif
 
 // link frames, motion subspaces and spatial inertias about the world origin for the q in LDS (oracle Artic::kinematics)
 // PACK worlds per wavefront: PACK = 1 -- the whole wave works on the image at g; PACK = 2 -- lanes 0-31 and 32-63 each work on THEIR
@@ -119,14 +139,14 @@ MH_DEV void kin_inertia(const Model& M, const Lay& Y, double* g)
       const double K[9] = { 0.0, -ax[2], ax[1], ax[2], 0.0, -ax[0], -ax[1], ax[0], 0.0 };
       double Rq[9];
       for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) Rq[3*a+b] = (((a == b) ? c : 0.0) + (t * ax[a]) * ax[b]) + s * K[3*a+b];
-      mat3mul(m.Rrel[i], Rq, Rl);
-      for (int k = 0; k < 3; k++) tl[k] = m.trel[i][k];
+      mat3mul(MH_RREL(i), Rq, Rl);
+      for (int k = 0; k < 3; k++) tl[k] = MH_TREL(i)[k];
     } else {
-      for (int k = 0; k < 9; k++) Rl[k] = m.Rrel[i][k];
+      for (int k = 0; k < 9; k++) Rl[k] = MH_RREL(i)[k];
       double d[3], Rd[3];
       for (int k = 0; k < 3; k++) d[k] = ax[k] * qi;
-      mat3vec(m.Rrel[i], d, Rd);
-      for (int k = 0; k < 3; k++) tl[k] = m.trel[i][k] + Rd[k];
+      mat3vec(MH_RREL(i), d, Rd);
+      for (int k = 0; k < 3; k++) tl[k] = MH_TREL(i)[k] + Rd[k];
     }
     for (int k = 0; k < 9; k++) g[Y.Rl + 9 * i + k] = Rl[k];
     for (int k = 0; k < 3; k++) g[Y.tl + 3 * i + k] = tl[k];
@@ -621,7 +641,7 @@ __device__ __noinline__ void stabilize_limits(const Model& M, const Lay& Y, doub
   wave_sync();
 }
 
-#ifdef MH_ARTIC_DRIVE_TU
+#if defined(MH_ARTIC_DRIVE_TU) || defined(MH_ARTIC_POSE_TU)
 // The drive (moby_hip_artic.h, mh_artic_drive): lane j < nj evaluates tau_j of step s from q / qd in LDS -- q already advanced by the
 // mini-step's position update, qd still its starting velocity -- and leaves it in the qdd slot of the image: dynamics() reads
 // tau_w[lane] there before the same lane writes b[lane] (CRB), dynamics_aba() reads every tau_w[i] on lane 0 in its inward pass,
@@ -644,12 +664,77 @@ MH_DEV void drive_tau(const mh_artic_drive& D, int B, int b, int s, const Lay& Y
 }
 #endif
 
-// MH_ARTIC_DRIVE_TU (mh_artic_drive.hip): the same step with a drive -- the undriven kernels are compiled from exactly the code they had before drives existed
+#ifdef MH_ARTIC_POSE_TU
+// Pose coordinates of a floating base (moby_hip_artic.h, MH_ARTIC_BASE_POSE).  Operation order = tests/native/artic_pose_ref.cpp, bit for bit.
+// Hamilton product o = a (x) b, quaternions stored w, x, y, z
+MH_DEV void quat_mul(const double* a, const double* b, double* o)
+{
+  o[0] = ((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3];
+  o[1] = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2];
+  o[2] = ((a[0] * b[2] - a[1] * b[3]) + a[2] * b[0]) + a[3] * b[1];
+  o[3] = ((a[0] * b[3] + a[1] * b[2]) - a[2] * b[1]) + a[3] * b[0];
+}
+// R(Q), row-major, for a unit Q
+MH_DEV void quat_R(const double* Q, double* R)
+{
+  const double w = Q[0], x = Q[1], y = Q[2], z = Q[3];
+  const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+  R[0] = 1.0 - 2.0 * (yy + zz); R[1] = 2.0 * (xy - wz);       R[2] = 2.0 * (xz + wy);
+  R[3] = 2.0 * (xy + wz);       R[4] = 1.0 - 2.0 * (xx + zz); R[5] = 2.0 * (yz - wx);
+  R[6] = 2.0 * (xz - wy);       R[7] = 2.0 * (yz + wx);       R[8] = 1.0 - 2.0 * (xx + yy);
+}
+// The fold: the six virtual joints' coordinates into the pose, q[0..5] back to zero (one thread; q, qd: the world's joint arrays; p, Q, R: its
+// pose).  p += q[0..2] (the sum kinematics forms for the base COM); Q = normalize(Q (x) Qx(q3) (x) Qy(q4) (x) Qz(q5)); qd[3..5] = the base's
+// angular velocity in its new axes, Rh' (e_x qd3 + Rx e_y qd4 + Rx Ry e_z qd5) = Rz(q5)' (Ry(q4)' (e_x qd3 + e_y qd4) + e_z qd5), full-angle
+// sin / cos by the double-angle formulas from the half angles; qd[0..2] (the COM velocity, global axes) stay
+MH_DEV void pose_fold(double* q, double* qd, double* p, double* Q, double* R)
+{
+  for (int k = 0; k < 3; k++) p[k] = p[k] + q[k];
+  double s3, c3, s4, c4, s5, c5;
+  sincos_kernel(0.5 * q[3], s3, c3); sincos_kernel(0.5 * q[4], s4, c4); sincos_kernel(0.5 * q[5], s5, c5);
+  const double qx[4] = { c3, s3, 0.0, 0.0 }, qy[4] = { c4, 0.0, s4, 0.0 }, qz[4] = { c5, 0.0, 0.0, s5 };
+  double t1[4], t2[4], t3[4];
+  quat_mul(Q, qx, t1); quat_mul(t1, qy, t2); quat_mul(t2, qz, t3);
+  const double n = sqrt(((t3[0] * t3[0] + t3[1] * t3[1]) + t3[2] * t3[2]) + t3[3] * t3[3]);
+  for (int k = 0; k < 4; k++) Q[k] = t3[k] / n;
+  const double S4 = 2.0 * (s4 * c4), C4 = c4 * c4 - s4 * s4, S5 = 2.0 * (s5 * c5), C5 = c5 * c5 - s5 * s5;
+  const double u0 = C4 * qd[3], u1 = qd[4], u2 = S4 * qd[3] + qd[5];
+  qd[3] = C5 * u0 + S5 * u1; qd[4] = C5 * u1 - S5 * u0; qd[5] = u2;
+  for (int k = 0; k < 6; k++) q[k] = 0.0;
+  quat_R(Q, R);
+}
+// world b's pose from HBM (B x 7: p, Q) into the image's slots, R(Q) rebuilt; the caller syncs
+MH_DEV void pose_load(const Lay& Y, double* g, const double* __restrict__ pose)
+{
+  if (lane_id() == 0) {
+    for (int k = 0; k < 3; k++) g[Y.pp + k] = pose[k];
+    for (int k = 0; k < 4; k++) g[Y.pQ + k] = pose[3 + k];
+    quat_R(g + Y.pQ, g + Y.pR);
+  }
+}
+MH_DEV void pose_store(const Lay& Y, const double* g, double* __restrict__ pose)
+{
+  if (lane_id() == 0) { for (int k = 0; k < 3; k++) pose[k] = g[Y.pp + k]; for (int k = 0; k < 4; k++) pose[3 + k] = g[Y.pQ + k]; }
+}
+// after a step that ran to its end: lane 0 folds the image's q / qd into its pose
+MH_DEV void pose_fold_lds(const Lay& Y, double* g)
+{
+  wave_sync();
+  if (lane_id() == 0) pose_fold(g + Y.q, g + Y.qd, g + Y.pp, g + Y.pQ, g + Y.pR);
+  wave_sync();
+}
+#endif
+
+// MH_ARTIC_DRIVE_TU (mh_artic_drive.hip): the same step with a drive -- the undriven kernels are compiled from exactly the code they had before drives existed.
+// MH_ARTIC_POSE_TU (mh_artic_pose.hip): the same step in pose coordinates, driven when Dp is not NULL (a constant after inlining)
 template <bool STAB>
 MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                             mh_world_aux* __restrict__ auxg
 #ifdef MH_ARTIC_DRIVE_TU
                             , const mh_artic_drive& D
+#endif
+#ifdef MH_ARTIC_POSE_TU
+                            , const mh_artic_drive* Dp, double* __restrict__ poseg
 #endif
                             )
 {
@@ -661,6 +746,9 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
   const Lay Y(nj, STAB ? NLSTAB : NLMAX);
   mh_world_aux* aux = auxg + b;
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = qdg[(size_t)b * nj + lane]; }
+#ifdef MH_ARTIC_POSE_TU
+  pose_load(Y, g, poseg + 7 * (size_t)b);
+#endif
   WaveRand rng; rng.load(aux->rng);
   if (lane == 0) g_lcp_prof_on = 0;
   int status = uni(aux->status);
@@ -677,6 +765,11 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
     drive_tau(D, B, b, s, Y, g);                                      // precalc_fwd_dyn's controller (Simulator.cpp:319-350): lane j reads the q it just wrote
     wave_sync();
     const bool ok = (M.m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, g + Y.qdd) : dynamics(M, Y, g, g + Y.qdd);
+#elif defined(MH_ARTIC_POSE_TU)
+    if (Dp) drive_tau(*Dp, B, b, s, Y, g);
+    wave_sync();
+    const double* tw = Dp ? g + Y.qdd : nullptr;
+    const bool ok = (M.m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, tw) : dynamics(M, Y, g, tw);
 #else
     wave_sync();
     const bool ok = (M.m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, nullptr) : dynamics(M, Y, g, nullptr);
@@ -690,9 +783,15 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
     minis++;
     if (STAB) { stabilize_limits(M, Y, g, rng, status, solves, rows, pivs, bytes, stab_iters, stab_rows); if (status & MH_WORLD_LCP_FAILED) break; }   // TSS:97
     steps++;
+#ifdef MH_ARTIC_POSE_TU
+    pose_fold_lds(Y, g);                                              // after the stabiliser: the step ran to its end
+#endif
   }
   wave_sync();
   if (lane < nj) { qg[(size_t)b * nj + lane] = g[Y.q + lane]; qdg[(size_t)b * nj + lane] = g[Y.qd + lane]; }
+#ifdef MH_ARTIC_POSE_TU
+  pose_store(Y, g, poseg + 7 * (size_t)b);
+#endif
   rng.store(aux->rng);
   if (lane == 0) {
     double tm = aux->time; for (int s = 0; s < minis; s++) tm += dt;
@@ -703,7 +802,7 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
   }
 }
 
-#ifndef MH_ARTIC_DRIVE_TU
+#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
 // The same step at three register budgets: 128 VGPRs (4 waves per SIMD = the 16 worlds per CU the 10 KB LDS image allows; 95 spilled
 // VGPRs), 168 (3 per SIMD, 14 spilled) and 193 (2 per SIMD, none).  The kernel waits on ~250 LDS round trips per step, so
 // resident waves win over spills: ur10 x 8192, 200 steps: 25.6 / 31.2 / 39.0 ms (profiles/r02_c_artic_occupancy.jsonl).
@@ -789,12 +888,24 @@ void k_artic_step_p2(const Model* __restrict__ Mg, int B, double dt, int nsteps,
 __global__ __launch_bounds__(64)
 void k_artic_step_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                        mh_world_aux* __restrict__ auxg) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg); }
+#endif
 
+#ifndef MH_ARTIC_DRIVE_TU
+// k_artic_fwd_dyn / k_artic_jacobian, and in pose coordinates k_artic_fwd_dyn_pose / k_artic_jacobian_pose: one more argument, the B x 7 poses
+#ifdef MH_ARTIC_POSE_TU
+#define MH_POSE_KERNEL(name) name##_pose
+#define MH_POSE_ARG , const double* __restrict__ poseg
+#define MH_POSE_LOAD() pose_load(Y, g, poseg + 7 * (size_t)b)
+#else
+#define MH_POSE_KERNEL(name) name
+#define MH_POSE_ARG
+#define MH_POSE_LOAD() ((void)0)
+#endif
 // seam B4: qdd = H^-1 (tau - C), H, link poses of the resident states
 __global__ __launch_bounds__(64)
-void k_artic_fwd_dyn(const Model* __restrict__ Mg, int B, const double* __restrict__ qg, const double* __restrict__ qdg,
+void MH_POSE_KERNEL(k_artic_fwd_dyn)(const Model* __restrict__ Mg, int B, const double* __restrict__ qg, const double* __restrict__ qdg,
                      const double* __restrict__ tau, double* __restrict__ qdd_out, double* __restrict__ H_out, double* __restrict__ poses,
-                     int* __restrict__ okflag)
+                     int* __restrict__ okflag MH_POSE_ARG)
 {
   extern __shared__ double g[];
   const int b = blockIdx.x;
@@ -803,6 +914,7 @@ void k_artic_fwd_dyn(const Model* __restrict__ Mg, int B, const double* __restri
   const int nj = M.m.nj, lane = lane_id();
   const Lay Y(nj);
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = qdg[(size_t)b * nj + lane]; }
+  MH_POSE_LOAD();
   wave_sync();
   const double* tw = tau ? tau + (size_t)b * nj : nullptr;
   bool ok;
@@ -822,8 +934,8 @@ void k_artic_fwd_dyn(const Model* __restrict__ Mg, int B, const double* __restri
 
 // calc_jacobian: column j = the twist of joint j (S_j, about the world origin) moved to the point, for j on the link's path
 __global__ __launch_bounds__(64)
-void k_artic_jacobian(const Model* __restrict__ Mg, int B, const double* __restrict__ qg, int link, const double* __restrict__ points,
-                      double* __restrict__ J_out)
+void MH_POSE_KERNEL(k_artic_jacobian)(const Model* __restrict__ Mg, int B, const double* __restrict__ qg, int link, const double* __restrict__ points,
+                      double* __restrict__ J_out MH_POSE_ARG)
 {
   extern __shared__ double g[];
   const int b = blockIdx.x;
@@ -832,6 +944,7 @@ void k_artic_jacobian(const Model* __restrict__ Mg, int B, const double* __restr
   const int nj = M.m.nj, lane = lane_id();
   const Lay Y(nj);
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = 0.0; }
+  MH_POSE_LOAD();
   wave_sync();
   kin_inertia(M, Y, g);
   const double* p = points + (size_t)b * 3;
@@ -846,8 +959,9 @@ void k_artic_jacobian(const Model* __restrict__ Mg, int B, const double* __restr
     J_out[(size_t)b * 6 * nj + e] = v;
   }
 }
+#endif
 
-#else   // the driven step kernels: their own code object (mh_artic_drive.hip)
+#if defined(MH_ARTIC_DRIVE_TU)   // the driven step kernels: their own code object (mh_artic_drive.hip)
 // the four budgets of k_artic_step_w{2..5} with a drive (mh_artic_batch_step_driven)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_artic_step_w3_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
@@ -866,6 +980,31 @@ void k_artic_step_w2_drive(const Model* __restrict__ Mg, int B, double dt, int n
 __global__ __launch_bounds__(64)
 void k_artic_step_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                              mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
+#elif defined(MH_ARTIC_POSE_TU)  // the pose-coordinate step kernels: their own code object (mh_artic_pose.hip)
+// the default budget of k_artic_step_w4 (MH_ARTIC_WAVES and MH_ARTIC_PACK do not apply in pose coordinates), undriven and driven
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_artic_step_w4_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                          mh_world_aux* __restrict__ auxg, double* __restrict__ poseg) { artic_step_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, nullptr, poseg); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_artic_step_w4_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                mh_world_aux* __restrict__ auxg, double* __restrict__ poseg, mh_artic_drive D) { artic_step_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, &D, poseg); }
+// k_artic_step_stab in pose coordinates, undriven and driven
+__global__ __launch_bounds__(64)
+void k_artic_step_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ poseg) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ poseg, mh_artic_drive D) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, &D, poseg); }
+// the switch from angles to pose coordinates (mh_artic_batch_set_base_coords): one thread per world folds its resident q / qd into the pose the
+// host wrote (the model's); a world carrying MH_WORLD_LCP_FAILED keeps its q, which still describe its configuration against that pose
+__global__ __launch_bounds__(64)
+void k_artic_pose_fold(int B, int nj, double* __restrict__ qg, double* __restrict__ qdg, const mh_world_aux* __restrict__ auxg, double* __restrict__ poseg)
+{
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B || (auxg[b].status & MH_WORLD_LCP_FAILED)) return;
+  double R[9];
+  pose_fold(qg + (size_t)b * nj, qdg + (size_t)b * nj, poseg + 7 * (size_t)b, poseg + 7 * (size_t)b + 3, R);
+}
 #endif
 
 #include "mh_artic_contacts.inc"
@@ -880,7 +1019,15 @@ struct mh_artic_batch {
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
   mh_artic_drive drive;   // the drive of mh_artic_batch_set_drive (terms 0 = none); its arrays live in d_drive
   double* d_drive;
+  int base_coords;        // MH_ARTIC_BASE_ANGLES / MH_ARTIC_BASE_POSE (mh_artic_batch_set_base_coords)
+  double* d_pose;         // pose coordinates: B x 7 (p, Q) per world; NULL in angle coordinates
 };
+
+// the pose-coordinate launches (mh_artic_pose.hip): the step (D NULL or terms 0 = undriven; arguments checked by the caller), and the
+// kernels of mh_artic_batch_fwd_dyn / link_poses / jacobian on the null stream
+int artic_pose_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+hipError_t artic_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
+hipError_t artic_pose_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
 static int check_drive(const mh_artic_drive* d, int nsteps)
@@ -893,7 +1040,7 @@ static int check_drive(const mh_artic_drive* d, int nsteps)
   return MH_OK;
 }
 
-#ifndef MH_ARTIC_DRIVE_TU
+#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
 extern "C" {
 
 int mh_artic_batch_device(const mh_artic_batch* ab) { return ab ? ab->device : fail(MH_ERR_INVALID_ARG, "null batch"); }
@@ -903,7 +1050,7 @@ int mh_artic_batch_destroy(mh_artic_batch* ab)
   if (!ab) return MH_OK;
   MH_ON_DEVICE(ab);
   (void)hipDeviceSynchronize();
-  void* ps[] = { ab->d_model, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws, ab->d_drive };
+  void* ps[] = { ab->d_model, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws, ab->d_drive, ab->d_pose };
   for (void* p : ps) if (p) (void)hipFree(p);
   delete ab;
   return MH_OK;
@@ -979,6 +1126,7 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
   ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
+  ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;
   bool ok = hipMalloc((void**)&ab->d_model, sizeof(ar::Model)) == hipSuccess && hipMalloc((void**)&ab->d_q, sB * nj * 8) == hipSuccess
          && hipMalloc((void**)&ab->d_qd, sB * nj * 8) == hipSuccess && hipMalloc((void**)&ab->d_aux, sB * sizeof(mh_world_aux)) == hipSuccess;
@@ -1017,6 +1165,7 @@ int mh_artic_batch_step(mh_artic_batch* ab, void* stream, double dt, int nsteps)
   if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
   if (nsteps == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
+  if (ab->base_coords == MH_ARTIC_BASE_POSE) return artic_pose_step(ab, stream, dt, nsteps, nullptr);
   if (ab->nspheres > 0) {                                     // bodies with collision geometry: the full step with mini-steps and contact rows
     hipLaunchKernelGGL(ab->cstab ? ar::k_artic_step_contacts_stab : ar::k_artic_step_contacts, dim3(ab->B), dim3(64), ar::lds_bytes_contacts(ab->nj), (hipStream_t)stream,
                        (const ar::Model*)ab->d_model, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws);
@@ -1095,9 +1244,11 @@ int mh_artic_batch_fwd_dyn(mh_artic_batch* ab, const double* tau, double* qdd_ou
   if (ok && tau) ok = hipMalloc((void**)&d_tau, B * nj * 8) == hipSuccess && hipMemcpy(d_tau, tau, B * nj * 8, hipMemcpyHostToDevice) == hipSuccess;
   if (ok && H_out) ok = hipMalloc((void**)&d_H, B * nj * nj * 8) == hipSuccess;
   if (!ok) { cleanup(); return fail(MH_ERR_HIP, "device allocation failed"); }
-  hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
-                     (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)d_tau, d_qdd, d_H, (double*)nullptr, d_ok);
-  hipError_t e = hipDeviceSynchronize();
+  hipError_t e = hipSuccess;
+  if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok);
+  else hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+                          (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)d_tau, d_qdd, d_H, (double*)nullptr, d_ok);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
   std::vector<int> hok(B);
   if (e == hipSuccess && qdd_out) e = hipMemcpy(qdd_out, d_qdd, B * nj * 8, hipMemcpyDeviceToHost);
   if (e == hipSuccess && H_out) e = hipMemcpy(H_out, d_H, B * nj * nj * 8, hipMemcpyDeviceToHost);
@@ -1117,9 +1268,11 @@ int mh_artic_batch_link_poses(mh_artic_batch* ab, double* poses)
   const size_t bytes = (size_t)ab->B * ab->nj * 12 * 8;
   double* d_p = nullptr;
   MH_HIP(hipMalloc((void**)&d_p, bytes));
-  hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
-                     (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)nullptr, (double*)nullptr, (double*)nullptr, d_p, (int*)nullptr);
-  hipError_t e = hipDeviceSynchronize();
+  hipError_t e = hipSuccess;
+  if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr);
+  else hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+                          (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)nullptr, (double*)nullptr, (double*)nullptr, d_p, (int*)nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(poses, d_p, bytes, hipMemcpyDeviceToHost);
   (void)hipFree(d_p);
   if (e != hipSuccess) return fail(MH_ERR_HIP, "link pose launch failed: %s", hipGetErrorString(e));
@@ -1139,9 +1292,10 @@ int mh_artic_batch_jacobian(mh_artic_batch* ab, int link, const double* points, 
   hipError_t e = hipMalloc((void**)&d_J, jb);
   if (e == hipSuccess) e = hipMemcpy(d_p, points, pb, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(ar::k_artic_jacobian, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
-                       (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, link, (const double*)d_p, d_J);
-    e = hipDeviceSynchronize();
+    if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_jacobian_launch(ab, link, d_p, d_J);
+    else hipLaunchKernelGGL(ar::k_artic_jacobian, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+                            (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, link, (const double*)d_p, d_J);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess) e = hipMemcpy(J_out, d_J, jb, hipMemcpyDeviceToHost);
   (void)hipFree(d_p); if (d_J) (void)hipFree(d_J);

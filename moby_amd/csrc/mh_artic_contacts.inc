@@ -543,6 +543,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_DRIVE_TU
                            , const mh_artic_drive& D, int B, int b, int s
 #endif
+#ifdef MH_ARTIC_POSE_TU
+                           , const mh_artic_drive* Dp, int B, int b, int s
+#endif
                            )
 {
   const mh_artic_model& m = M.m;
@@ -573,6 +576,10 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_DRIVE_TU
   drive_tau(D, B, b, s, Y, g);                                    // (read by the dynamics after kin_inertia's barriers)
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, g + Y.qdd) : dynamics(M, Y, g, g + Y.qdd);
+#elif defined(MH_ARTIC_POSE_TU)
+  if (Dp) drive_tau(*Dp, B, b, s, Y, g);
+  const double* tw = Dp ? g + Y.qdd : nullptr;
+  const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, tw) : dynamics(M, Y, g, tw);
 #else
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, nullptr) : dynamics(M, Y, g, nullptr);
 #endif
@@ -842,6 +849,9 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #ifdef MH_ARTIC_DRIVE_TU
                                 , const mh_artic_drive& D
 #endif
+#ifdef MH_ARTIC_POSE_TU
+                                , const mh_artic_drive* Dp, double* __restrict__ poseg
+#endif
                                 )
 {
   extern __shared__ double g[];
@@ -854,6 +864,9 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   mh_world_aux* aux = auxg + b;
   double* ws = wsg ? wsg + (size_t)b * 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE : nullptr;   // Drumwright-Shell: _MM and the Lemke LU workspace
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = qdg[(size_t)b * nj + lane]; }
+#ifdef MH_ARTIC_POSE_TU
+  pose_load(Y, g, poseg + 7 * (size_t)b);
+#endif
   WaveRand rng; rng.load(aux->rng);
   if (lane == 0) g_lcp_prof_on = 0;
   int status = uni(aux->status);
@@ -868,6 +881,8 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
     while (h < dt) {
 #ifdef MH_ARTIC_DRIVE_TU
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, D, B, b, s));
+#elif defined(MH_ARTIC_POSE_TU)
+      const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s));
 #else
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes));
 #endif
@@ -889,8 +904,15 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
       if (status & MH_WORLD_LCP_FAILED) break;                    // compute_X threw inside the stabiliser
     }
     steps++;
+#ifdef MH_ARTIC_POSE_TU
+    pose_fold_lds(Y, g);                                          // new coordinates: the link frames in LDS are the same only to round-off
+    kin_ok = false;
+#endif
   }
   if (lane < nj) { qg[(size_t)b * nj + lane] = g[Y.q + lane]; qdg[(size_t)b * nj + lane] = g[Y.qd + lane]; }
+#ifdef MH_ARTIC_POSE_TU
+  pose_store(Y, g, poseg + 7 * (size_t)b);
+#endif
   rng.store(aux->rng);
   if (lane == 0) {
     aux->time = tm; aux->status = status;
@@ -900,7 +922,7 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   }
 }
 
-#ifndef MH_ARTIC_DRIVE_TU
+#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
 // 2 waves per SIMD = the 8 worlds per CU the 18 KB LDS image allows
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
@@ -909,7 +931,7 @@ void k_artic_step_contacts(const Model* __restrict__ Mg, int B, double dt, int n
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg); }
-#else
+#elif defined(MH_ARTIC_DRIVE_TU)
 // the same two with a drive (mh_artic_batch_step_driven)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
@@ -917,4 +939,18 @@ void k_artic_step_contacts_drive(const Model* __restrict__ Mg, int B, double dt,
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, D); }
+#else
+// the two in pose coordinates, undriven and driven (mh_artic_pose.hip)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_artic_step_contacts_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_artic_step_contacts_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                      mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_artic_step_contacts_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                     mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_artic_step_contacts_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                           mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
 #endif
