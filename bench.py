@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; --dump-outputs: see dump_outputs below)
+
+A plain run does only what the headline figure needs: build (a no-op when the build is current), set up the batch, warm up,
+time the K steps, write --dump-outputs, print the result line.  Everything else the benchmark measures -- the CPU baselines,
+the other configurations, the strong-scaling leg, the long-horizon leg -- runs only with --full (the --no-* options then
+leave single legs out).
 
 Workload (config.workload): BASELINE.json configs[1] -- sphere-stack x4096:
 4096 independent instances of /root/reference/example/stacks/sphere-stack.xml
@@ -16,12 +21,12 @@ leaves the GPU between steps); inputs are resident in HBM before the clock start
 
 N > 1 started as plain `python bench.py --gpus N ...` (no RANK in the environment) re-launches itself under
 `python -m torch.distributed.run` as a CHILD process before anything touches the GPU and returns the child's exit code.
-`scaling` is "weak" (`--worlds` per GPU, the headline `value`); for N > 1 the same line also carries `strong_scaling`:
+`scaling` is "weak" (`--worlds` per GPU, the headline `value`); with --full, for N > 1 the same line also carries `strong_scaling`:
 ONE batch of `--worlds` split N ways (4096 / 8 = 512 worlds per GPU = 2 waves per CU), timed the same way.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel) and
+Prints ONE JSON line on rank 0 with `roofline` (dominant kernel) and, with --full,
 `cpu_baseline` (the CPU oracle on the host cores; rank 0, N = 1 only).
-Informational legs (rank 0, N = 1, outside the timed region): `config4_impact_handler` -- 4-box stacks x1024 through the
+Informational legs (--full; rank 0, N = 1, outside the timed region): `config4_impact_handler` -- 4-box stacks x1024 through the
 impact-handler entry (include/moby_hip_impact.h), one cold and one warm call; `config4_full_step` -- box stacks as full
 simulator steps (include/moby_hip_stack.h); `config5_ur10` -- the ur10 arm x8192 (include/moby_hip_artic.h);
 `config2_full_run` -- the headline batch's whole
@@ -690,6 +695,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--worlds", type=int, default=WORLDS_PER_GPU)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run the CPU baselines, the other configurations, the long-horizon leg and, for N > 1, the strong-scaling leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config3", action="store_true")
     ap.add_argument("--no-config4", action="store_true")
@@ -721,8 +728,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
+    legs = args.full and rank == 0 and world_size == 1     # the legs besides the headline figure
     cpu = c3cpu = c4cpu_part = c5cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if legs and not args.no_cpu_baseline:
         # every CPU sample runs here, BEFORE the GPU is initialised (the worker pools fork) and before any GPU leg is timed
         cpu = cpu_baseline(args.worlds, args.steps, args.warmup)
         if not args.no_config3:
@@ -805,7 +813,7 @@ def main():
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
-        "scaling_note": "`value` is WEAK scaling: every GPU steps its own %d worlds (N x %d in all) -- the figure north_star's >= 6x at 8 GPUs is read on.  For N > 1 the same line "
+        "scaling_note": "`value` is WEAK scaling: every GPU steps its own %d worlds (N x %d in all) -- the figure north_star's >= 6x at 8 GPUs is read on.  With --full, for N > 1 the same line "
                         "carries `strong_scaling`: ONE batch of %d worlds split N ways (%d / 8 = 512 worlds per GPU = half a wave per SIMD of a kernel whose time is one "
                         "wave's dependent chain): it cannot approach 6x by construction and is reported for completeness" % (B, B, B, B),
         "vs_baseline": None,
@@ -825,24 +833,24 @@ def main():
                      "model": "LCP-entry bytes 8(n^2+2n) per solved LCP (SURVEY 8d); the fused kernel itself only moves %d B of state per launch" % int(fused_bytes)},
     }
 
-    if world_size > 1:
+    if args.full and world_size > 1:
         out["strong_scaling"] = strong_leg(dist, mdist, S, lambda f, c: WorldBatchDevice(sc, S.sphere_stack_state_range(f, c)), B, rank, world_size, dev,
                                            args.steps, args.warmup, torch.cuda.synchronize, stream)
     if cpu is not None:
         out["cpu_baseline"] = cpu
-    if rank == 0 and world_size == 1 and not args.no_long_horizon:
+    if legs and not args.no_long_horizon:
         out["config2_full_run"] = config2_full_run_leg(torch, S, WorldBatchDevice, B)   # after the timed region; informational
         out["long_horizon"] = long_horizon_leg(torch, wb, stream, B, args)   # after the timed region; informational
-    if rank == 0 and world_size == 1 and not args.no_config4:
+    if legs and not args.no_config4:
         out["config4_impact_handler"] = config4_leg(torch)             # after the timed region; informational
         out["config4_full_step"] = config4_full_step_leg(torch, args.config4_boxes, args.config4_worlds, args.config4_steps, None, c4cpu_part)
-    if rank == 0 and world_size == 1 and not args.no_config4 and args.config4_tall_boxes > 0:
+    if legs and not args.no_config4 and args.config4_tall_boxes > 0:
         out["config4_tall_stack"] = config4_full_step_leg(torch, args.config4_tall_boxes, args.config4_tall_worlds, 1, None, None,
             note="the largest stack of BASELINE config 4's family of which 64 worlds take one full COLD step well inside 60 s on one MI355X (28 boxes: 36-38 s; 32 boxes, "
                  "n = 1024: 55-60 s; BASELINE's own 64 boxes, n = 2048: 135 s for 64 worlds, 62 of them ending in LCPSolverException -- tests/test_big_gpu.py holds 64 boxes x 8 worlds to the oracle's fixture)")
-    if rank == 0 and world_size == 1 and not args.no_config3:
+    if legs and not args.no_config3:
         out["config3_rimless_wheel"] = config3_leg(torch, S, WorldBatchDevice, c3cpu)
-    if rank == 0 and world_size == 1 and not args.no_config5:
+    if legs and not args.no_config5:
         out["config5_ur10"] = config5_leg(torch, cpu=not args.no_cpu_baseline, cpu_part=c5cpu)
     if rank == 0:
         print(json.dumps(out))

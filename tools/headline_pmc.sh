@@ -5,7 +5,7 @@ set -e
 TAG=${1:-headline}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-config4 --no-long-horizon --no-config5"
+CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-config4 --no-long-horizon --no-config5"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -- $CMD > $OUT/bench_under_rocprof.json 2> $OUT/ks.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > /dev/null 2> $OUT/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > /dev/null 2> $OUT/write.err

@@ -7,10 +7,10 @@ TAG=${1:-session}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python3 bench.py --no-cpu-baseline --no-config4 --no-long-horizon --no-config5"
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+CMD="python3 bench.py --full --no-cpu-baseline --no-config4 --no-long-horizon --no-config5"
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done" > $OUT/progress.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -- python3 bench.py --no-cpu-baseline --no-config4 --no-long-horizon > $OUT/bench_under_rocprof.json 2> $OUT/ks.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -- python3 bench.py --full --no-cpu-baseline --no-config4 --no-long-horizon > $OUT/bench_under_rocprof.json 2> $OUT/ks.err
 echo "ks done" >> $OUT/progress.txt
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > /dev/null 2> $OUT/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > /dev/null 2> $OUT/write.err

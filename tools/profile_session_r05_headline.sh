@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 DRV="--gpus 1 --steps 20 --warmup 5"
 CMD="python3 bench.py $DRV --no-cpu-baseline --no-config3 --no-config4 --no-long-horizon --no-config5"
 echo "$CMD" > $OUT/command.txt
-python3 bench.py $DRV > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py $DRV --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done" > $OUT/progress.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -- $CMD > $OUT/bench_under_rocprof.json 2> $OUT/ks.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > /dev/null 2> $OUT/fetch.err

@@ -8,7 +8,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMIT = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None   # the build the session ran (commit before profiling)
 P = os.path.join(ROOT, "profiles")
-CMDTXT = open(os.path.join(src, "command.txt")).read().strip() if os.path.exists(os.path.join(src, "command.txt")) else "python3 bench.py --no-cpu-baseline --no-config4 --no-long-horizon --no-config5"
+CMDTXT = open(os.path.join(src, "command.txt")).read().strip() if os.path.exists(os.path.join(src, "command.txt")) else "python3 bench.py --full --no-cpu-baseline --no-config4 --no-long-horizon --no-config5"
 one = lambda pat: (glob.glob(os.path.join(src, pat)) or [None])[0]
 shutil.copy(os.path.join(src, "bench.json"), os.path.join(P, tag + "_bench.json"))
 if os.path.exists(os.path.join(src, "bench_under_rocprof.json")):
