@@ -242,6 +242,8 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    measured no faster, profiles/r04_a_artic_issue.json).
                                             key 10: lcp_fast in the 1024-thread geometry solves a nonbasic system of up to 191 rows in the registers of
                                                    its sixteen waves (1, default) or through the HBM workspace (0).
+                                            key 12: sphere-only articulated bodies stepped by the box kernels (1, for batches created after it; default 0: their own kernels;
+                                                   include/moby_hip_artic.h, mh_artic_model.nboxes).
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);

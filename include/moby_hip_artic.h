@@ -39,6 +39,7 @@ extern "C" {
 #define MH_ARTIC_CRB  0
 #define MH_ARTIC_FSAB 1
 #define MH_ARTIC_MAX_SPHERES 4    /* sphere primitives carried by links (contacts against the one static plane) */
+#define MH_ARTIC_MAX_BOXES 8      /* box primitives carried by links (the same plane) */
 
 /* Joint i carries link i; joints are listed parents first.  A link may be massless as long as its joint moves mass (something outboard of it has mass).  All quantities are LOCAL (constant), as a reader of
  * model.sdf derives them once at q = 0 (mh_io_load_sdf, moby_amd/host/mh_io.cpp):
@@ -101,6 +102,29 @@ typedef struct mh_artic_model {
    * at least NEAR_ZERO, find_contacts' otherwise; Cn_v = distance - |eps| - NEAR_ZERO, CStab:431) and the mixed LCP
    * MM = [Cn X Cn'  Cn X L'; .  L X L'] (CStab:705-904, 932-970); update_q's line search then evaluates the sphere distances too. */
   double cstab_eps;                                /* ConstraintStabilization::eps ("unilateral-stabilization-tol"), default NEAR_ZERO (CStab:59) */
+  /* Box primitives fixed to links against the same static plane (appended: every field above keeps its offset).  They share plane_R / plane_o,
+   * the cp_* ContactParameters, min_step_size and contact_dist_thresh with the spheres.  A box is BoxPrimitive (full edge lengths, as
+   * mh_scene.geom_dim) with its centre and axes in its link's frame; vertices in BoxPrimitive::get_vertices order (BoxPrimitive.cpp:358-365):
+   * vertex i = centre + R (+-xlen/2, +-ylen/2, +-zlen/2), the minus sign on x / y / z when bit 2 / 1 / 0 of i is set.
+   *   contacts         find_contacts_plane_generic (CCD.inl:848-886): every vertex whose plane-frame height is <= TOL gives one contact AT the
+   *                    vertex, normal = the plane's.  Canonical order: the spheres in index order, then the boxes in index order, each box's
+   *                    vertices in get_vertices order.
+   *   signed distance  BoxPrimitive::calc_signed_dist -> PlanePrimitive (the lowest vertex's height; the first vertex wins ties)
+   *   conservative     calc_CA_Euler_step_generic (CCD.cpp:169-235): distance > 0 -> dist / calc_max_dist(link, -n0, rmax), the same articulated
+   *   advancement      calc_max_dist as the spheres', rmax = the box's full diagonal + |link COM - box centre| (CollisionGeometry.cpp:52-68);
+   *                    distance <= 0 -> calc_next_CA_Euler_step_generic: no vertex within NEAR_ZERO = no bound; a vertex approaching = 0; three
+   *                    non-collinear contacts among the FIRST three = rest (CCD.cpp:285-323); otherwise calc_next_CA_Euler_step_polyhedron_plane
+   *                    (CCD.cpp:405-468) with the link's angular velocity and its linear velocity at the box centre, in box axes.
+   *   stabiliser       per (box, plane) pair (CStab:306-345): distance >= NEAR_ZERO -> one contact at the lowest vertex, normal towards its
+   *                    projection on the plane; otherwise the vertex contacts within NEAR_ZERO.  cstab_eval reads the spheres', then the boxes' distances.
+   * Capacity (the oracle's rules in handle_impacts / stabilize): no-slip NC + NL <= MH_NOSLIP_MAX, Drumwright-Shell N <= MH_LCP_MAX_N_WAVE, the
+   * stabiliser's n <= MH_LCP_MAX_N_WAVE; a world beyond them carries MH_WORLD_UNSUPPORTED and its run ends, as for spheres.  Models with boxes
+   * step through their own kernels (mh_artic_box.hip); sphere-only models keep theirs (mh_debug_set(12, 1) sends them through the box kernels). */
+  int    nboxes;
+  int    box_link[MH_ARTIC_MAX_BOXES];
+  double box_center[MH_ARTIC_MAX_BOXES][3];        /* link frame */
+  double box_R[MH_ARTIC_MAX_BOXES][9];             /* the box's axes in the link frame, row-major, orthonormal */
+  double box_len[MH_ARTIC_MAX_BOXES][3];           /* full edge lengths xlen ylen zlen, > 0 */
 } mh_artic_model;
 
 /* B worlds resident on the GPU: joint positions q and velocities qd (B x nj each) + mh_world_aux (rand() stream, time,

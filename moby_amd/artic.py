@@ -17,8 +17,10 @@ from . import scene as S
 MH_ARTIC_MAX_JOINTS = 16
 MH_JOINT_REVOLUTE, MH_JOINT_PRISMATIC = 0, 1
 MH_ARTIC_MAX_SPHERES = 4
+MH_ARTIC_MAX_BOXES = 8
 _NJ = MH_ARTIC_MAX_JOINTS
 _NS = MH_ARTIC_MAX_SPHERES
+_NB = MH_ARTIC_MAX_BOXES
 
 
 class mh_artic_model(ctypes.Structure):
@@ -31,7 +33,9 @@ class mh_artic_model(ctypes.Structure):
                 ("sphere_radius", ctypes.c_double * _NS), ("plane_R", ctypes.c_double * 9), ("plane_o", ctypes.c_double * 3),
                 ("cp_epsilon", ctypes.c_double), ("cp_mu_coulomb", ctypes.c_double), ("min_step_size", ctypes.c_double),
                 ("contact_dist_thresh", ctypes.c_double), ("cp_mu_viscous", ctypes.c_double), ("cp_compliance", ctypes.c_double),
-                ("cp_nk", ctypes.c_int), ("cstab_max_iterations", ctypes.c_int), ("cstab_eps", ctypes.c_double)]
+                ("cp_nk", ctypes.c_int), ("cstab_max_iterations", ctypes.c_int), ("cstab_eps", ctypes.c_double),
+                ("nboxes", ctypes.c_int), ("box_link", ctypes.c_int * _NB), ("box_center", (ctypes.c_double * 3) * _NB),
+                ("box_R", (ctypes.c_double * 9) * _NB), ("box_len", (ctypes.c_double * 3) * _NB)]
 
 
 MH_ARTIC_CRB, MH_ARTIC_FSAB = 0, 1      # moby_hip_artic.h: RCArticulatedBody::algorithm_type
@@ -177,16 +181,30 @@ def add_spheres(model, spheres, plane_normal=(0.0, 0.0, 1.0), plane_point=(0.0, 
     plane through plane_point with the given normal (the +Y axis of the plane frame, as PlanePrimitive has it); the
     ContactParameters of the (robot, plane) pair (ur10.xml:19: epsilon 0, mu-coulomb 100).  Returns the model."""
     assert 0 < len(spheres) <= MH_ARTIC_MAX_SPHERES
+    Rp = _plane_frame(model, plane_normal, plane_point, model.nboxes > 0)
     model.nspheres = len(spheres)
     for i, (link, c, r) in enumerate(spheres):
         assert 0 <= link < model.nj and r > 0
         model.sphere_link[i] = int(link); model.sphere_radius[i] = float(r)
         for k in range(3):
             model.sphere_center[i][k] = float(c[k])
+    _set_plane(model, Rp, plane_point, epsilon, mu_coulomb, mu_viscous, compliance, nk)
+    return model
+
+
+def _plane_frame(model, plane_normal, plane_point, shared):
+    """The plane frame of a normal (its +Y axis); shared: the model's other kind of primitive already has a plane -- refuse one that disagrees."""
     n = np.asarray(plane_normal, dtype=float); n = n / np.linalg.norm(n)
     e = np.eye(3)[int(np.argmin(np.abs(n)))]
     xax = np.cross(n, e); xax = xax / np.linalg.norm(xax); zax = np.cross(xax, n)
     Rp = np.column_stack([xax, n, zax])                       # columns: the plane frame's axes; +Y = normal
+    if shared:
+        if list(Rp.flat) != list(model.plane_R) or [float(v) for v in plane_point] != list(model.plane_o):
+            raise ValueError("the model's spheres and boxes share one plane: this one disagrees with the plane already set")
+    return Rp
+
+
+def _set_plane(model, Rp, plane_point, epsilon, mu_coulomb, mu_viscous, compliance, nk):
     for k in range(9):
         model.plane_R[k] = Rp.flat[k]
     for k in range(3):
@@ -195,6 +213,26 @@ def add_spheres(model, spheres, plane_normal=(0.0, 0.0, 1.0), plane_point=(0.0, 
     model.cp_mu_viscous = float(mu_viscous); model.cp_compliance = float(compliance); model.cp_nk = int(nk)
     model.min_step_size = S.NEAR_ZERO
     model.contact_dist_thresh = 1e-6
+
+
+def add_boxes(model, boxes, plane_normal=(0.0, 0.0, 1.0), plane_point=(0.0, 0.0, 0.0), epsilon=0.0, mu_coulomb=100.0, mu_viscous=0.0,
+              compliance=0.0, nk=4):
+    """Box primitives on links against the model's one static plane (include/moby_hip_artic.h, mh_artic_model.nboxes):
+    boxes = [(link, centre in the link frame, R (the box's axes in the link frame, 3x3), (xlen, ylen, zlen) full edge lengths), ...].
+    The plane and the ContactParameters are those of add_spheres, shared with the spheres (one set per model: the last call sets the
+    parameters; a plane that disagrees with one already set is refused).  Returns the model."""
+    assert 0 < len(boxes) <= MH_ARTIC_MAX_BOXES
+    Rp = _plane_frame(model, plane_normal, plane_point, model.nspheres > 0)
+    model.nboxes = len(boxes)
+    for i, (link, c, R, dims) in enumerate(boxes):
+        R = np.asarray(R, dtype=float).reshape(3, 3)
+        assert 0 <= link < model.nj and all(d > 0 for d in dims)
+        model.box_link[i] = int(link)
+        for k in range(3):
+            model.box_center[i][k] = float(c[k]); model.box_len[i][k] = float(dims[k])
+        for k in range(9):
+            model.box_R[i][k] = R.flat[k]
+    _set_plane(model, Rp, plane_point, epsilon, mu_coulomb, mu_viscous, compliance, nk)
     return model
 
 

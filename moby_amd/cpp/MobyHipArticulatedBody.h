@@ -12,9 +12,10 @@
 //   floater.set_base_coords(MH_ARTIC_BASE_POSE);     // a floating base carried as a pose per copy (no singular middle hinge)
 //   floater.base_pose(P); floater.set_base_pose(P);   // B x 7: COM px py pz, unit quaternion qw qx qy qz (checkpoint = q(), qd(), base_pose)
 //
-// Collision geometry (sphere primitives on links against one static plane, contacts with mu-coulomb >= 100 as ur10.xml:19 has
+// Collision geometry (sphere and box primitives on links against one static plane, contacts with mu-coulomb >= 100 as ur10.xml:19 has
 // them) is part of the model: fill it before constructing the batch, e.g.
 //   MobyHip::add_link_sphere(io.model, finger_link, centre_in_link_frame, 0.03);     // <Sphere> CollisionGeometry on a link
+//   MobyHip::add_link_box(io.model, foot_link, centre_in_link_frame, R_in_link_frame, lengths);   // <Box> CollisionGeometry on a link
 //   MobyHip::set_ground_plane(io.model, normal, point_on_plane, /*epsilon*/ 0.0, /*mu_coulomb*/ 100.0);
 // step() then runs TimeSteppingSimulator::step in full: conservative advancement, mini-steps, contact + limit rows in one LCP.
 //
@@ -36,6 +37,16 @@ inline void add_link_sphere(mh_artic_model& m, int link, const double centre[3],
   const int s = m.nspheres++;
   m.sphere_link[s] = link; m.sphere_radius[s] = radius;
   for (int k = 0; k < 3; k++) m.sphere_center[s][k] = centre[k];
+}
+// CollisionGeometry of a BoxPrimitive on link `link`: centre and axes (row-major R, orthonormal) in the link frame, full edge lengths
+// xlen ylen zlen (include/moby_hip_artic.h, mh_artic_model.nboxes); it meets the same plane as the spheres
+inline void add_link_box(mh_artic_model& m, int link, const double centre[3], const double R[9], const double lengths[3])
+{
+  if (m.nboxes >= MH_ARTIC_MAX_BOXES) throw std::runtime_error("MobyHip::add_link_box: more than MH_ARTIC_MAX_BOXES boxes");
+  const int b = m.nboxes++;
+  m.box_link[b] = link;
+  for (int k = 0; k < 3; k++) { m.box_center[b][k] = centre[k]; m.box_len[b][k] = lengths[k]; }
+  for (int k = 0; k < 9; k++) m.box_R[b][k] = R[k];
 }
 // The static PlanePrimitive (its +Y axis is the normal, PlanePrimitive.cpp) through `point`, and the ContactParameters of the
 // (robot, plane) pair; simulator constants at the reference's defaults (TimeSteppingSimulator.cpp:48, ConstraintSimulator.cpp:56)

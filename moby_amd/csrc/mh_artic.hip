@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <cstddef>
 #include <vector>
 #include <mutex>
 #include "../../include/moby_hip_artic.h"
@@ -28,10 +29,23 @@ constexpr int NJ = MH_ARTIC_MAX_JOINTS;
 constexpr int NLMAX = MH_NOSLIP_MAX;
 constexpr double NEAR_ZERO_ = 1.4901161193847656e-08;
 
+struct Boxes {            // mh_artic_model's box block (mh_artic_batch_create copies it here)
+  int n;
+  int link[MH_ARTIC_MAX_BOXES];
+  double center[MH_ARTIC_MAX_BOXES][3], R[MH_ARTIC_MAX_BOXES][9], len[MH_ARTIC_MAX_BOXES][3];
+};
 struct Model {            // mh_artic_model + what the kernel wants precomputed: ancestor masks
-  mh_artic_model m;
-  unsigned anc[NJ];       // bit j: joint j lies on the path from joint i to the base (i itself included)
-  double fcos[32], fsin[32];   // friction polygon of the Drumwright-Shell model: cos / sin(j / (nk/2 - 1) pi/2) by the HOST's libm (ICH-QP:462-470)
+  // anc, fcos and fsin sit where they sat before the box block was appended to mh_artic_model -- over that block, which is therefore NOT valid
+  // in m on the device (read bx) -- so that every kernel written before boxes existed keeps its code byte for byte
+  union {
+    mh_artic_model m;
+    struct {
+      unsigned char head_[offsetof(mh_artic_model, nboxes)];
+      unsigned anc[NJ];       // bit j: joint j lies on the path from joint i to the base (i itself included)
+      double fcos[32], fsin[32];   // friction polygon of the Drumwright-Shell model: cos / sin(j / (nk/2 - 1) pi/2) by the HOST's libm (ICH-QP:462-470)
+    };
+  };
+  Boxes bx;
 };
 
 __constant__ Pow10Table c_pow10a;
@@ -641,7 +655,7 @@ __device__ __noinline__ void stabilize_limits(const Model& M, const Lay& Y, doub
   wave_sync();
 }
 
-#if defined(MH_ARTIC_DRIVE_TU) || defined(MH_ARTIC_POSE_TU)
+#if defined(MH_ARTIC_DRIVE_TU) || defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
 // The drive (moby_hip_artic.h, mh_artic_drive): lane j < nj evaluates tau_j of step s from q / qd in LDS -- q already advanced by the
 // mini-step's position update, qd still its starting velocity -- and leaves it in the qdd slot of the image: dynamics() reads
 // tau_w[lane] there before the same lane writes b[lane] (CRB), dynamics_aba() reads every tau_w[i] on lane 0 in its inward pass,
@@ -802,7 +816,7 @@ MH_DEV void artic_step_body(const Model* __restrict__ Mg, int B, double dt, int 
   }
 }
 
-#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
+#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU) && !defined(MH_ARTIC_BOX_TU)
 // The same step at three register budgets: 128 VGPRs (4 waves per SIMD = the 16 worlds per CU the 10 KB LDS image allows; 95 spilled
 // VGPRs), 168 (3 per SIMD, 14 spilled) and 193 (2 per SIMD, none).  The kernel waits on ~250 LDS round trips per step, so
 // resident waves win over spills: ur10 x 8192, 200 steps: 25.6 / 31.2 / 39.0 ms (profiles/r02_c_artic_occupancy.jsonl).
@@ -890,7 +904,7 @@ void k_artic_step_stab(const Model* __restrict__ Mg, int B, double dt, int nstep
                        mh_world_aux* __restrict__ auxg) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg); }
 #endif
 
-#ifndef MH_ARTIC_DRIVE_TU
+#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_BOX_TU)
 // k_artic_fwd_dyn / k_artic_jacobian, and in pose coordinates k_artic_fwd_dyn_pose / k_artic_jacobian_pose: one more argument, the B x 7 poses
 #ifdef MH_ARTIC_POSE_TU
 #define MH_POSE_KERNEL(name) name##_pose
@@ -980,7 +994,7 @@ void k_artic_step_w2_drive(const Model* __restrict__ Mg, int B, double dt, int n
 __global__ __launch_bounds__(64)
 void k_artic_step_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
                              mh_world_aux* __restrict__ auxg, mh_artic_drive D) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, D); }
-#elif defined(MH_ARTIC_POSE_TU)  // the pose-coordinate step kernels: their own code object (mh_artic_pose.hip)
+#elif defined(MH_ARTIC_POSE_TU) && !defined(MH_ARTIC_BOX_TU)  // the pose-coordinate step kernels: their own code object (mh_artic_pose.hip)
 // the default budget of k_artic_step_w4 (MH_ARTIC_WAVES and MH_ARTIC_PACK do not apply in pose coordinates), undriven and driven
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_artic_step_w4_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
@@ -1014,9 +1028,11 @@ void k_artic_pose_fold(int B, int nj, double* __restrict__ qg, double* __restric
 struct mh_artic_batch {
   int device;                // the HIP device the batch lives on (current at create); every entry point runs there (MH_ON_DEVICE)
   int B, nj, nspheres, cstab, algorithm;
+  int nboxes;                // box primitives: the step goes through the box kernels (mh_artic_box.hip), as it does for spheres under mh_debug_set(12, 1)
   mh::artic::Model* d_model;
   double* d_q; double* d_qd; mh_world_aux* d_aux;
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
+  size_t ws_stride;       // doubles per world in d_ws: 2 x 64 x 64, or WS_BOX for the box kernels (their stabiliser keeps its rows there too)
   mh_artic_drive drive;   // the drive of mh_artic_batch_set_drive (terms 0 = none); its arrays live in d_drive
   double* d_drive;
   int base_coords;        // MH_ARTIC_BASE_ANGLES / MH_ARTIC_BASE_POSE (mh_artic_batch_set_base_coords)
@@ -1028,6 +1044,11 @@ struct mh_artic_batch {
 int artic_pose_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
 hipError_t artic_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
 hipError_t artic_pose_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
+// the box kernels (mh_artic_box.hip / mh_artic_box_pose.hip): every step of a model with boxes, and of a sphere-only model under mh_debug_set(12, 1);
+// D as artic_pose_step's
+int artic_box_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+int artic_box_pose_launch(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+static inline bool artic_uses_box(const mh_artic_batch* ab) { return ab->nboxes > 0 || (ab->nspheres > 0 && mh_g_debug_artic_box != 0); }
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
 static int check_drive(const mh_artic_drive* d, int nsteps)
@@ -1040,7 +1061,7 @@ static int check_drive(const mh_artic_drive* d, int nsteps)
   return MH_OK;
 }
 
-#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
+#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU) && !defined(MH_ARTIC_BOX_TU)
 extern "C" {
 
 int mh_artic_batch_device(const mh_artic_batch* ab) { return ab ? ab->device : fail(MH_ERR_INVALID_ARG, "null batch"); }
@@ -1066,6 +1087,7 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   const int nj = model->nj;
   if (nj < 1 || nj > MH_ARTIC_MAX_JOINTS) return fail(MH_ERR_INVALID_ARG, "nj = %d outside [1, %d]", nj, MH_ARTIC_MAX_JOINTS);
   ar::Model hm; std::memset(&hm, 0, sizeof(hm)); hm.m = *model;
+  std::memset(hm.anc, 0, sizeof(hm.anc)); std::memset(hm.fcos, 0, sizeof(hm.fcos)); std::memset(hm.fsin, 0, sizeof(hm.fsin));   // (they overlay m's box block: bx holds it)
   for (int i = 0; i < nj; i++) {
     const int p = model->parent[i];
     if (p >= i || p < -1) return fail(MH_ERR_INVALID_ARG, "joint %d: parent %d must come before it (-1 = base)", i, p);
@@ -1095,11 +1117,25 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
     if (model->sphere_link[s] < 0 || model->sphere_link[s] >= nj) return fail(MH_ERR_INVALID_ARG, "sphere %d: link %d outside [0, %d)", s, model->sphere_link[s], nj);
     if (!(model->sphere_radius[s] > 0.0)) return fail(MH_ERR_INVALID_ARG, "sphere %d: radius must be > 0", s);
   }
+  if (model->nboxes < 0 || model->nboxes > MH_ARTIC_MAX_BOXES) return fail(MH_ERR_INVALID_ARG, "nboxes = %d outside [0, %d]", model->nboxes, MH_ARTIC_MAX_BOXES);
+  for (int k = 0; k < model->nboxes; k++) {
+    if (model->box_link[k] < 0 || model->box_link[k] >= nj) return fail(MH_ERR_INVALID_ARG, "box %d: link %d outside [0, %d)", k, model->box_link[k], nj);
+    for (int c = 0; c < 3; c++) if (!(model->box_len[k][c] > 0.0) || !std::isfinite(model->box_len[k][c])) return fail(MH_ERR_INVALID_ARG, "box %d: edge lengths must be finite and > 0", k);
+    const double* Rb = model->box_R[k];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {       // R R' = I
+      const double d = (Rb[3*i] * Rb[3*j] + Rb[3*i+1] * Rb[3*j+1]) + Rb[3*i+2] * Rb[3*j+2];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) < 1e-9)) return fail(MH_ERR_INVALID_ARG, "box %d: box_R is not orthonormal", k);
+    }
+    hm.bx.link[k] = model->box_link[k];
+    for (int c = 0; c < 3; c++) { hm.bx.center[k][c] = model->box_center[k][c]; hm.bx.len[k][c] = model->box_len[k][c]; }
+    for (int c = 0; c < 9; c++) hm.bx.R[k][c] = Rb[c];
+  }
+  hm.bx.n = model->nboxes;
   if (model->cstab_max_iterations < 0) return fail(MH_ERR_INVALID_ARG, "cstab_max_iterations = %d < 0", model->cstab_max_iterations);
-  if (model->nspheres > 0) {
+  if (model->nspheres > 0 || model->nboxes > 0) {
     const double* Rp = model->plane_R; const double nn = Rp[1]*Rp[1] + Rp[4]*Rp[4] + Rp[7]*Rp[7];
     if (!(nn > 0.999999 && nn < 1.000001)) return fail(MH_ERR_INVALID_ARG, "plane_R is not a rotation (its +Y column is the plane normal)");
-    if (!(model->min_step_size > 0.0) || !(model->contact_dist_thresh > 0.0)) return fail(MH_ERR_INVALID_ARG, "min_step_size and contact_dist_thresh must be > 0 when spheres are present");
+    if (!(model->min_step_size > 0.0) || !(model->contact_dist_thresh > 0.0)) return fail(MH_ERR_INVALID_ARG, "min_step_size and contact_dist_thresh must be > 0 when spheres or boxes are present");
     if (!(model->cp_epsilon >= 0.0) || !(model->cp_mu_coulomb >= 0.0)) return fail(MH_ERR_INVALID_ARG, "contact parameters must be >= 0");
     if (!(model->cp_mu_coulomb >= 1e2)) {                         // the Drumwright-Shell model's parameters
       const int nk = model->cp_nk > 0 ? model->cp_nk : 4;
@@ -1124,14 +1160,16 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   }
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
-  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->nboxes = model->nboxes; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;
   bool ok = hipMalloc((void**)&ab->d_model, sizeof(ar::Model)) == hipSuccess && hipMalloc((void**)&ab->d_q, sB * nj * 8) == hipSuccess
          && hipMalloc((void**)&ab->d_qd, sB * nj * 8) == hipSuccess && hipMalloc((void**)&ab->d_aux, sB * sizeof(mh_world_aux)) == hipSuccess;
-  if (ok && model->nspheres > 0 && (!(model->cp_mu_coulomb >= 1e2) || model->cstab_max_iterations != 0))   // (the stabiliser's LCP with contact AND limit rows lives there too)
-    ok = hipMalloc((void**)&ab->d_ws, sB * 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE * sizeof(double)) == hipSuccess;
+  // the box kernels' layout for a model with boxes, and for a sphere model created while mh_debug_set(12, 1) sends it to those kernels
+  ab->ws_stride = (model->nboxes > 0 || (model->nspheres > 0 && mh_g_debug_artic_box != 0)) ? ar::WS_BOX : 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE;
+  if (ok && (model->nspheres > 0 || model->nboxes > 0) && (!(model->cp_mu_coulomb >= 1e2) || model->cstab_max_iterations != 0))   // (the stabiliser's LCP with contact AND limit rows lives there too)
+    ok = hipMalloc((void**)&ab->d_ws, sB * ab->ws_stride * sizeof(double)) == hipSuccess;
   if (ok) {
     std::vector<mh_world_aux> a(sB);
     mh_world_aux_init(&a[0], 1);
@@ -1165,6 +1203,7 @@ int mh_artic_batch_step(mh_artic_batch* ab, void* stream, double dt, int nsteps)
   if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
   if (nsteps == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
+  if (artic_uses_box(ab)) return artic_box_step(ab, stream, dt, nsteps, nullptr);
   if (ab->base_coords == MH_ARTIC_BASE_POSE) return artic_pose_step(ab, stream, dt, nsteps, nullptr);
   if (ab->nspheres > 0) {                                     // bodies with collision geometry: the full step with mini-steps and contact rows
     hipLaunchKernelGGL(ab->cstab ? ar::k_artic_step_contacts_stab : ar::k_artic_step_contacts, dim3(ab->B), dim3(64), ar::lds_bytes_contacts(ab->nj), (hipStream_t)stream,

@@ -13,11 +13,25 @@
 // factorisations of <= 8 x 8) and the Schur-complement assembly run on lane 0 out of LDS -- no private arrays, no barriers
 // under divergent control flow.
 
+#ifdef MH_ARTIC_BOX_TU
+// the box kernels (mh_artic_box.hip): the impact handler holds MH_NOSLIP_MAX contacts (four box feet flat on the ground under the no-slip
+// model); the contact list holds every sphere and every box vertex, so that the impacting test and the stabiliser see all of them
+constexpr int NS = MH_NOSLIP_MAX;
+constexpr int NCL = MH_ARTIC_MAX_SPHERES + 8 * MH_ARTIC_MAX_BOXES;
+#else
 constexpr int NS = MH_ARTIC_MAX_SPHERES;
+constexpr int NCL = NS;
+#endif
 constexpr int NR = MH_NOSLIP_MAX;
 constexpr int MT = 2 * NS;                                  // largest tangent set
+constexpr int LOFF = (3 * NS <= 32) ? 32 : 3 * NS;          // first lane of the limit rows where lanes < 3 nc hold the contact rows
 constexpr double A_INF_ = 1.7976931348623157e308;
 
+#ifdef MH_ARTIC_BOX_TU
+constexpr int NINTS = (16 + NCL + 2 * NS + 2 + 1) / 2;      // the ints below, in doubles
+#else
+constexpr int NINTS = 24;
+#endif
 struct LayC {
   int qsave, V, cp, C, XC, G, CL, Cv, Lv, MM, qq, QX, W, Yy, YXv, t2, imp, l, A, art, ints, total;
   // The arrays that live across calls (qsave, V, the contact list, ints) and most temporaries sit behind the config-5 image; the
@@ -27,19 +41,23 @@ struct LayC {
   __host__ __device__ LayC(int base, int n, int arena, int arena_size) {
     int o = base, a = arena;
     const int a_end = arena + arena_size;
-    qsave = o; o += n; V = o; o += 6 * n; cp = o; o += 12 * NS;
+    qsave = o; o += n; V = o; o += 6 * n; cp = o; o += 12 * NCL;
     C = o; o += 3 * NS * n; XC = o; o += 3 * NS * n; CL = o; o += 3 * NS * NR; Cv = o; o += 3 * NS;
     Lv = o; o += NR; qq = o; o += NR;
     QX = o; o += NR * MT; W = o; o += MT * NR; Yy = o; o += MT * MT; YXv = o; o += MT; t2 = o; o += MT;
-    imp = o; o += 3 * NS; l = o; o += NR; art = o; o += MH_LCP_MAX_N_WAVE /* Lemke's artificial column: up to 64 rows in the Drumwright-Shell LCP */; ints = o; o += 24;
+    imp = o; o += 3 * NS; l = o; o += NR; art = o; o += MH_LCP_MAX_N_WAVE /* Lemke's artificial column: up to 64 rows in the Drumwright-Shell LCP */; ints = o; o += NINTS;
     if (a + NR * NR <= a_end) { MM = a; a += NR * NR; } else { MM = o; o += NR * NR; }
     if (a + NR * NR <= a_end) { A = a; a += NR * NR; } else { A = o; o += NR * NR; }
     if (a + 6 * NS * NS <= a_end) { G = a; a += 6 * NS * NS; } else { G = o; o += 6 * NS * NS; }
     total = o;
   }
 };
-// ints: idx[16] (joint | upper << 8), clink[4], Sx[4], Tx[4], ns, nt
-constexpr int I_IDX = 0, I_LINK = 16, I_SX = 20, I_TX = 24, I_NS = 28, I_NT = 29;
+// ints: idx[16] (joint | upper << 8), clink[NCL], Sx[NS], Tx[NS], ns, nt
+constexpr int I_IDX = 0, I_LINK = 16, I_SX = I_LINK + NCL, I_TX = I_SX + NS, I_NS = I_TX + NS, I_NT = I_NS + 1;
+// the per-world HBM workspace: _MM and the Lemke LU workspace of the Drumwright-Shell / stabiliser LCP (2 x 64 x 64); the box kernels' stabiliser
+// adds Cn and Cn X for up to 64 contacts and the distances of the whole contact list behind them
+constexpr size_t WS_C = 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE, WS_XC = WS_C + MH_LCP_MAX_N_WAVE * NJ, WS_DIST = WS_XC + MH_LCP_MAX_N_WAVE * NJ;
+constexpr size_t WS_BOX = WS_DIST + MH_ARTIC_MAX_SPHERES + 8 * MH_ARTIC_MAX_BOXES;
 // the arena = Lay's I6, v, a, f, F, Iv (contiguous, 60 nj + 12 doubles); its offset from the layout itself on the device, by the
 // same arithmetic on the host (q qd qdd C: 4 nj; H L X: 3 nj^2; R x S: 18 nj -- Rl, tl share v and a since round 5)
 static size_t lds_bytes_contacts(int nj) {
@@ -141,6 +159,112 @@ MH_DEV double CA_step(const mh_artic_model& m, const Lay& Y, const LayC& Z, cons
   return (cand < A_INF_) ? cand : A_INF_;
 }
 
+#ifdef MH_ARTIC_BOX_TU
+// ---- box primitives on links (mh_artic_model.nboxes; the model's box block is read from M.bx).  Every lane computes the same numbers. ----
+// vertex i of box k in the model frame, BoxPrimitive::get_vertices order (BoxPrimitive.cpp:358-365): the link frame's centre + Rb (+-x/2, +-y/2, +-z/2)
+MH_DEV void box_vertex(const Model& M, const Lay& Y, const double* g, int k, int i, double v[3]) {
+  const Boxes& X = M.bx; const int l = X.link[k];
+  const double hx = X.len[k][0] * 0.5, hy = X.len[k][1] * 0.5, hz = X.len[k][2] * 0.5;
+  const double px = (i & 4) ? -hx : hx, py = (i & 2) ? -hy : hy, pz = (i & 1) ? -hz : hz;
+  const double* Rb = X.R[k];
+  const double lp[3] = { X.center[k][0] + ((Rb[0]*px + Rb[1]*py) + Rb[2]*pz), X.center[k][1] + ((Rb[3]*px + Rb[4]*py) + Rb[5]*pz),
+                         X.center[k][2] + ((Rb[6]*px + Rb[7]*py) + Rb[8]*pz) };
+  double rc[3]; mat3vec(g + Y.R + 9 * l, lp, rc);
+  for (int c = 0; c < 3; c++) v[c] = g[Y.x + 3 * l + c] + rc[c];
+}
+// BoxPrimitive::calc_signed_dist -> PlanePrimitive (PlanePrimitive.cpp:338-376): the lowest vertex's plane-frame height, the first vertex wins
+// ties; pa = that vertex, pp = it in the plane frame
+MH_DEV double box_dist(const Model& M, const Lay& Y, const double* g, int k, double pa[3], double pp[3]) {
+  double mn = A_INF_;
+  for (int i = 0; i < 8; i++) {
+    double v[3], q[3]; box_vertex(M, Y, g, k, i, v); to_plane(M.m, v, q);
+    if (q[1] < mn) { mn = q[1]; for (int c = 0; c < 3; c++) { pa[c] = v[c]; pp[c] = q[c]; } }
+  }
+  return mn;
+}
+// CollisionGeometry::get_farthest_point_distance (CollisionGeometry.cpp:52-68): BoxPrimitive's bounding radius (the FULL diagonal) + the
+// centre's offset from the link COM
+MH_DEV double rmax_box(const Model& M, int k) {
+  const Boxes& X = M.bx; const int l = X.link[k];
+  const double d[3] = { X.center[k][0] - M.m.com[l][0], X.center[k][1] - M.m.com[l][1], X.center[k][2] - M.m.com[l][2] };
+  const double x = X.len[k][0], y = X.len[k][1], z = X.len[k][2];
+  return sqrt((x*x + y*y) + z*z) + sqrt((d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]);
+}
+// CompGeom::rel_equal / collinear (CompGeom.cpp:1923-1931, CompGeom.h:110)
+MH_DEV bool rel_equal_(double x, double y) {
+  const double ax = fabs(x), ay = fabs(y);
+  const double m1 = (ay < 1.0) ? 1.0 : ay, mm = (ax < m1) ? m1 : ax;
+  return fabs(x - y) <= NEAR_ZERO_ * mm;
+}
+MH_DEV bool collinear_(const double* a, const double* b, const double* c) {
+  return rel_equal_((c[2]-a[2])*(b[1]-a[1]), (b[2]-a[2])*(c[1]-a[1])) && rel_equal_((b[2]-a[2])*(c[0]-a[0]), (b[0]-a[0])*(c[2]-a[2])) &&
+         rel_equal_((b[0]-a[0])*(c[1]-a[1]), (b[1]-a[1])*(c[0]-a[0]));
+}
+// box k against the plane: CCD::calc_CA_Euler_step_generic (CCD.cpp:169-235) -> calc_next_CA_Euler_step_generic (:238-405, the rest rule :285-323)
+// -> calc_next_CA_Euler_step_polyhedron_plane (:405-468); uniform
+MH_DEV double CA_box(const Model& M, const Lay& Y, const LayC& Z, const double* g, int k) {
+  const mh_artic_model& m = M.m;
+  const int link = M.bx.link[k];
+  double pa[3], pp[3];
+  const double dist = box_dist(M, Y, g, k, pa, pp);
+  double n[3]; plane_n(m, n);
+  const double* V6 = g + Z.V + 6 * link;
+  if (dist <= 0.0) {
+    int cnt = 0; double c0[3], c1[3], c2[3];
+    bool approach = false;
+    for (int i = 0; i < 8; i++) {                                    // find_contacts(NEAR_ZERO): the vertices within it, in order
+      double v[3], q[3]; box_vertex(M, Y, g, k, i, v); to_plane(m, v, q);
+      if (!(q[1] <= NEAR_ZERO_)) continue;
+      if (point_vel_dir(V6, v, n) < -NEAR_ZERO_) approach = true;
+      double* dst = (cnt == 0) ? c0 : ((cnt == 1) ? c1 : c2);
+      if (cnt < 3) for (int c = 0; c < 3; c++) dst[c] = v[c];
+      cnt++;
+    }
+    if (cnt == 0) return A_INF_;
+    if (approach) return 0.0;
+    if (cnt >= 3 && !collinear_(c0, c1, c2)) return A_INF_;
+    // the polyhedron-plane step: normal = the plane's, offset0 = <n, first contact>; velocities at the box's pose, in box axes
+    const double offset0 = dot3(n, c0);
+    double Rbg[9]; mat3mul(g + Y.R + 9 * link, M.bx.R[k], Rbg);
+    double cb[3]; { double rc[3]; mat3vec(g + Y.R + 9 * link, M.bx.center[k], rc); for (int c = 0; c < 3; c++) cb[c] = g[Y.x + 3 * link + c] + rc[c]; }
+    auto to_box = [&](const double* v, double* o) {
+      o[0] = (Rbg[0]*v[0] + Rbg[3]*v[1]) + Rbg[6]*v[2]; o[1] = (Rbg[1]*v[0] + Rbg[4]*v[1]) + Rbg[7]*v[2]; o[2] = (Rbg[2]*v[0] + Rbg[5]*v[1]) + Rbg[8]*v[2];
+    };
+    double nP[3]; to_box(n, nP);
+    const double d0[3] = { n[0] * offset0 - cb[0], n[1] * offset0 - cb[1], n[2] * offset0 - cb[2] };
+    double t[3]; to_box(d0, t);
+    const double offset = dot3(nP, t);
+    double wxc[3]; cross3(V6, cb, wxc);
+    const double vrel[3] = { V6[3] + wxc[0], V6[4] + wxc[1], V6[5] + wxc[2] };
+    double wb[3], vb[3]; to_box(V6, wb); to_box(vrel, vb);
+    const double av_norm = sqrt(dot3(wb, wb));
+    const double lv_dot_n = -dot3(nP, vb);
+    const double hx = M.bx.len[k][0] * 0.5, hy = M.bx.len[k][1] * 0.5, hz = M.bx.len[k][2] * 0.5;
+    double max_step = A_INF_;
+    for (int i = 0; i < 8; i++) {
+      const double vtx[3] = { (i & 4) ? -hx : hx, (i & 2) ? -hy : hy, (i & 1) ? -hz : hz };
+      const double r = sqrt(dot3(vtx, vtx));
+      const double dv = dot3(nP, vtx) - offset;
+      if (dv < NEAR_ZERO_) continue;
+      const double sp = lv_dot_n + av_norm * r;
+      const double speed = (0.0 > sp) ? 0.0 : sp;
+      const double cand = dv / speed;
+      max_step = (cand < max_step) ? cand : max_step;
+    }
+    return max_step;
+  }
+  double pb[3]; from_plane(m, pp[0], 0.0, pp[2], pb);
+  const double d0[3] = { pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2] };
+  const double len = sqrt(dot3(d0, d0));
+  const double mn0[3] = { -(d0[0] / len), -(d0[1] / len), -(d0[2] / len) };
+  const double tA = calc_max_dist(m, Y, g, link, mn0, rmax_box(M, k));
+  double total = tA + 0.0;
+  if (total < 0.0) total = 0.0;
+  const double cand = dist / total;
+  return (cand < A_INF_) ? cand : A_INF_;
+}
+#endif
+
 // lane 0, LDS: dpotf2('L') / dpotrs of linalg.hpp (chol_factor, chol_solve), column-major with leading dimension ld
 MH_DEV bool chol_factor_s(int n, double* A, int ld) {
   for (int j = 0; j < n; j++) {
@@ -189,7 +313,11 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   link_velocities(M, Y, Z, g);
   const double qdi = (lane < nj) ? g[Y.qd + lane] : 0.0;
   bool imp_c = false;
+#ifdef MH_ARTIC_BOX_TU
+  for (int i = lane; i < nc; i += 64) imp_c = imp_c || point_vel_dir(g + Z.V + 6 * ints[I_LINK + i], g + Z.cp + 12 * i, g + Z.cp + 12 * i + 3) < -NEAR_ZERO_;
+#else
   if (lane < nc) imp_c = point_vel_dir(g + Z.V + 6 * ints[I_LINK + lane], g + Z.cp + 12 * lane, g + Z.cp + 12 * lane + 3) < -NEAR_ZERO_;
+#endif
   const bool impacting = ballot(imp_c || (up && -qdi < -NEAR_ZERO_) || (lo && qdi < -NEAR_ZERO_)) != 0ull;   // CSim:313-323
   if (!impacting) return;
   // ICH:123-146: the no-slip model when every CONTACT has mu_coulomb >= 100 (an island of limits alone takes it too), else the
@@ -386,17 +514,17 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
       cv = cv + acc;
       g[Z.W + lane] = cv;                                         // staged: W is dead
     }
-    if (lane >= 32 && lane < 32 + nl) {                           // L_v rows
-      const int k = lane - 32;
+    if (lane >= LOFF && lane < LOFF + nl) {                           // L_v rows
+      const int k = lane - LOFF;
       double lv = Lv[k];
       for (int d = 0; d < 3; d++) { double acc = 0.0; for (int i = 0; i < nc; i++) acc = acc + CL[d * NS * NR + i * nl + k] * imp[d * NS + i]; lv = lv + acc; }
       double acc = 0.0; for (int k2 = 0; k2 < nl; k2++) acc = acc + X[(idx[k] & 255) * nj + (idx[k2] & 255)] * ll[k2];
       lv = lv + acc;
-      g[Z.W + 32 + k] = lv;
+      g[Z.W + LOFF + k] = lv;
     }
     wave_sync();
     if (lane < 3 * nc) Cv[(lane / nc) * NS + (lane % nc)] = g[Z.W + lane];
-    if (lane >= 32 && lane < 32 + nl) Lv[lane - 32] = g[Z.W + lane];
+    if (lane >= LOFF && lane < LOFF + nl) Lv[lane - LOFF] = g[Z.W + lane];
     wave_sync();
   };
   auto minv_of = [&]() -> double {                               // calc_min_constraint_velocity (ICH:413-424); uniform
@@ -412,7 +540,7 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   wave_sync();
   bool ch = false;                                                // apply_restitution(q) (ICH:497-525)
   if (lane < nc) { const double v = imp[lane] * m.cp_epsilon; imp[lane] = v; ch = v > NEAR_ZERO_; }
-  if (lane >= 32 && lane < 32 + nl) { const int k = lane - 32; const double v = ll[k] * m.limit_restitution[idx[k] & 255]; ll[k] = v; ch = v > NEAR_ZERO_; }
+  if (lane >= LOFF && lane < LOFF + nl) { const int k = lane - LOFF; const double v = ll[k] * m.limit_restitution[idx[k] & 255]; ll[k] = v; ch = v > NEAR_ZERO_; }
   const bool changed = ballot(ch) != 0ull;
   wave_sync();
   if (changed) {
@@ -507,7 +635,7 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
       double sv = aux->zbuf[nc + lane];     sv = sv - aux->zbuf[3 * nc + lane]; imp[NS + lane] = sv;
       double tv = aux->zbuf[2 * nc + lane]; tv = tv - aux->zbuf[4 * nc + lane]; imp[2 * NS + lane] = tv;
     }
-    if (lane >= 32 && lane < 32 + nl) ll[lane - 32] = aux->zbuf[5 * nc + lane - 32];
+    if (lane >= LOFF && lane < LOFF + nl) ll[lane - LOFF] = aux->zbuf[5 * nc + lane - LOFF];
     wave_sync();
   };
   if (!solve_qp()) return;
@@ -516,7 +644,7 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   wave_sync();
   bool ch = false;                                                // apply_restitution(q, z) (ICH:470-491): the cn and l entries of z
   if (lane < nc) { const double v = aux->zbuf[lane] * m.cp_epsilon; aux->zbuf[lane] = v; ch = v > NEAR_ZERO_; }
-  if (lane >= 32 && lane < 32 + nl) { const int k = lane - 32; const double v = aux->zbuf[5 * nc + k] * m.limit_restitution[idx[k] & 255]; aux->zbuf[5 * nc + k] = v; ch = v > NEAR_ZERO_; }
+  if (lane >= LOFF && lane < LOFF + nl) { const int k = lane - LOFF; const double v = aux->zbuf[5 * nc + k] * m.limit_restitution[idx[k] & 255]; aux->zbuf[5 * nc + k] = v; ch = v > NEAR_ZERO_; }
   const bool changed = ballot(ch) != 0ull;
   wave_sync();
   if (changed) {
@@ -532,7 +660,7 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   link_velocities(M, Y, Z, g);                                    // ICH:157-167
   bool tol = false;
   if (lane < nc) tol = point_vel_dir(g + Z.V + 6 * ints[I_LINK + lane], g + Z.cp + 12 * lane, g + Z.cp + 12 * lane + 3) < -NEAR_ZERO_;
-  if (lane >= 32 && lane < 32 + nl) { const int c = idx[lane - 32]; const double v = g[Y.qd + (c & 255)]; tol = ((c & 256) ? -v : v) < -NEAR_ZERO_; }
+  if (lane >= LOFF && lane < LOFF + nl) { const int c = idx[lane - LOFF]; const double v = g[Y.qd + (c & 255)]; tol = ((c & 256) ? -v : v) < -NEAR_ZERO_; }
   if (ballot(tol) != 0ull) status |= MH_WORLD_IMPACT_TOL;
 }
 
@@ -543,7 +671,7 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_DRIVE_TU
                            , const mh_artic_drive& D, int B, int b, int s
 #endif
-#ifdef MH_ARTIC_POSE_TU
+#if defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
                            , const mh_artic_drive* Dp, int B, int b, int s
 #endif
                            )
@@ -563,6 +691,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
     link_velocities(M, Y, Z, g);
     double CA = A_INF_;
     for (int s = 0; s < m.nspheres; s++) { const double e = CA_step(m, Y, Z, g, s); CA = (e < CA) ? e : CA; }
+#ifdef MH_ARTIC_BOX_TU
+    for (int k = 0; k < M.bx.n; k++) { const double e = CA_box(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
+#endif
     CA = uni(CA);
     if (CA <= 0.0) { kin_ok = true; break; }
     double tc = (m.min_step_size > CA) ? m.min_step_size : CA;
@@ -576,7 +707,7 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_DRIVE_TU
   drive_tau(D, B, b, s, Y, g);                                    // (read by the dynamics after kin_inertia's barriers)
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, g + Y.qdd) : dynamics(M, Y, g, g + Y.qdd);
-#elif defined(MH_ARTIC_POSE_TU)
+#elif defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
   if (Dp) drive_tau(*Dp, B, b, s, Y, g);
   const double* tw = Dp ? g + Y.qdd : nullptr;
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, tw) : dynamics(M, Y, g, tw);
@@ -604,6 +735,23 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
       nc++;
     }
   }
+#ifdef MH_ARTIC_BOX_TU
+  for (int k = 0; k < M.bx.n; k++) {                               // find_contacts_plane_generic: a contact at every vertex within the threshold
+    double pa[3], pp[3];
+    if (!(box_dist(M, Y, g, k, pa, pp) < m.contact_dist_thresh)) continue;
+    for (int i = 0; i < 8; i++) {
+      double v[3], q[3]; box_vertex(M, Y, g, k, i, v); to_plane(m, v, q);
+      if (!(q[1] <= m.contact_dist_thresh)) continue;
+      if (lane == 0) {
+        double* c = g + Z.cp + 12 * nc;
+        double n[3], sv[3], tv[3]; plane_n(m, n); orthonormal_basis(n, sv, tv);
+        for (int c2 = 0; c2 < 3; c2++) { c[c2] = v[c2]; c[3 + c2] = n[c2]; c[6 + c2] = sv[c2]; c[9 + c2] = tv[c2]; }
+        ints[I_LINK + nc] = M.bx.link[k];
+      }
+      nc++;
+    }
+  }
+#endif
   nc = uni(nc);
   wave_sync();
   handle_impacts(M, Y, Z, g, ws, aux, rng, nc, status, solves, rows, pivs, bytes);
@@ -625,12 +773,25 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
   const mh_artic_model& m = M.m;
   const unsigned maxit = (unsigned)m.cstab_max_iterations;
   if (maxit == 0) return;
+#ifdef MH_ARTIC_BOX_TU
+  if (!ws) { status |= MH_WORLD_UNSUPPORTED; return; }              // (the host allocates it for every stabilising batch)
+#endif
+#ifdef MH_ARTIC_BOX_TU
+  // the boxes' distances follow the spheres' in uC; up to NCL contacts: their distances and Cn / Cn X live in the HBM workspace behind the LCP
+  const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres, ngeo = nsph + M.bx.n;
+  const int nu = ngeo + 2 * nj;
+  double* uO = g + Z.W; double* uN = uO + 48; double* uT = uN + 48;   // (nu <= 12 + 32)
+  int* idx = reinterpret_cast<int*>(g + Z.QX);
+  int* ints = reinterpret_cast<int*>(g + Z.ints);
+  double* dist = ws + WS_DIST;
+#else
   const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres;
   const int nu = nsph + 2 * nj;                                    // entries of uC: the pairwise distances, then joint 0's two slacks nj times
   double* uO = g + Z.W; double* uN = uO + 40; double* uT = uN + 40;   // uC at q, at q + dq, at the trial q (nu <= 4 + 32)
   int* idx = reinterpret_cast<int*>(g + Z.QX);                    // idx[k] = joint | (upper << 8), a row for every finite limit
   int* ints = reinterpret_cast<int*>(g + Z.ints);
   double* dist = g + Z.Cv;                                         // the contacts' signed distances
+#endif
   const double hi0 = m.hilimit[0], lo0 = m.lolimit[0];
   // evaluate_unilateral_constraints at the q in LDS into `out`; returns the most negative entry (uniform)
   auto eval = [&](double* out) -> double {
@@ -638,9 +799,16 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
     kin_inertia(M, Y, g);
     double vio = A_INF_;
     for (int s2 = 0; s2 < nsph; s2++) { double cp[3]; sphere_in_plane(m, Y, g, s2, cp); const double d = cp[1] + (-1.0 * m.sphere_radius[s2]); if (lane == 0) out[s2] = d; vio = (d < vio) ? d : vio; }
+#ifdef MH_ARTIC_BOX_TU
+    for (int k = 0; k < M.bx.n; k++) { double pa[3], pp[3]; const double d = box_dist(M, Y, g, k, pa, pp); if (lane == 0) out[nsph + k] = d; vio = (d < vio) ? d : vio; }
+    const double q0 = g[Y.q];
+    const double a = (hi0 - q0) - 0.0, b2 = (q0 + 0.0) - lo0;
+    if (lane < nj) { out[ngeo + 2 * lane] = a; out[ngeo + 2 * lane + 1] = b2; }
+#else
     const double q0 = g[Y.q];
     const double a = (hi0 - q0) - 0.0, b2 = (q0 + 0.0) - lo0;
     if (lane < nj) { out[nsph + 2 * lane] = a; out[nsph + 2 * lane + 1] = b2; }
+#endif
     vio = (a < vio) ? a : vio; vio = (b2 < vio) ? b2 : vio;
     wave_sync();
     return uni(vio);
@@ -678,6 +846,26 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
         nc++;
       }
     }
+#ifdef MH_ARTIC_BOX_TU
+    for (int k = 0; k < M.bx.n; k++) {                             // CStab:306-345 for (box, plane): one synthetic contact, or the vertices within NEAR_ZERO
+      double pa[3], pp[3];
+      const double low = box_dist(M, Y, g, k, pa, pp);
+      if (low >= NEAR_ZERO_) {
+        double pb[3]; from_plane(m, pp[0], 0.0, pp[2], pb);
+        const double d[3] = { pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2] };
+        const double len = sqrt((d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]);
+        if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int c2 = 0; c2 < 3; c2++) { c[c2] = pa[c2]; c[3 + c2] = d[c2] / len; } ints[I_LINK + nc] = M.bx.link[k]; dist[nc] = low; }
+        nc++;
+      } else {
+        for (int i = 0; i < 8; i++) {
+          double v[3], q[3]; box_vertex(M, Y, g, k, i, v); to_plane(m, v, q);
+          if (!(q[1] <= NEAR_ZERO_)) continue;
+          if (lane == 0) { double* c = g + Z.cp + 12 * nc; double nn[3]; plane_n(m, nn); for (int c2 = 0; c2 < 3; c2++) { c[c2] = v[c2]; c[3 + c2] = nn[c2]; } ints[I_LINK + nc] = M.bx.link[k]; dist[nc] = q[1]; }
+          nc++;
+        }
+      }
+    }
+#endif
     nc = uni(nc);
     const int n = nc + nl;
     wave_sync();
@@ -692,7 +880,11 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
       wave_sync();
       inverse_from_factor(Y, g);
       const double* X = g + Y.X;
+#ifdef MH_ARTIC_BOX_TU
+      double* C = ws + WS_C; double* XC = ws + WS_XC;
+#else
       double* C = g + Z.C; double* XC = g + Z.XC;
+#endif
       for (int e = lane; e < nc * nj; e += 64) {                   // Cn rows: [n, r x n] . calc_jacobian(link) at the link's COM (handle_impacts' rows, normal direction)
         const int i = e / nj, j = e - i * nj;
         const int l = ints[I_LINK + i];
@@ -849,8 +1041,11 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #ifdef MH_ARTIC_DRIVE_TU
                                 , const mh_artic_drive& D
 #endif
+#if defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
+                                , const mh_artic_drive* Dp
+#endif
 #ifdef MH_ARTIC_POSE_TU
-                                , const mh_artic_drive* Dp, double* __restrict__ poseg
+                                , double* __restrict__ poseg
 #endif
                                 )
 {
@@ -862,7 +1057,11 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   const Lay Y(nj);
   const LayC Z(Y.total, nj, Y.I6, 60 * nj + 12);
   mh_world_aux* aux = auxg + b;
+#ifdef MH_ARTIC_BOX_TU
+  double* ws = wsg ? wsg + (size_t)b * WS_BOX : nullptr;
+#else
   double* ws = wsg ? wsg + (size_t)b * 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE : nullptr;   // Drumwright-Shell: _MM and the Lemke LU workspace
+#endif
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = qdg[(size_t)b * nj + lane]; }
 #ifdef MH_ARTIC_POSE_TU
   pose_load(Y, g, poseg + 7 * (size_t)b);
@@ -881,7 +1080,7 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
     while (h < dt) {
 #ifdef MH_ARTIC_DRIVE_TU
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, D, B, b, s));
-#elif defined(MH_ARTIC_POSE_TU)
+#elif defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s));
 #else
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes));
@@ -922,7 +1121,36 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   }
 }
 
-#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
+#if defined(MH_ARTIC_BOX_TU) && !defined(MH_ARTIC_POSE_TU)
+// the box kernels (mh_artic_box.hip): {plain, stab} x {undriven, driven} in angle coordinates; their LDS image holds one world per SIMD or two
+// (DESIGN 4.4), so no waves-per-EU bound
+__global__ __launch_bounds__(64)
+void k_artic_step_box(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                      mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
+__global__ __launch_bounds__(64)
+void k_artic_step_box_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
+__global__ __launch_bounds__(64)
+void k_artic_step_box_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                           mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
+__global__ __launch_bounds__(64)
+void k_artic_step_box_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
+#elif defined(MH_ARTIC_BOX_TU)
+// the same four in pose coordinates (mh_artic_box_pose.hip)
+__global__ __launch_bounds__(64)
+void k_artic_step_box_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                           mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_box_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_box_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_box_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                      mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+#elif !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
 // 2 waves per SIMD = the 8 worlds per CU the 18 KB LDS image allows
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_artic_step_contacts(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,

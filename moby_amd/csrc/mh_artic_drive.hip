@@ -37,6 +37,7 @@ int mh_artic_batch_step_driven(mh_artic_batch* ab, void* stream, double dt, int 
   if (rc != MH_OK) return rc;
   if (nsteps == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
+  if (artic_uses_box(ab)) return artic_box_step(ab, stream, dt, nsteps, &D);
   if (ab->base_coords == MH_ARTIC_BASE_POSE) return artic_pose_step(ab, stream, dt, nsteps, &D);
   if (init_pow10() != MH_OK) return MH_ERR_HIP;
   const ar::Model* M = ab->d_model;

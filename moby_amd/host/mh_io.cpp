@@ -250,7 +250,7 @@ extern "C" int mh_io_load_sdf(const char* path, const double gravity[3], mh_io_a
 // ---- URDF (src/URDFReader.cpp) ----------------------------------------------------------------------------
 namespace {
 struct UrdfLink { std::string name; bool has_inertial = false; bool bad_inertia = false; Pose inertial; double mass = 0.0; double I[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-                  int cg = 0; Pose cg_pose; double cg_radius = 0.0; std::string cg_kind; };      // cg: 0 none, 1 sphere, 2 box / cylinder
+                  int cg = 0; Pose cg_pose; double cg_radius = 0.0; double cg_size[3] = {0.0, 0.0, 0.0}; std::string cg_kind; };      // cg: 0 none, 1 sphere, 2 box / cylinder
 struct UrdfJoint { std::string name, parent, child; int type = 0; Pose origin; double axis[3] = {1.0, 0.0, 0.0}; double lo = 0.0, hi = 0.0; };
 constexpr int URDF_FIXED = 2;
 // URDFReader::read_origin (URDFReader.cpp:943-972): the first <origin>, xyz and rpy attributes, Quatd::rpy
@@ -264,7 +264,9 @@ bool urdf_origin(xmlNode* parent, Pose& p) {
   return true;
 }
 // the robot as a fixed-base tree of 1-DOF joints; a FixedJoint's outboard link rides on the link that carries it
-struct UrdfGeom { int link; std::string id; bool sphere; double center[3]; double radius; std::string kind; };   // link -1: the base
+// a box: its centre (center), axes (R, row-major) and full edge lengths (dims) in the model link's frame
+struct UrdfGeom { int link; std::string id; bool sphere; double center[3]; double radius; std::string kind;
+                  bool box = false; double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; double dims[3] = {0.0, 0.0, 0.0}; };   // link -1: the base
 struct UrdfRobot { std::string name, base; mh_io_artic art; std::vector<UrdfGeom> geoms; std::vector<std::string> link_names; };
 
 int parse_urdf(const char* path, UrdfRobot& rob)
@@ -302,7 +304,11 @@ int parse_urdf(const char* path, UrdfRobot& rob)
         if (xmlNode* ge = child_named(col, "geometry")) {
           xmlNode* sp = child_named(ge, "sphere");
           // read_primitive tries box, cylinder, sphere in that order (:813-836)
-          if (child_named(ge, "box")) { L.cg = 2; L.cg_kind = "box"; }
+          if (xmlNode* bx = child_named(ge, "box")) {
+            L.cg = 2; L.cg_kind = "box";
+            const Attrs ba = attrs_of(bx);
+            if (ba.has("size")) { const std::vector<double> v = numbers(ba.str("size")); if (v.size() != 3) return fail("link %s: <box size> needs three numbers", L.name.c_str()); for (int k = 0; k < 3; k++) L.cg_size[k] = v[k]; }
+          }
           else if (child_named(ge, "cylinder")) { L.cg = 2; L.cg_kind = "cylinder"; }
           else if (sp && attrs_of(sp).has("radius")) { L.cg = 1; L.cg_kind = "sphere"; L.cg_radius = std::atof(attrs_of(sp).str("radius").c_str()); }
           if (L.cg && !urdf_origin(col, L.cg_pose)) return fail("link %s: bad collision <origin>", L.name.c_str());
@@ -371,6 +377,7 @@ int parse_urdf(const char* path, UrdfRobot& rob)
     if (!L.cg) return;
     UrdfGeom g; g.link = carrier; g.id = L.name; g.sphere = (L.cg == 1); g.radius = L.cg_radius; g.kind = L.cg_kind;
     double c[3]; mat3vec(P.R, L.cg_pose.x, c); for (int k = 0; k < 3; k++) g.center[k] = c[k] + P.x[k];
+    if (L.cg_kind == "box") { g.box = true; mat3mul(P.R, L.cg_pose.R, g.R); for (int k = 0; k < 3; k++) g.dims[k] = L.cg_size[k]; }
     rob.geoms.push_back(g);
   };
   add_geom(-1, identity_pose(), links[link_of[rob.base]]);
@@ -954,16 +961,20 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
     auto add_welded = [&](const XLink& T, int link, const double* org) {
       for (const XWeldGeom& w : T.wg) {
         UrdfGeom g; g.link = link; g.id = w.id; g.sphere = prims.count(w.prim) && prims[w.prim].type == MH_GEOM_SPHERE; g.radius = g.sphere ? prims[w.prim].dim[0] : 0.0;
+        g.box = prims.count(w.prim) && prims[w.prim].type == MH_GEOM_BOX;
         const double d[3] = { w.x[0] - org[0], w.x[1] - org[1], w.x[2] - org[2] };
         double a[3], Rr[9], b[3] = { 0.0, 0.0, 0.0 };
-        mat3Tvec(T.R, d, a); mat3Tmul(T.R, w.R, Rr); if (g.sphere) mat3vec(Rr, prims[w.prim].o, b);
+        mat3Tvec(T.R, d, a); mat3Tmul(T.R, w.R, Rr); if (g.sphere || g.box) mat3vec(Rr, prims[w.prim].o, b);
         for (int k = 0; k < 3; k++) g.center[k] = a[k] + b[k];
+        if (g.box) { mat3mul(Rr, prims[w.prim].R, g.R); for (int k = 0; k < 3; k++) g.dims[k] = prims[w.prim].dim[k]; }
         geoms.push_back(g);
       }
     };
     if (B0.has_cg && floating) {                                             // the floating base link moves: link 5, its frame's origin is its COM
       UrdfGeom g; g.link = 5; g.id = base; g.sphere = prims.count(B0.geom) && prims[B0.geom].type == MH_GEOM_SPHERE; g.radius = g.sphere ? prims[B0.geom].dim[0] : 0.0;
-      for (int k = 0; k < 3; k++) g.center[k] = g.sphere ? prims[B0.geom].o[k] : 0.0;
+      g.box = prims.count(B0.geom) && prims[B0.geom].type == MH_GEOM_BOX;
+      for (int k = 0; k < 3; k++) g.center[k] = (g.sphere || g.box) ? prims[B0.geom].o[k] : 0.0;
+      if (g.box) { for (int k = 0; k < 9; k++) g.R[k] = prims[B0.geom].R[k]; for (int k = 0; k < 3; k++) g.dims[k] = prims[B0.geom].dim[k]; }
       if (B0.composite) { const double d[3] = { B0.x[0] - B0.cx[0], B0.x[1] - B0.cx[1], B0.x[2] - B0.cx[2] }; double a[3]; mat3Tvec(B0.R, d, a); for (int k = 0; k < 3; k++) g.center[k] += a[k]; }
       geoms.push_back(g);
     }
@@ -974,12 +985,15 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
       add_welded(L, i, joints[order[i - nv]].loc);
       if (!L.has_cg) continue;
       UrdfGeom g; g.link = i; g.id = L.id; g.sphere = prims.count(L.geom) && prims[L.geom].type == MH_GEOM_SPHERE; g.radius = g.sphere ? prims[L.geom].dim[0] : 0.0;
+      g.box = prims.count(L.geom) && prims[L.geom].type == MH_GEOM_BOX;
+      const bool off = g.sphere || g.box;
       // centre in the model link frame (origin at the joint): COM offset + the primitive's own offset in the link's axes
-      for (int k = 0; k < 3; k++) g.center[k] = m.com[i][k] + (g.sphere ? prims[L.geom].o[k] : 0.0);
+      for (int k = 0; k < 3; k++) g.center[k] = m.com[i][k] + (off ? prims[L.geom].o[k] : 0.0);
       if (L.composite) {                                                     // (the COM has moved away from the link's own position, where its geometry is)
         const double* jl = joints[order[i - nv]].loc; const double d[3] = { L.x[0] - jl[0], L.x[1] - jl[1], L.x[2] - jl[2] }; double a[3]; mat3Tvec(L.R, d, a);
-        for (int k = 0; k < 3; k++) g.center[k] = a[k] + (g.sphere ? prims[L.geom].o[k] : 0.0);
+        for (int k = 0; k < 3; k++) g.center[k] = a[k] + (off ? prims[L.geom].o[k] : 0.0);
       }
+      if (g.box) { for (int k = 0; k < 9; k++) g.R[k] = prims[L.geom].R[k]; for (int k = 0; k < 3; k++) g.dims[k] = prims[L.geom].dim[k]; }
       geoms.push_back(g);
     }
   }
@@ -992,7 +1006,16 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
     for (const UrdfGeom& g : geoms) {
       if (g.link < 0) continue;                                              // rides on the fixed base: static against the static plane
       if (pair_disabled(g.id, plane_body) || pair_disabled(abid, plane_body)) continue;
-      if (!g.sphere) return fail("link %s: only Sphere collision geometry can meet the plane (others: disable the pair)", g.id.c_str());
+      if (g.box) {
+        if (m.nboxes >= MH_ARTIC_MAX_BOXES) return fail("more than %d link boxes", MH_ARTIC_MAX_BOXES);
+        if (!(g.dims[0] > 0.0 && g.dims[1] > 0.0 && g.dims[2] > 0.0)) return fail("link %s: a box needs three positive edge lengths", g.id.c_str());
+        const int b = m.nboxes++;
+        m.box_link[b] = g.link;
+        for (int k = 0; k < 3; k++) { m.box_center[b][k] = g.center[k]; m.box_len[b][k] = g.dims[k]; }
+        for (int k = 0; k < 9; k++) m.box_R[b][k] = g.R[k];
+        continue;
+      }
+      if (!g.sphere) return fail("link %s: only Sphere and Box collision geometry can meet the plane (others: disable the pair)", g.id.c_str());
       if (m.nspheres >= MH_ARTIC_MAX_SPHERES) return fail("more than %d link spheres", MH_ARTIC_MAX_SPHERES);
       const int s = m.nspheres++;
       m.sphere_link[s] = g.link; m.sphere_radius[s] = g.radius;
