@@ -40,6 +40,7 @@ extern "C" {
 #define MH_ARTIC_FSAB 1
 #define MH_ARTIC_MAX_SPHERES 4    /* sphere primitives carried by links (contacts against the one static plane) */
 #define MH_ARTIC_MAX_BOXES 8      /* box primitives carried by links (the same plane) */
+#define MH_ARTIC_MAX_PAIRS 6      /* every pair of MH_ARTIC_MAX_SPHERES spheres */
 
 /* Joint i carries link i; joints are listed parents first.  A link may be massless as long as its joint moves mass (something outboard of it has mass).  All quantities are LOCAL (constant), as a reader of
  * model.sdf derives them once at q = 0 (mh_io_load_sdf, moby_amd/host/mh_io.cpp):
@@ -125,6 +126,35 @@ typedef struct mh_artic_model {
   double box_center[MH_ARTIC_MAX_BOXES][3];        /* link frame */
   double box_R[MH_ARTIC_MAX_BOXES][9];             /* the box's axes in the link frame, row-major, orthonormal */
   double box_len[MH_ARTIC_MAX_BOXES][3];           /* full edge lengths xlen ylen zlen, > 0 */
+  /* Sphere contacts between links (appended: every field above keeps its offset).  A pair names two spheres of the sphere list that sit on
+   * DIFFERENT links: an arm against itself, two fingers, two chains that hang from the world in one model (several joints with parent = -1).
+   * The pairs share the model's one set of cp_* ContactParameters, min_step_size and contact_dist_thresh with the plane contacts.  A sphere
+   * whose bit is set in sphere_no_plane does not meet the plane (its pair with the plane body is disabled, or the scene has no plane); it still
+   * counts in pairs.  Centres cA, cB and link frames in the model frame:
+   *   contact          find_contacts_sphere_sphere (CCD.inl:1163-1206): d = cA - cB, dist = |d| - rA - rB (= (|d| - rA) - rB); none if dist > TOL;
+   *                    n = d / |d| (from b to a); point = ((cA - n rA) + (cB + n rB)) * 0.5; tangents by orthonormal_basis(n).  Canonical order
+   *                    of a world's contact list: spheres against the plane in index order (masked ones skipped), boxes, then pairs in index order.
+   *   row              for each of the three directions (ICH:1817-1895, two add_contact_dir_to_Jacobian blocks): column j =
+   *                    [dir, (p - comA) x dir] . J_A(comA)_j  +  [-dir, (p - comB) x -dir] . J_B(comB)_j, A's term FIRST, each term the one-link
+   *                    expression; a joint that is an ancestor of only one of the two links gets that term alone, of neither 0.0.
+   *   constraint       A's point velocity along n MINUS B's (the impacting test, conservative advancement, the tolerance test after the impact);
+   *   velocity         a plane contact keeps its single term.
+   *   conservative     the sphere rule (CCD.cpp:138-235): dist > NEAR_ZERO -> dist / max(0, calc_max_dist(linkA, -n0, rmaxA) + calc_max_dist(linkB, n0, rmaxB)),
+   *   advancement      n0 = n of the closest points; dist <= NEAR_ZERO -> a contact with |constraint velocity| < 10 NEAR_ZERO = no bound; dist <= 0 ->
+   *                    no contact = no bound, approaching (< -NEAR_ZERO) = 0, else no bound.  calc_max_dist adds the floating base's linear
+   *                    velocity only for links that descend from joint 0 (a second root does not ride on the base); for a single-root model that
+   *                    is every link, as before.
+   *   stabiliser       one row per pair and iteration (CStab:306-345): dist >= NEAR_ZERO -> the synthetic contact at cA - n rA with normal n,
+   *                    otherwise the contact above (TOL = NEAR_ZERO); Cn_v = dist - |eps| - NEAR_ZERO.  cstab_eval reads the distances of the spheres that meet the plane
+   *                    (a masked sphere has no entry), the boxes', then the pairs'.
+   * Capacity as for boxes.  Models with pairs or a mask step through their own kernels (mh_artic_pair.hip, mh_artic_pair_pose.hip);
+   * mh_debug_set(13, 1) sends box and sphere models through them too (batches created after it).
+   * mh_artic_batch_create refuses (MH_ERR_INVALID_ARG): npairs outside [0, MH_ARTIC_MAX_PAIRS], an index outside the sphere list, a == b, both
+   * spheres on one link, a pair listed twice in either order, bits of sphere_no_plane beyond nspheres. */
+  int    npairs;                                   /* 0 = no link-link contacts */
+  int    pair_a[MH_ARTIC_MAX_PAIRS];               /* indices into the sphere list; a is the reference's geometry A */
+  int    pair_b[MH_ARTIC_MAX_PAIRS];               /*   (the normal points from b to a) */
+  int    sphere_no_plane;                          /* bit s set: sphere s does not meet the plane; 0 = every sphere does */
 } mh_artic_model;
 
 /* B worlds resident on the GPU: joint positions q and velocities qd (B x nj each) + mh_world_aux (rand() stream, time,

@@ -18,9 +18,11 @@ MH_ARTIC_MAX_JOINTS = 16
 MH_JOINT_REVOLUTE, MH_JOINT_PRISMATIC = 0, 1
 MH_ARTIC_MAX_SPHERES = 4
 MH_ARTIC_MAX_BOXES = 8
+MH_ARTIC_MAX_PAIRS = 6
 _NJ = MH_ARTIC_MAX_JOINTS
 _NS = MH_ARTIC_MAX_SPHERES
 _NB = MH_ARTIC_MAX_BOXES
+_NP = MH_ARTIC_MAX_PAIRS
 
 
 class mh_artic_model(ctypes.Structure):
@@ -35,7 +37,8 @@ class mh_artic_model(ctypes.Structure):
                 ("contact_dist_thresh", ctypes.c_double), ("cp_mu_viscous", ctypes.c_double), ("cp_compliance", ctypes.c_double),
                 ("cp_nk", ctypes.c_int), ("cstab_max_iterations", ctypes.c_int), ("cstab_eps", ctypes.c_double),
                 ("nboxes", ctypes.c_int), ("box_link", ctypes.c_int * _NB), ("box_center", (ctypes.c_double * 3) * _NB),
-                ("box_R", (ctypes.c_double * 9) * _NB), ("box_len", (ctypes.c_double * 3) * _NB)]
+                ("box_R", (ctypes.c_double * 9) * _NB), ("box_len", (ctypes.c_double * 3) * _NB),
+                ("npairs", ctypes.c_int), ("pair_a", ctypes.c_int * _NP), ("pair_b", ctypes.c_int * _NP), ("sphere_no_plane", ctypes.c_int)]
 
 
 MH_ARTIC_CRB, MH_ARTIC_FSAB = 0, 1      # moby_hip_artic.h: RCArticulatedBody::algorithm_type
@@ -233,6 +236,23 @@ def add_boxes(model, boxes, plane_normal=(0.0, 0.0, 1.0), plane_point=(0.0, 0.0,
         for k in range(9):
             model.box_R[i][k] = R.flat[k]
     _set_plane(model, Rp, plane_point, epsilon, mu_coulomb, mu_viscous, compliance, nk)
+    return model
+
+
+def add_pairs(model, pairs, no_plane=()):
+    """Sphere contacts between links (include/moby_hip_artic.h, mh_artic_model.npairs): pairs = [(a, b), ...] name two spheres of the model's
+    sphere list (add_spheres first) that sit on different links -- a is the reference's geometry A, the contact normal points from b to a;
+    no_plane lists the spheres that do not meet the plane.  The pairs share the model's contact parameters with the plane contacts.
+    mh_artic_batch_create checks the rest (indices, a pair listed twice).  Returns the model."""
+    assert len(pairs) <= MH_ARTIC_MAX_PAIRS
+    model.npairs = len(pairs)
+    for k, (a, b) in enumerate(pairs):
+        model.pair_a[k] = int(a); model.pair_b[k] = int(b)
+    mask = 0
+    for s in no_plane:
+        assert 0 <= int(s) < MH_ARTIC_MAX_SPHERES
+        mask |= 1 << int(s)
+    model.sphere_no_plane = mask
     return model
 
 

@@ -16,6 +16,7 @@
 // them) is part of the model: fill it before constructing the batch, e.g.
 //   MobyHip::add_link_sphere(io.model, finger_link, centre_in_link_frame, 0.03);     // <Sphere> CollisionGeometry on a link
 //   MobyHip::add_link_box(io.model, foot_link, centre_in_link_frame, R_in_link_frame, lengths);   // <Box> CollisionGeometry on a link
+//   MobyHip::add_sphere_pair(io.model, 0, 1);                                        // spheres 0 and 1 (on different links) can collide
 //   MobyHip::set_ground_plane(io.model, normal, point_on_plane, /*epsilon*/ 0.0, /*mu_coulomb*/ 100.0);
 // step() then runs TimeSteppingSimulator::step in full: conservative advancement, mini-steps, contact + limit rows in one LCP.
 //
@@ -47,6 +48,18 @@ inline void add_link_box(mh_artic_model& m, int link, const double centre[3], co
   m.box_link[b] = link;
   for (int k = 0; k < 3; k++) { m.box_center[b][k] = centre[k]; m.box_len[b][k] = lengths[k]; }
   for (int k = 0; k < 9; k++) m.box_R[b][k] = R[k];
+}
+// A sphere contact between links: spheres a and b of the model's sphere list (add_link_sphere first), on different links; a is the reference's
+// geometry A, the contact normal points from b to a (include/moby_hip_artic.h, mh_artic_model.npairs).  The pair shares the ContactParameters
+// of set_ground_plane.  meets_plane_a / _b = false takes that sphere off the plane (mh_artic_model.sphere_no_plane).
+inline void add_sphere_pair(mh_artic_model& m, int a, int b, bool meets_plane_a = true, bool meets_plane_b = true)
+{
+  if (m.npairs >= MH_ARTIC_MAX_PAIRS) throw std::runtime_error("MobyHip::add_sphere_pair: more than MH_ARTIC_MAX_PAIRS pairs");
+  if (a < 0 || a >= m.nspheres || b < 0 || b >= m.nspheres || a == b) throw std::runtime_error("MobyHip::add_sphere_pair: two different spheres of the sphere list");
+  const int k = m.npairs++;
+  m.pair_a[k] = a; m.pair_b[k] = b;
+  if (!meets_plane_a) m.sphere_no_plane |= 1 << a;
+  if (!meets_plane_b) m.sphere_no_plane |= 1 << b;
 }
 // The static PlanePrimitive (its +Y axis is the normal, PlanePrimitive.cpp) through `point`, and the ContactParameters of the
 // (robot, plane) pair; simulator constants at the reference's defaults (TimeSteppingSimulator.cpp:48, ConstraintSimulator.cpp:56)

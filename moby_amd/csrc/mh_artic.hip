@@ -34,9 +34,15 @@ struct Boxes {            // mh_artic_model's box block (mh_artic_batch_create c
   int link[MH_ARTIC_MAX_BOXES];
   double center[MH_ARTIC_MAX_BOXES][3], R[MH_ARTIC_MAX_BOXES][9], len[MH_ARTIC_MAX_BOXES][3];
 };
+struct Pairs {            // mh_artic_model's pair block (mh_artic_batch_create copies it here)
+  int n;
+  int a[MH_ARTIC_MAX_PAIRS], b[MH_ARTIC_MAX_PAIRS];
+  int no_plane;           // mh_artic_model.sphere_no_plane
+};
 struct Model {            // mh_artic_model + what the kernel wants precomputed: ancestor masks
   // anc, fcos and fsin sit where they sat before the box block was appended to mh_artic_model -- over that block, which is therefore NOT valid
-  // in m on the device (read bx) -- so that every kernel written before boxes existed keeps its code byte for byte
+  // in m on the device (read bx) -- so that every kernel written before boxes existed keeps its code byte for byte.  The pair block at the end
+  // of m is valid there, but the kernels read the copy in pr, beside bx
   union {
     mh_artic_model m;
     struct {
@@ -46,6 +52,7 @@ struct Model {            // mh_artic_model + what the kernel wants precomputed:
     };
   };
   Boxes bx;
+  Pairs pr;
 };
 
 __constant__ Pow10Table c_pow10a;
@@ -1029,6 +1036,8 @@ struct mh_artic_batch {
   int device;                // the HIP device the batch lives on (current at create); every entry point runs there (MH_ON_DEVICE)
   int B, nj, nspheres, cstab, algorithm;
   int nboxes;                // box primitives: the step goes through the box kernels (mh_artic_box.hip), as it does for spheres under mh_debug_set(12, 1)
+  int use_pair;              // sphere pairs between links or a plane mask: the step goes through the pair kernels (mh_artic_pair.hip), as it does for
+                             // every model with geometry created under mh_debug_set(13, 1)
   mh::artic::Model* d_model;
   double* d_q; double* d_qd; mh_world_aux* d_aux;
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
@@ -1048,7 +1057,12 @@ hipError_t artic_pose_jacobian_launch(mh_artic_batch* ab, int link, const double
 // D as artic_pose_step's
 int artic_box_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
 int artic_box_pose_launch(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
-static inline bool artic_uses_box(const mh_artic_batch* ab) { return ab->nboxes > 0 || (ab->nspheres > 0 && mh_g_debug_artic_box != 0); }
+// the pair kernels (mh_artic_pair.hip / mh_artic_pair_pose.hip): artic_box_step hands a batch with use_pair on to them; the LDS image of their
+// layout at nj joints, in bytes (mh_artic_batch_create refuses a model whose image would not fit a workgroup)
+int artic_pair_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+int artic_pair_pose_launch(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+size_t artic_pair_lds_bytes(int nj);
+static inline bool artic_uses_box(const mh_artic_batch* ab) { return ab->use_pair != 0 || ab->nboxes > 0 || (ab->nspheres > 0 && mh_g_debug_artic_box != 0); }
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
 static int check_drive(const mh_artic_drive* d, int nsteps)
@@ -1131,6 +1145,22 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
     for (int c = 0; c < 9; c++) hm.bx.R[k][c] = Rb[c];
   }
   hm.bx.n = model->nboxes;
+  // sphere pairs between links
+  if (model->npairs < 0 || model->npairs > MH_ARTIC_MAX_PAIRS) return fail(MH_ERR_INVALID_ARG, "npairs = %d outside [0, %d]", model->npairs, MH_ARTIC_MAX_PAIRS);
+  for (int k = 0; k < model->npairs; k++) {
+    const int a = model->pair_a[k], b = model->pair_b[k];
+    if (a < 0 || a >= model->nspheres || b < 0 || b >= model->nspheres) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) outside the sphere list [0, %d)", k, a, b, model->nspheres);
+    if (a == b) return fail(MH_ERR_INVALID_ARG, "pair %d: sphere %d against itself", k, a);
+    if (model->sphere_link[a] == model->sphere_link[b]) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres %d and %d sit on the same link %d", k, a, b, model->sphere_link[a]);
+    for (int k2 = 0; k2 < k; k2++)
+      if ((model->pair_a[k2] == a && model->pair_b[k2] == b) || (model->pair_a[k2] == b && model->pair_b[k2] == a)) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) are pair %d already", k, a, b, k2);
+    hm.pr.a[k] = a; hm.pr.b[k] = b;
+  }
+  if (model->sphere_no_plane < 0 || (model->sphere_no_plane >> model->nspheres) != 0) return fail(MH_ERR_INVALID_ARG, "sphere_no_plane = 0x%x has bits beyond the %d spheres", (unsigned)model->sphere_no_plane, model->nspheres);
+  hm.pr.n = model->npairs; hm.pr.no_plane = model->sphere_no_plane;
+  const bool has_geom = model->nspheres > 0 || model->nboxes > 0;
+  const bool use_pair = model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
+  if (use_pair && artic_pair_lds_bytes(nj) > 65536) return fail(MH_ERR_INVALID_ARG, "the pair kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, artic_pair_lds_bytes(nj));
   if (model->cstab_max_iterations < 0) return fail(MH_ERR_INVALID_ARG, "cstab_max_iterations = %d < 0", model->cstab_max_iterations);
   if (model->nspheres > 0 || model->nboxes > 0) {
     const double* Rp = model->plane_R; const double nn = Rp[1]*Rp[1] + Rp[4]*Rp[4] + Rp[7]*Rp[7];
@@ -1160,15 +1190,16 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   }
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
-  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->nboxes = model->nboxes; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->nboxes = model->nboxes; ab->use_pair = use_pair ? 1 : 0; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;
   bool ok = hipMalloc((void**)&ab->d_model, sizeof(ar::Model)) == hipSuccess && hipMalloc((void**)&ab->d_q, sB * nj * 8) == hipSuccess
          && hipMalloc((void**)&ab->d_qd, sB * nj * 8) == hipSuccess && hipMalloc((void**)&ab->d_aux, sB * sizeof(mh_world_aux)) == hipSuccess;
   // the box kernels' layout for a model with boxes, and for a sphere model created while mh_debug_set(12, 1) sends it to those kernels
-  ab->ws_stride = (model->nboxes > 0 || (model->nspheres > 0 && mh_g_debug_artic_box != 0)) ? ar::WS_BOX : 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE;
-  if (ok && (model->nspheres > 0 || model->nboxes > 0) && (!(model->cp_mu_coulomb >= 1e2) || model->cstab_max_iterations != 0))   // (the stabiliser's LCP with contact AND limit rows lives there too)
+  // (and the pair kernels' for a batch that steps through those)
+  ab->ws_stride = use_pair ? ar::WS_PAIR : (model->nboxes > 0 || (model->nspheres > 0 && mh_g_debug_artic_box != 0)) ? ar::WS_BOX : 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE;
+  if (ok && (model->nspheres > 0 || model->nboxes > 0) && (use_pair || !(model->cp_mu_coulomb >= 1e2) || model->cstab_max_iterations != 0))   // (the stabiliser's LCP with contact AND limit rows lives there too)
     ok = hipMalloc((void**)&ab->d_ws, sB * ab->ws_stride * sizeof(double)) == hipSuccess;
   if (ok) {
     std::vector<mh_world_aux> a(sB);

@@ -13,7 +13,11 @@
 // factorisations of <= 8 x 8) and the Schur-complement assembly run on lane 0 out of LDS -- no private arrays, no barriers
 // under divergent control flow.
 
-#ifdef MH_ARTIC_BOX_TU
+#ifdef MH_ARTIC_PAIR_TU
+// the pair kernels (mh_artic_pair.hip): the box kernels' sizes with room for the sphere pairs between links in the contact list
+constexpr int NS = MH_NOSLIP_MAX;
+constexpr int NCL = MH_ARTIC_MAX_SPHERES + 8 * MH_ARTIC_MAX_BOXES + MH_ARTIC_MAX_PAIRS;
+#elif defined(MH_ARTIC_BOX_TU)
 // the box kernels (mh_artic_box.hip): the impact handler holds MH_NOSLIP_MAX contacts (four box feet flat on the ground under the no-slip
 // model); the contact list holds every sphere and every box vertex, so that the impacting test and the stabiliser see all of them
 constexpr int NS = MH_NOSLIP_MAX;
@@ -27,7 +31,9 @@ constexpr int MT = 2 * NS;                                  // largest tangent s
 constexpr int LOFF = (3 * NS <= 32) ? 32 : 3 * NS;          // first lane of the limit rows where lanes < 3 nc hold the contact rows
 constexpr double A_INF_ = 1.7976931348623157e308;
 
-#ifdef MH_ARTIC_BOX_TU
+#ifdef MH_ARTIC_PAIR_TU
+constexpr int NINTS = (16 + 2 * NCL + 2 * NS + 2 + 1) / 2;  // the ints below, in doubles
+#elif defined(MH_ARTIC_BOX_TU)
 constexpr int NINTS = (16 + NCL + 2 * NS + 2 + 1) / 2;      // the ints below, in doubles
 #else
 constexpr int NINTS = 24;
@@ -48,16 +54,46 @@ struct LayC {
     imp = o; o += 3 * NS; l = o; o += NR; art = o; o += MH_LCP_MAX_N_WAVE /* Lemke's artificial column: up to 64 rows in the Drumwright-Shell LCP */; ints = o; o += NINTS;
     if (a + NR * NR <= a_end) { MM = a; a += NR * NR; } else { MM = o; o += NR * NR; }
     if (a + NR * NR <= a_end) { A = a; a += NR * NR; } else { A = o; o += NR * NR; }
+#ifdef MH_ARTIC_PAIR_TU
+    // the pair kernels' image must fit a workgroup's 64 KB up to MH_ARTIC_MAX_JOINTS: where G would push it over (from 12 joints on), G goes to
+    // the world's HBM workspace instead (G = -1; handle_impacts picks the pointer)
+    if (a + 6 * NS * NS <= a_end) { G = a; a += 6 * NS * NS; } else if (sizeof(double) * (size_t)(o + 6 * NS * NS) > 65536) G = -1; else { G = o; o += 6 * NS * NS; }
+#else
     if (a + 6 * NS * NS <= a_end) { G = a; a += 6 * NS * NS; } else { G = o; o += 6 * NS * NS; }
+#endif
     total = o;
   }
 };
 // ints: idx[16] (joint | upper << 8), clink[NCL], Sx[NS], Tx[NS], ns, nt
+#ifdef MH_ARTIC_PAIR_TU
+// ... and a second link table beside clink: clinkB[NCL], the contact's other link (the reference's geometry B), -1 = the plane
+constexpr int I_IDX = 0, I_LINK = 16, I_LINKB = I_LINK + NCL, I_SX = I_LINKB + NCL, I_TX = I_SX + NS, I_NS = I_TX + NS, I_NT = I_NS + 1;
+#define MH_SET_LINKB(i, v) ints[I_LINKB + (i)] = (v);
+#define MH_BASE_PARAM , bool on_base
+#define MH_BASE_ARG(M_, link_) , ((M_).anc[link_] & 1u) != 0u
+#define MH_ON_BASE && on_base
+#define MH_SKIP_MASKED(M_, s_) if (((M_).pr.no_plane >> (s_)) & 1) continue;
+#else
 constexpr int I_IDX = 0, I_LINK = 16, I_SX = I_LINK + NCL, I_TX = I_SX + NS, I_NS = I_TX + NS, I_NT = I_NS + 1;
+#define MH_SET_LINKB(i, v)
+#define MH_BASE_PARAM
+#define MH_BASE_ARG(M_, link_)
+#define MH_ON_BASE
+#define MH_SKIP_MASKED(M_, s_)
+#endif
 // the per-world HBM workspace: _MM and the Lemke LU workspace of the Drumwright-Shell / stabiliser LCP (2 x 64 x 64); the box kernels' stabiliser
 // adds Cn and Cn X for up to 64 contacts and the distances of the whole contact list behind them
 constexpr size_t WS_C = 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE, WS_XC = WS_C + MH_LCP_MAX_N_WAVE * NJ, WS_DIST = WS_XC + MH_LCP_MAX_N_WAVE * NJ;
 constexpr size_t WS_BOX = WS_DIST + MH_ARTIC_MAX_SPHERES + 8 * MH_ARTIC_MAX_BOXES;
+constexpr size_t WS_PAIR_G = WS_BOX + MH_ARTIC_MAX_PAIRS + 2;   // the pair kernels: the pairs' distances behind the boxes', then the C X C' blocks of a
+constexpr size_t WS_PAIR = WS_PAIR_G + 6 * MH_NOSLIP_MAX * MH_NOSLIP_MAX;   // model whose LDS image has no room for them (LayC::G < 0)
+#ifdef MH_ARTIC_PAIR_TU
+constexpr size_t WS_WORLD = WS_PAIR;
+constexpr int USTRIDE = 56;                                  // the stabiliser's uC vectors: 4 + 8 + 6 distances + 32 slacks
+#elif defined(MH_ARTIC_BOX_TU)
+constexpr size_t WS_WORLD = WS_BOX;
+constexpr int USTRIDE = 48;
+#endif
 // the arena = Lay's I6, v, a, f, F, Iv (contiguous, 60 nj + 12 doubles); its offset from the layout itself on the device, by the
 // same arithmetic on the host (q qd qdd C: 4 nj; H L X: 3 nj^2; R x S: 18 nj -- Rl, tl share v and a since round 5)
 static size_t lds_bytes_contacts(int nj) {
@@ -117,9 +153,9 @@ MH_DEV void link_velocities(const Model& M, const Lay& Y, const LayC& Z, double*
   wave_sync();
 }
 // the articulated CCD::calc_max_dist (CCD.cpp:545-583); n: the direction of approach (a floating base adds its linear velocity along it: the three virtual sliders' rates)
-MH_DEV double calc_max_dist(const mh_artic_model& m, const Lay& Y, const double* g, int link, const double* n, double rmax) {
+MH_DEV double calc_max_dist(const mh_artic_model& m, const Lay& Y, const double* g, int link, const double* n, double rmax MH_BASE_PARAM) {
   double mv = 0.0;
-  if (m.floating_base) mv = (n[0] * g[Y.qd] + n[1] * g[Y.qd + 1]) + n[2] * g[Y.qd + 2];
+  if (m.floating_base MH_ON_BASE) mv = (n[0] * g[Y.qd] + n[1] * g[Y.qd + 1]) + n[2] * g[Y.qd + 2];
   int inner = link;
   mv = mv + (2.0 * rmax) * fabs(g[Y.qd + inner]);
   while (m.parent[inner] >= 0) {
@@ -136,7 +172,7 @@ MH_DEV double rmax_of(const mh_artic_model& m, int s) {
   return m.sphere_radius[s] + sqrt((d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]);
 }
 // CCD::calc_CA_Euler_step_sphere -> _generic -> calc_next_CA_Euler_step_generic (CCD.cpp:138-405); uniform
-MH_DEV double CA_step(const mh_artic_model& m, const Lay& Y, const LayC& Z, const double* g, int s) {
+MH_DEV double CA_step(const mh_artic_model& m, const Lay& Y, const LayC& Z, const double* g, int s MH_BASE_PARAM) {
   double cp[3]; sphere_in_plane(m, Y, g, s, cp);
   const double dist = cp[1] + (-1.0 * m.sphere_radius[s]);
   const int link = m.sphere_link[s];
@@ -152,7 +188,11 @@ MH_DEV double CA_step(const mh_artic_model& m, const Lay& Y, const LayC& Z, cons
     return A_INF_;
   }
   const double mn[3] = { -n[0], -n[1], -n[2] };
+#ifdef MH_ARTIC_PAIR_TU
+  const double tA = calc_max_dist(m, Y, g, link, mn, rmax_of(m, s), on_base);
+#else
   const double tA = calc_max_dist(m, Y, g, link, mn, rmax_of(m, s));
+#endif
   double total = tA + 0.0;
   if (total < 0.0) total = 0.0;
   const double cand = dist / total;
@@ -257,11 +297,98 @@ MH_DEV double CA_box(const Model& M, const Lay& Y, const LayC& Z, const double* 
   const double d0[3] = { pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2] };
   const double len = sqrt(dot3(d0, d0));
   const double mn0[3] = { -(d0[0] / len), -(d0[1] / len), -(d0[2] / len) };
-  const double tA = calc_max_dist(m, Y, g, link, mn0, rmax_box(M, k));
+  const double tA = calc_max_dist(m, Y, g, link, mn0, rmax_box(M, k) MH_BASE_ARG(M, link));
   double total = tA + 0.0;
   if (total < 0.0) total = 0.0;
   const double cand = dist / total;
   return (cand < A_INF_) ? cand : A_INF_;
+}
+#endif
+
+#ifdef MH_ARTIC_PAIR_TU
+// ---- sphere pairs between links (mh_artic_model.npairs; the model's pair block is read from M.pr).  Every lane computes the same numbers. ----
+MH_DEV void sphere_centre(const mh_artic_model& m, const Lay& Y, const double* g, int s, double c[3]) {
+  const int l = m.sphere_link[s];
+  double rc[3]; mat3vec(g + Y.R + 9 * l, m.sphere_center[s], rc);
+  for (int k = 0; k < 3; k++) c[k] = g[Y.x + 3 * l + k] + rc[k];
+}
+// find_contacts_sphere_sphere's distance (CCD.inl:1189-1190): d = cA - cB, dist = (|d| - rA) - rB, n = d / |d| (from b to a)
+MH_DEV double pair_dist(const Model& M, const Lay& Y, const double* g, int k, double cA[3], double cB[3], double n[3]) {
+  const mh_artic_model& m = M.m;
+  const int a = M.pr.a[k], b = M.pr.b[k];
+  sphere_centre(m, Y, g, a, cA); sphere_centre(m, Y, g, b, cB);
+  const double d[3] = { cA[0] - cB[0], cA[1] - cB[1], cA[2] - cB[2] };
+  const double len = sqrt((d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]);
+  for (int c = 0; c < 3; c++) n[c] = d[c] / len;
+  return (len - m.sphere_radius[a]) - m.sphere_radius[b];
+}
+// the contact point halfway between the closest points (CCD.inl:1195-1200), or false
+MH_DEV bool pair_contact(const Model& M, const Lay& Y, const double* g, int k, double TOL, double p[3], double n[3], double& dist) {
+  double cA[3], cB[3];
+  dist = pair_dist(M, Y, g, k, cA, cB, n);
+  if (dist > TOL) return false;
+  const double rA = M.m.sphere_radius[M.pr.a[k]], rB = M.m.sphere_radius[M.pr.b[k]];
+  for (int c = 0; c < 3; c++) p[c] = ((cA[c] - n[c] * rA) + (cB[c] + n[c] * rB)) * 0.5;
+  return true;
+}
+// the constraint velocity of a contact between links la and lb (lb < 0: the plane): A's point velocity along d minus B's
+MH_DEV double pair_vel(const LayC& Z, const double* g, int la, int lb, const double* p, const double* d) {
+  double v = point_vel_dir(g + Z.V + 6 * la, p, d);
+  if (lb >= 0) v = v - point_vel_dir(g + Z.V + 6 * lb, p, d);
+  return v;
+}
+// the sphere rule of conservative advancement for pair k (CCD.cpp:138-235), the ladder CA_step walks for the plane; uniform
+MH_DEV double CA_pair(const Model& M, const Lay& Y, const LayC& Z, const double* g, int k) {
+  const mh_artic_model& m = M.m;
+  const int sa = M.pr.a[k], sb = M.pr.b[k], la = m.sphere_link[sa], lb = m.sphere_link[sb];
+  double cA[3], cB[3], n[3], p[3], nn[3], d2;
+  const double dist = pair_dist(M, Y, g, k, cA, cB, n);
+  if (!(dist > NEAR_ZERO_)) {
+    const bool has = pair_contact(M, Y, g, k, NEAR_ZERO_, p, nn, d2);
+    if (has && fabs(pair_vel(Z, g, la, lb, p, nn)) < NEAR_ZERO_ * 10) return A_INF_;
+  }
+  if (dist <= 0.0) {
+    if (!pair_contact(M, Y, g, k, NEAR_ZERO_, p, nn, d2)) return A_INF_;
+    if (pair_vel(Z, g, la, lb, p, nn) < -NEAR_ZERO_) return 0.0;
+    return A_INF_;
+  }
+  const double mn[3] = { -n[0], -n[1], -n[2] };
+  const double tA = calc_max_dist(m, Y, g, la, mn, rmax_of(m, sa), (M.anc[la] & 1u) != 0u);
+  const double tB = calc_max_dist(m, Y, g, lb, n, rmax_of(m, sb), (M.anc[lb] & 1u) != 0u);
+  double total = tA + tB;
+  if (total < 0.0) total = 0.0;
+  const double cand = dist / total;
+  return (cand < A_INF_) ? cand : A_INF_;
+}
+// one link's share of a contact row: the wrench [dir, (p - com) x dir] about link l's COM times column j of calc_jacobian at that COM
+MH_DEV double row_term(const mh_artic_model& m, const Lay& Y, const double* g, int l, int j, const double* p, const double* dir) {
+  double rc[3], com[3], r[3], w[6];
+  mat3vec(g + Y.R + 9 * l, m.com[l], rc);
+  for (int k = 0; k < 3; k++) { com[k] = g[Y.x + 3 * l + k] + rc[k]; r[k] = p[k] - com[k]; }
+  cross3(r, dir, w + 3);
+  for (int k = 0; k < 3; k++) w[k] = dir[k];
+  const double* Sj = g + Y.S + 6 * j;
+  double acc = 0.0;
+  for (int k = 0; k < 6; k++) {
+    double Jk;
+    if (k >= 3) Jk = Sj[k - 3];
+    else { const int k1 = (k + 1) % 3, k2 = (k + 2) % 3; Jk = Sj[3 + k] + (Sj[k1] * com[k2] - Sj[k2] * com[k1]); }
+    acc = acc + w[k] * Jk;
+  }
+  return acc;
+}
+// entry j of the row of a contact between links la and lb (lb < 0: the plane) at p along dir: A's term with dir plus B's with -dir, A's first;
+// a joint that is an ancestor of only one link gets that term alone, of neither 0.0 (ICH:1817-1895)
+MH_DEV double contact_row(const Model& M, const Lay& Y, const double* g, int la, int lb, int j, const double* p, const double* dir) {
+  const bool inA = ((M.anc[la] >> j) & 1u) != 0u, inB = lb >= 0 && ((M.anc[lb] >> j) & 1u) != 0u;
+  double val = 0.0;
+  if (inA) val = row_term(M.m, Y, g, la, j, p, dir);
+  if (inB) {
+    const double nd[3] = { -dir[0], -dir[1], -dir[2] };
+    const double tb = row_term(M.m, Y, g, lb, j, p, nd);
+    val = inA ? val + tb : tb;
+  }
+  return val;
 }
 #endif
 
@@ -313,7 +440,9 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   link_velocities(M, Y, Z, g);
   const double qdi = (lane < nj) ? g[Y.qd + lane] : 0.0;
   bool imp_c = false;
-#ifdef MH_ARTIC_BOX_TU
+#ifdef MH_ARTIC_PAIR_TU
+  for (int i = lane; i < nc; i += 64) imp_c = imp_c || pair_vel(Z, g, ints[I_LINK + i], ints[I_LINKB + i], g + Z.cp + 12 * i, g + Z.cp + 12 * i + 3) < -NEAR_ZERO_;
+#elif defined(MH_ARTIC_BOX_TU)
   for (int i = lane; i < nc; i += 64) imp_c = imp_c || point_vel_dir(g + Z.V + 6 * ints[I_LINK + i], g + Z.cp + 12 * i, g + Z.cp + 12 * i + 3) < -NEAR_ZERO_;
 #else
   if (lane < nc) imp_c = point_vel_dir(g + Z.V + 6 * ints[I_LINK + lane], g + Z.cp + 12 * lane, g + Z.cp + 12 * lane + 3) < -NEAR_ZERO_;
@@ -343,6 +472,9 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
     const int d = e / (nc * nj), i = (e - d * nc * nj) / nj, j = e - d * nc * nj - i * nj;
     const int l = ints[I_LINK + i];
     double val = 0.0;
+#ifdef MH_ARTIC_PAIR_TU
+    val = contact_row(M, Y, g, l, ints[I_LINKB + i], j, g + Z.cp + 12 * i, g + Z.cp + 12 * i + 3 + 3 * d);
+#else
     if ((M.anc[l] >> j) & 1u) {
       double rc[3], com[3], r[3], w[6];
       mat3vec(g + Y.R + 9 * l, m.com[l], rc);
@@ -360,6 +492,7 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
       }
       val = acc;
     }
+#endif
     C[e] = val;
   }
   wave_sync();
@@ -369,7 +502,13 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
     XC[e] = acc;
   }
   wave_sync();
+#ifdef MH_ARTIC_PAIR_TU
+  if (Z.G < 0 && !ws) { status |= MH_WORLD_UNSUPPORTED; return; }   // (the host allocates the workspace for every pair batch)
+  double* G = (Z.G < 0) ? ws + WS_PAIR_G : g + Z.G;
+  double* CL = g + Z.CL; double* Cv = g + Z.Cv; double* Lv = g + Z.Lv;
+#else
   double* G = g + Z.G; double* CL = g + Z.CL; double* Cv = g + Z.Cv; double* Lv = g + Z.Lv;
+#endif
   for (int e = lane; e < 6 * nc * nc; e += 64) {                  // the cross blocks (ICH:2127-2147)
     const int blk = e / (nc * nc), ij = e - blk * nc * nc, i = ij / nc, j = ij - i * nc;
     const int a = (blk < 3) ? 0 : ((blk < 5) ? 1 : 2), b = (blk < 3) ? blk : ((blk < 5) ? blk - 2 : 2);
@@ -659,7 +798,11 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   }
   link_velocities(M, Y, Z, g);                                    // ICH:157-167
   bool tol = false;
+#ifdef MH_ARTIC_PAIR_TU
+  if (lane < nc) tol = pair_vel(Z, g, ints[I_LINK + lane], ints[I_LINKB + lane], g + Z.cp + 12 * lane, g + Z.cp + 12 * lane + 3) < -NEAR_ZERO_;
+#else
   if (lane < nc) tol = point_vel_dir(g + Z.V + 6 * ints[I_LINK + lane], g + Z.cp + 12 * lane, g + Z.cp + 12 * lane + 3) < -NEAR_ZERO_;
+#endif
   if (lane >= LOFF && lane < LOFF + nl) { const int c = idx[lane - LOFF]; const double v = g[Y.qd + (c & 255)]; tol = ((c & 256) ? -v : v) < -NEAR_ZERO_; }
   if (ballot(tol) != 0ull) status |= MH_WORLD_IMPACT_TOL;
 }
@@ -690,9 +833,12 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
     kin_ok = false;
     link_velocities(M, Y, Z, g);
     double CA = A_INF_;
-    for (int s = 0; s < m.nspheres; s++) { const double e = CA_step(m, Y, Z, g, s); CA = (e < CA) ? e : CA; }
+    for (int s = 0; s < m.nspheres; s++) { MH_SKIP_MASKED(M, s) const double e = CA_step(m, Y, Z, g, s MH_BASE_ARG(M, m.sphere_link[s])); CA = (e < CA) ? e : CA; }
 #ifdef MH_ARTIC_BOX_TU
     for (int k = 0; k < M.bx.n; k++) { const double e = CA_box(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
+#endif
+#ifdef MH_ARTIC_PAIR_TU
+    for (int k = 0; k < M.pr.n; k++) { const double e = CA_pair(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
 #endif
     CA = uni(CA);
     if (CA <= 0.0) { kin_ok = true; break; }
@@ -722,6 +868,7 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
   int* ints = reinterpret_cast<int*>(g + Z.ints);
   int nc = 0;
   for (int s = 0; s < m.nspheres; s++) {
+    MH_SKIP_MASKED(M, s)
     double cp[3]; sphere_in_plane(m, Y, g, s, cp);
     const double dist = cp[1] + (-1.0 * m.sphere_radius[s]);
     double p[3];
@@ -731,6 +878,7 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
         double n[3], sv[3], tv[3]; plane_n(m, n); orthonormal_basis(n, sv, tv);
         for (int k = 0; k < 3; k++) { c[k] = p[k]; c[3 + k] = n[k]; c[6 + k] = sv[k]; c[9 + k] = tv[k]; }
         ints[I_LINK + nc] = m.sphere_link[s];
+        MH_SET_LINKB(nc, -1)
       }
       nc++;
     }
@@ -747,9 +895,24 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
         double n[3], sv[3], tv[3]; plane_n(m, n); orthonormal_basis(n, sv, tv);
         for (int c2 = 0; c2 < 3; c2++) { c[c2] = v[c2]; c[3 + c2] = n[c2]; c[6 + c2] = sv[c2]; c[9 + c2] = tv[c2]; }
         ints[I_LINK + nc] = M.bx.link[k];
+        MH_SET_LINKB(nc, -1)
       }
       nc++;
     }
+  }
+#endif
+#ifdef MH_ARTIC_PAIR_TU
+  for (int k = 0; k < M.pr.n; k++) {                               // find_contacts_sphere_sphere: at most one contact per pair
+    double p[3], n[3], dist;
+    if (!pair_contact(M, Y, g, k, m.contact_dist_thresh, p, n, dist) || !(dist < m.contact_dist_thresh)) continue;
+    if (lane == 0) {
+      double* c = g + Z.cp + 12 * nc;
+      double sv[3], tv[3]; orthonormal_basis(n, sv, tv);
+      for (int c2 = 0; c2 < 3; c2++) { c[c2] = p[c2]; c[3 + c2] = n[c2]; c[6 + c2] = sv[c2]; c[9 + c2] = tv[c2]; }
+      ints[I_LINK + nc] = m.sphere_link[M.pr.a[k]];
+      ints[I_LINKB + nc] = m.sphere_link[M.pr.b[k]];
+    }
+    nc++;
   }
 #endif
   nc = uni(nc);
@@ -778,9 +941,14 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
 #endif
 #ifdef MH_ARTIC_BOX_TU
   // the boxes' distances follow the spheres' in uC; up to NCL contacts: their distances and Cn / Cn X live in the HBM workspace behind the LCP
+#ifdef MH_ARTIC_PAIR_TU
+  // ... and the pairs' follow the boxes'; a sphere masked off the plane has no entry
+  const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres, ngeo = (nsph - popc((uint64_t)(unsigned)M.pr.no_plane)) + M.bx.n + M.pr.n;
+#else
   const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres, ngeo = nsph + M.bx.n;
+#endif
   const int nu = ngeo + 2 * nj;
-  double* uO = g + Z.W; double* uN = uO + 48; double* uT = uN + 48;   // (nu <= 12 + 32)
+  double* uO = g + Z.W; double* uN = uO + USTRIDE; double* uT = uN + USTRIDE;   // (nu <= 12 + 32, with pairs 18 + 32)
   int* idx = reinterpret_cast<int*>(g + Z.QX);
   int* ints = reinterpret_cast<int*>(g + Z.ints);
   double* dist = ws + WS_DIST;
@@ -798,13 +966,22 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
     wave_sync();
     kin_inertia(M, Y, g);
     double vio = A_INF_;
+#ifdef MH_ARTIC_PAIR_TU
+    int o = 0;
+    for (int s2 = 0; s2 < nsph; s2++) { MH_SKIP_MASKED(M, s2) double cp[3]; sphere_in_plane(m, Y, g, s2, cp); const double d = cp[1] + (-1.0 * m.sphere_radius[s2]); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+    for (int k = 0; k < M.bx.n; k++) { double pa[3], pp[3]; const double d = box_dist(M, Y, g, k, pa, pp); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+    for (int k = 0; k < M.pr.n; k++) { double cA[3], cB[3], n[3]; const double d = pair_dist(M, Y, g, k, cA, cB, n); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+    const double q0 = g[Y.q];
+    const double a = (hi0 - q0) - 0.0, b2 = (q0 + 0.0) - lo0;
+    if (lane < nj) { out[ngeo + 2 * lane] = a; out[ngeo + 2 * lane + 1] = b2; }
+#elif defined(MH_ARTIC_BOX_TU)
     for (int s2 = 0; s2 < nsph; s2++) { double cp[3]; sphere_in_plane(m, Y, g, s2, cp); const double d = cp[1] + (-1.0 * m.sphere_radius[s2]); if (lane == 0) out[s2] = d; vio = (d < vio) ? d : vio; }
-#ifdef MH_ARTIC_BOX_TU
     for (int k = 0; k < M.bx.n; k++) { double pa[3], pp[3]; const double d = box_dist(M, Y, g, k, pa, pp); if (lane == 0) out[nsph + k] = d; vio = (d < vio) ? d : vio; }
     const double q0 = g[Y.q];
     const double a = (hi0 - q0) - 0.0, b2 = (q0 + 0.0) - lo0;
     if (lane < nj) { out[ngeo + 2 * lane] = a; out[ngeo + 2 * lane + 1] = b2; }
 #else
+    for (int s2 = 0; s2 < nsph; s2++) { double cp[3]; sphere_in_plane(m, Y, g, s2, cp); const double d = cp[1] + (-1.0 * m.sphere_radius[s2]); if (lane == 0) out[s2] = d; vio = (d < vio) ? d : vio; }
     const double q0 = g[Y.q];
     const double a = (hi0 - q0) - 0.0, b2 = (q0 + 0.0) - lo0;
     if (lane < nj) { out[nsph + 2 * lane] = a; out[nsph + 2 * lane + 1] = b2; }
@@ -831,6 +1008,7 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
     // the contact list (the link frames of the current q are in LDS: eval ran at it)
     int nc = 0;
     for (int s2 = 0; s2 < nsph; s2++) {
+      MH_SKIP_MASKED(M, s2)
       double cp[3]; sphere_in_plane(m, Y, g, s2, cp);
       const double low = cp[1] + (-1.0 * m.sphere_radius[s2]);
       double p[3], nn[3];
@@ -842,7 +1020,7 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
         for (int k = 0; k < 3; k++) nn[k] = d[k] / len;
       } else { have = find_contact(m, Y, g, s2, NEAR_ZERO_, p); plane_n(m, nn); }
       if (have) {
-        if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int k = 0; k < 3; k++) { c[k] = p[k]; c[3 + k] = nn[k]; } ints[I_LINK + nc] = m.sphere_link[s2]; dist[nc] = low; }
+        if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int k = 0; k < 3; k++) { c[k] = p[k]; c[3 + k] = nn[k]; } ints[I_LINK + nc] = m.sphere_link[s2]; MH_SET_LINKB(nc, -1) dist[nc] = low; }
         nc++;
       }
     }
@@ -854,16 +1032,28 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
         double pb[3]; from_plane(m, pp[0], 0.0, pp[2], pb);
         const double d[3] = { pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2] };
         const double len = sqrt((d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]);
-        if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int c2 = 0; c2 < 3; c2++) { c[c2] = pa[c2]; c[3 + c2] = d[c2] / len; } ints[I_LINK + nc] = M.bx.link[k]; dist[nc] = low; }
+        if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int c2 = 0; c2 < 3; c2++) { c[c2] = pa[c2]; c[3 + c2] = d[c2] / len; } ints[I_LINK + nc] = M.bx.link[k]; MH_SET_LINKB(nc, -1) dist[nc] = low; }
         nc++;
       } else {
         for (int i = 0; i < 8; i++) {
           double v[3], q[3]; box_vertex(M, Y, g, k, i, v); to_plane(m, v, q);
           if (!(q[1] <= NEAR_ZERO_)) continue;
-          if (lane == 0) { double* c = g + Z.cp + 12 * nc; double nn[3]; plane_n(m, nn); for (int c2 = 0; c2 < 3; c2++) { c[c2] = v[c2]; c[3 + c2] = nn[c2]; } ints[I_LINK + nc] = M.bx.link[k]; dist[nc] = q[1]; }
+          if (lane == 0) { double* c = g + Z.cp + 12 * nc; double nn[3]; plane_n(m, nn); for (int c2 = 0; c2 < 3; c2++) { c[c2] = v[c2]; c[3 + c2] = nn[c2]; } ints[I_LINK + nc] = M.bx.link[k]; MH_SET_LINKB(nc, -1) dist[nc] = q[1]; }
           nc++;
         }
       }
+    }
+#endif
+#ifdef MH_ARTIC_PAIR_TU
+    for (int k = 0; k < M.pr.n; k++) {                             // CStab:306-345 for a sphere pair: the synthetic contact on A's surface, or find_contacts'
+      double cA[3], cB[3], n[3], p[3];
+      const double low = pair_dist(M, Y, g, k, cA, cB, n);
+      const double rA = m.sphere_radius[M.pr.a[k]], rB = m.sphere_radius[M.pr.b[k]];
+      if (low >= NEAR_ZERO_) { for (int c2 = 0; c2 < 3; c2++) p[c2] = cA[c2] - n[c2] * rA; }
+      else { for (int c2 = 0; c2 < 3; c2++) p[c2] = ((cA[c2] - n[c2] * rA) + (cB[c2] + n[c2] * rB)) * 0.5; }
+      if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int c2 = 0; c2 < 3; c2++) { c[c2] = p[c2]; c[3 + c2] = n[c2]; }
+                       ints[I_LINK + nc] = m.sphere_link[M.pr.a[k]]; ints[I_LINKB + nc] = m.sphere_link[M.pr.b[k]]; dist[nc] = low; }
+      nc++;
     }
 #endif
     nc = uni(nc);
@@ -889,6 +1079,9 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
         const int i = e / nj, j = e - i * nj;
         const int l = ints[I_LINK + i];
         double val = 0.0;
+#ifdef MH_ARTIC_PAIR_TU
+        val = contact_row(M, Y, g, l, ints[I_LINKB + i], j, g + Z.cp + 12 * i, g + Z.cp + 12 * i + 3);
+#else
         if ((M.anc[l] >> j) & 1u) {
           double rc[3], com[3], r[3], w[6];
           mat3vec(g + Y.R + 9 * l, m.com[l], rc);
@@ -906,6 +1099,7 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
           }
           val = acc;
         }
+#endif
         C[e] = val;
       }
       wave_sync();
@@ -1058,7 +1252,7 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   const LayC Z(Y.total, nj, Y.I6, 60 * nj + 12);
   mh_world_aux* aux = auxg + b;
 #ifdef MH_ARTIC_BOX_TU
-  double* ws = wsg ? wsg + (size_t)b * WS_BOX : nullptr;
+  double* ws = wsg ? wsg + (size_t)b * WS_WORLD : nullptr;
 #else
   double* ws = wsg ? wsg + (size_t)b * 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE : nullptr;   // Drumwright-Shell: _MM and the Lemke LU workspace
 #endif
@@ -1121,7 +1315,35 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   }
 }
 
-#if defined(MH_ARTIC_BOX_TU) && !defined(MH_ARTIC_POSE_TU)
+#if defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_POSE_TU)
+// the pair kernels (mh_artic_pair.hip): {plain, stab} x {undriven, driven} in angle coordinates; one world per workgroup's LDS image as the box kernels
+__global__ __launch_bounds__(64)
+void k_artic_step_pair(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                             mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
+#elif defined(MH_ARTIC_PAIR_TU)
+// the same four in pose coordinates (mh_artic_pair_pose.hip)
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_pair_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+#elif defined(MH_ARTIC_BOX_TU) && !defined(MH_ARTIC_POSE_TU)
 // the box kernels (mh_artic_box.hip): {plain, stab} x {undriven, driven} in angle coordinates; their LDS image holds one world per SIMD or two
 // (DESIGN 4.4), so no waves-per-EU bound
 __global__ __launch_bounds__(64)

@@ -997,15 +997,26 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
       geoms.push_back(g);
     }
   }
-  // every pair of the body's own geometries must be disabled (the whole body, or link by link) -- geometries riding on one link cannot meet
+  // pairs of the body's own geometries that are not disabled (the whole body, or link by link): two spheres on different moving links become a
+  // sphere pair (mh_artic_model.npairs); anything else is refused -- geometries riding on one link cannot meet
+  std::vector<std::pair<size_t, size_t> > gpairs; std::vector<char> in_pair(geoms.size(), 0);
   if (!pair_disabled(abid, abid))
-    for (size_t x = 0; x < geoms.size(); x++) for (size_t y = x + 1; y < geoms.size(); y++)
-      if (geoms[x].link != geoms[y].link && !pair_disabled(geoms[x].id, geoms[y].id))
-        return fail("links %s and %s can collide: link-link contact is not supported (add a <DisabledPair>)", geoms[x].id.c_str(), geoms[y].id.c_str());
-  if (!plane_body.empty()) {
-    for (const UrdfGeom& g : geoms) {
+    for (size_t x = 0; x < geoms.size(); x++) for (size_t y = x + 1; y < geoms.size(); y++) {
+      if (geoms[x].link == geoms[y].link || pair_disabled(geoms[x].id, geoms[y].id)) continue;
+      if (geoms[x].link < 0 || geoms[y].link < 0)
+        return fail("links %s and %s can collide: contact with geometry on the fixed base (a static obstacle) is not supported (add a <DisabledPair>)", geoms[x].id.c_str(), geoms[y].id.c_str());
+      if (!geoms[x].sphere || !geoms[y].sphere)
+        return fail("links %s and %s can collide: link-link contact is supported between two Spheres only, not for a Box or another primitive (add a <DisabledPair>)", geoms[x].id.c_str(), geoms[y].id.c_str());
+      gpairs.push_back(std::make_pair(x, y)); in_pair[x] = in_pair[y] = 1;
+    }
+  if (gpairs.size() > (size_t)MH_ARTIC_MAX_PAIRS) return fail("more than %d link-link sphere pairs (add <DisabledPair>s)", MH_ARTIC_MAX_PAIRS);
+  std::vector<int> sphere_of(geoms.size(), -1);
+  if (!plane_body.empty() || !gpairs.empty()) {
+    for (size_t gi = 0; gi < geoms.size(); gi++) {
+      const UrdfGeom& g = geoms[gi];
       if (g.link < 0) continue;                                              // rides on the fixed base: static against the static plane
-      if (pair_disabled(g.id, plane_body) || pair_disabled(abid, plane_body)) continue;
+      const bool meets = !plane_body.empty() && !(pair_disabled(g.id, plane_body) || pair_disabled(abid, plane_body));
+      if (!meets && !in_pair[gi]) continue;
       if (g.box) {
         if (m.nboxes >= MH_ARTIC_MAX_BOXES) return fail("more than %d link boxes", MH_ARTIC_MAX_BOXES);
         if (!(g.dims[0] > 0.0 && g.dims[1] > 0.0 && g.dims[2] > 0.0)) return fail("link %s: a box needs three positive edge lengths", g.id.c_str());
@@ -1020,7 +1031,23 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
       const int s = m.nspheres++;
       m.sphere_link[s] = g.link; m.sphere_radius[s] = g.radius;
       for (int k = 0; k < 3; k++) m.sphere_center[s][k] = g.center[k];
+      sphere_of[gi] = s;
+      if (!meets) m.sphere_no_plane |= 1 << s;                               // in a pair only: its pair with the plane body is disabled, or there is no plane
     }
+    for (const auto& gp : gpairs) { const int k = m.npairs++; m.pair_a[k] = sphere_of[gp.first]; m.pair_b[k] = sphere_of[gp.second]; }
+  }
+  if (plane_body.empty() && !gpairs.empty()) {
+    // no plane body: every sphere is masked off the plane; the plane frame only has to be a rotation, the parameters are the body's own pair's
+    for (int k = 0; k < 9; k++) m.plane_R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    m.cp_nk = 4;
+    for (const CP& p : cps) {
+      const bool a_in = p.a == abid || link_of.count(p.a), b_in = p.b == abid || link_of.count(p.b);
+      if (a_in && b_in) { m.cp_epsilon = p.eps; m.cp_mu_coulomb = p.mu; m.cp_mu_viscous = p.muv; m.cp_compliance = p.comp; m.cp_nk = p.nk; break; }
+    }
+    m.min_step_size = std::sqrt(2.220446049250313e-16); m.contact_dist_thresh = 1e-6;
+    { const Attrs sa = attrs_of(sim); if (sa.has("min-step-size")) m.min_step_size = std::atof(sa.str("min-step-size").c_str()); }
+  }
+  if (!plane_body.empty()) {
     // the plane: PlanePrimitive's +Y is the normal; body pose times primitive pose, expressed in the model (base) frame
     double Rw[9]; mat3mul(plane_Rb, plane_prim.R, Rw);
     double ow[3]; mat3vec(plane_Rb, plane_prim.o, ow); for (int k = 0; k < 3; k++) ow[k] += plane_x[k];

@@ -1,0 +1,144 @@
+"""Fuzz of the pair kernels (include/moby_hip_artic.h, mh_artic_model.npairs / sphere_no_plane; mh_artic_pair.hip, mh_artic_pair_pose.hip)
+against the pair reference (tests/native/artic_pair_ref.cpp): random trees with one or two roots -- a random floating body
+(tests/test_artic_pose.py random_floating) or a random fixed-base chain, and half the time a second chain of 1-2 hinges hanging from the world
+beside it -- 2-4 spheres of random size on random links placed so that they start close to one another, every pair of spheres on different
+links listed with probability 0.7, a random plane mask, sometimes a box too, against a floor under the no-slip or the Drumwright-Shell model;
+the stabiliser on or off, CRB or FSAB, angle or pose coordinates (floating bases), random states and random drives changed every launch of 10
+steps; q, qd, the poses, the rand() stream, the warm starts and the counters bit for bit.
+python tests/tools/fuzz_artic_pair.py [seed0] [cases]"""
+import os
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from moby_amd import _lib, artic as A, scene as S  # noqa: E402
+from tests.artic_pair_ref import build_pair_ref  # noqa: E402
+from tests.test_artic_drive import FIELDS    # noqa: E402
+from tests.test_artic_pose import rand_rot, random_floating  # noqa: E402
+
+
+def add_root(m, rng):
+    """a second chain of 1-2 hinges about z hanging from the world beside the first tree (joints appended, parent -1)"""
+    n0 = m.nj
+    x = np.array([rng.uniform(0.2, 0.5), rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1)])
+    for k in range(int(rng.integers(1, 3))):
+        j = m.nj
+        if j >= A.MH_ARTIC_MAX_JOINTS: break
+        m.parent[j] = -1 if k == 0 else j - 1; m.jtype[j] = A.MH_JOINT_REVOLUTE
+        for c in range(9): m.Rrel[j][c] = float(c % 4 == 0); m.inertia[j][c] = 0.01 * float(c % 4 == 0)
+        for c in range(3):
+            m.trel[j][c] = x[c] if k == 0 else (0.0, -0.3, 0.0)[c]; m.axis[j][c] = float(c == 2); m.com[j][c] = (0.0, -0.15, 0.0)[c]
+        m.mass[j] = float(rng.uniform(0.2, 1.0)); m.lolimit[j] = -np.finfo(float).max; m.hilimit[j] = np.finfo(float).max; m.limit_restitution[j] = 0.0
+        m.nj = j + 1
+    return n0
+
+
+def make_case(seed):
+    rng = np.random.default_rng(seed)
+    floating = rng.random() < 0.6
+    if floating:
+        m = random_floating(rng)
+        first = 5
+    else:
+        m = A.chain_model(int(rng.integers(2, 4)), gravity=(0.0, -9.81, 0.0))
+        first = 0
+    root2 = add_root(m, rng) if rng.random() < 0.5 else None
+    nj = m.nj
+    for j in range(6 if floating else 0, nj):
+        if rng.random() < 0.5:
+            m.lolimit[j] = -rng.uniform(0.05, 0.6); m.hilimit[j] = rng.uniform(0.05, 0.6); m.limit_restitution[j] = rng.choice([0.0, 0.4])
+    eps = float(rng.choice([0.0, 0.3])); mu = float(rng.choice([100.0, 0.5, 0.05]))
+    floor = (0.0, float(rng.uniform(-0.6, -0.2)), 0.0)
+    links = list(range(first, nj))
+    ns = int(rng.integers(2, 5))
+    sl = [int(rng.choice(links)) for _ in range(ns)]
+    if root2 is not None: sl[-1] = int(rng.integers(root2, nj))          # one sphere on the second root
+    if len(set(sl)) == 1 and len(links) > 1: sl[0] = [l for l in links if l != sl[0]][0]
+    A.add_spheres(m, [(l, rng.uniform(-0.15, 0.15, 3), float(rng.uniform(0.05, 0.2))) for l in sl], plane_normal=(0.0, 1.0, 0.0),
+                  plane_point=floor, epsilon=eps, mu_coulomb=mu)
+    if rng.random() < 0.3:
+        A.add_boxes(m, [(int(rng.choice(links)), rng.uniform(-0.2, 0.2, 3), rand_rot(rng) if rng.random() < 0.7 else np.eye(3), rng.uniform(0.05, 0.4, 3))],
+                    plane_normal=(0.0, 1.0, 0.0), plane_point=floor, epsilon=eps, mu_coulomb=mu)
+    pairs = [(a, b) if rng.random() < 0.5 else (b, a) for a in range(ns) for b in range(a + 1, ns) if sl[a] != sl[b] and rng.random() < 0.7]
+    A.add_pairs(m, pairs[:A.MH_ARTIC_MAX_PAIRS], no_plane=[s for s in range(ns) if rng.random() < 0.3])
+    m.cstab_max_iterations = int(rng.choice([0, 10]))
+    m.algorithm = int(rng.integers(0, 2))
+    B = int(rng.integers(1, 5))
+    q = np.zeros((B, nj)); qd = np.zeros((B, nj))
+    if floating:
+        q[:, :3] = rng.uniform(-0.1, 0.1, (B, 3)); q[:, 3:6] = rng.uniform(-1.0, 1.0, (B, 3))
+        qd[:, :3] = rng.uniform(-1.0, 1.0, (B, 3)); qd[:, 3:6] = rng.uniform(-5.0, 5.0, (B, 3))
+        qd[:, 6:] = rng.uniform(-2.0, 2.0, (B, nj - 6))
+    else:
+        q[:] = rng.uniform(-0.5, 0.5, (B, nj)); qd[:] = rng.uniform(-2.0, 2.0, (B, nj))
+    pose = floating and rng.random() < 0.5
+    launches = []
+    for _ in range(int(rng.integers(2, 6))):
+        if rng.random() < 0.3:
+            launches.append(None)
+            continue
+        rows = 10 if rng.random() < 0.5 else 1
+        sh = (rows, B, nj) if rows > 1 else (B, nj)
+        launches.append(A.Drive(kp=rng.uniform(0.0, 10.0, (B, nj)), kv=rng.uniform(0.0, 0.5, (B, nj)), q_des=rng.uniform(-0.5, 0.5, sh),
+                                qd_des=rng.uniform(-1.0, 1.0, sh), tau_ff=rng.uniform(-2.0, 2.0, sh)))
+    return m, q, qd, pose, launches
+
+
+if __name__ == "__main__":
+    seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 6100
+    cases = int(sys.argv[2]) if len(sys.argv) > 2 else 300
+    ref = build_pair_ref(Path(tempfile.mkdtemp()))
+    SKIP_AFTER = 5.0
+    bad = skipped = solves = failed = unsup = rows16 = 0
+    if len(sys.argv) > 3:                                                     # (no GPU: list what the cases hold and what the reference makes of them)
+        for case in range(cases):
+            m, q0, qd0, pose, launches = make_case(seed0 + case)
+            q_r, qd_r, aux_r = q0.copy(), qd0.copy(), S.new_aux(q0.shape[0])
+            ref.step(m, q_r, qd_r, aux_r, 1e-3, 10 * len(launches))
+            print(seed0 + case, "nj", m.nj, "pairs", m.npairs, "mask", m.sphere_no_plane, "solves", int(aux_r["lcp_solves"].sum()), "status", list(aux_r["status"]))
+        sys.exit(0)
+    for case in range(cases):
+        m, q0, qd0, pose, launches = make_case(seed0 + case)
+        B, nj = q0.shape
+        try:
+            ab = A.ArticBatch(m, np.zeros_like(q0), np.zeros_like(qd0), base_coords="pose" if pose else "angles")
+        except _lib.MobyHipError as e:                                         # the pair kernels' LDS image beyond 64 KB (more than 10 joints)
+            assert "LDS image" in str(e), e
+            skipped += 1; print("seed %d refused by create: %s" % (seed0 + case, e), flush=True); continue
+        P0 = ab.base_pose() if pose else None
+        # the reference first: a world that keeps hitting the mini-step cap costs minutes on either side -- skip such a case
+        q_r, qd_r, aux_r = q0.copy(), qd0.copy(), S.new_aux(B)
+        P_r = None if P0 is None else P0.copy()
+        t0 = time.time(); done = 0
+        for d in launches:
+            if time.time() - t0 > SKIP_AFTER:
+                break
+            ref.step(m, q_r, qd_r, aux_r, 1e-3, 10, pose=P_r, drive=d); done += 1
+        if done < len(launches):
+            ab.close(); skipped += 1; print("seed %d skipped: the reference needed more than %g s" % (seed0 + case, SKIP_AFTER), flush=True); continue
+        ab.upload(q0, qd0, S.new_aux(B))
+        for d in launches:
+            ab.step(1e-3, 10, drive=d)
+        q_g, qd_g, aux_g = ab.download()
+        P_g = ab.base_pose() if pose else None
+        ab.close()
+        same = (np.array_equal(q_g, q_r, equal_nan=True) and np.array_equal(qd_g, qd_r, equal_nan=True)
+                and (not pose or np.array_equal(P_g, P_r, equal_nan=True)) and all(np.array_equal(aux_g[f], aux_r[f]) for f in FIELDS))
+        for w in range(B):
+            k = int(aux_r["vns_size"][w]); same = same and np.array_equal(aux_g["vns"][w, :k], aux_r["vns"][w, :k])
+            k = int(aux_r["zlast_size"][w]); same = same and np.array_equal(aux_g["zlast"][w, :k], aux_r["zlast"][w, :k])
+        solves += int(aux_r["lcp_solves"].sum()); failed += int(((aux_r["status"] & S.MH_WORLD_LCP_FAILED) != 0).sum())
+        unsup += int(((aux_r["status"] & S.MH_WORLD_UNSUPPORTED) != 0).sum())
+        if not same:
+            bad += 1
+            print("MISMATCH seed %d: nj %d pairs %d boxes %d spheres %d alg %d stab %d pose %d; max |dq| %.3e; %s" % (
+                seed0 + case, nj, m.npairs, m.nboxes, m.nspheres, m.algorithm, m.cstab_max_iterations, pose, np.nanmax(np.abs(q_g - q_r)),
+                [f for f in FIELDS if not np.array_equal(aux_g[f], aux_r[f])]), flush=True)
+    print("fuzz_artic_pair: %d cases from seed %d (%d skipped: too slow for the reference, or too many joints for the pair kernels), %d mismatches; %d LCP solves, %d worlds ended by an "
+          "exception, %d over capacity" % (cases, seed0, skipped, bad, solves, failed, unsup))
+    sys.exit(1 if bad else 0)
