@@ -246,6 +246,8 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    include/moby_hip_artic.h, mh_artic_model.nboxes).
                                             key 13: articulated bodies with link spheres or boxes stepped by the pair kernels (1, for batches created after it; default 0:
                                                    their own kernels; include/moby_hip_artic.h, mh_artic_model.npairs).
+                                            key 14: articulated bodies with link spheres, boxes or sphere pairs stepped by the box-sphere kernels (1, for batches created
+                                                   after it; default 0: their own kernels; include/moby_hip_artic.h, mh_artic_model.pair_kind).
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);

@@ -41,6 +41,8 @@ extern "C" {
 #define MH_ARTIC_MAX_SPHERES 4    /* sphere primitives carried by links (contacts against the one static plane) */
 #define MH_ARTIC_MAX_BOXES 8      /* box primitives carried by links (the same plane) */
 #define MH_ARTIC_MAX_PAIRS 6      /* every pair of MH_ARTIC_MAX_SPHERES spheres */
+#define MH_ARTIC_PAIR_SPHERES    0   /* mh_artic_model.pair_kind */
+#define MH_ARTIC_PAIR_BOX_SPHERE 1
 
 /* Joint i carries link i; joints are listed parents first.  A link may be massless as long as its joint moves mass (something outboard of it has mass).  All quantities are LOCAL (constant), as a reader of
  * model.sdf derives them once at q = 0 (mh_io_load_sdf, moby_amd/host/mh_io.cpp):
@@ -155,6 +157,37 @@ typedef struct mh_artic_model {
   int    pair_a[MH_ARTIC_MAX_PAIRS];               /* indices into the sphere list; a is the reference's geometry A */
   int    pair_b[MH_ARTIC_MAX_PAIRS];               /*   (the normal points from b to a) */
   int    sphere_no_plane;                          /* bit s set: sphere s does not meet the plane; 0 = every sphere does */
+  /* Box-sphere contacts between links and static boxes (appended: every field above keeps its offset; a zeroed pair_kind is the model above).
+   * A pair of kind MH_ARTIC_PAIR_BOX_SPHERE names a box (pair_a: index into the BOX list) and a sphere (pair_b: index into the sphere list) on
+   * different links; the box is the reference's geometry A wherever the pair is read (CCD.inl:15,26 swaps the arguments so that it is).  npairs
+   * counts both kinds, at most MH_ARTIC_MAX_PAIRS together.  box_link = -1 is a STATIC box: box_center / box_R are its pose in the model frame; it
+   * never meets the plane (no plane contacts, no entry in the plane's conservative-advancement or stabiliser distance lists), must appear in at
+   * least one box-sphere pair, and stands for a disabled body: no Jacobian term, calc_max_dist = 0 (CCD.cpp:589-590).  A link box in a pair still
+   * meets the plane as before: there is no plane mask for boxes.  A sphere that appears only in box-sphere pairs may carry its sphere_no_plane bit.
+   * With c the sphere's centre in the box's frame, h the half lengths, R the radius, p = clamp(c, -h, h) (the fixed point of the reference's
+   * projected-gradient QP, BoxPrimitive.cpp:183-254), v = p - c:
+   *   contact          find_contacts_box_sphere (CCD.inl:1208-1259).  If any |p_i| < h_i or |v| < R (every face and edge region, and every
+   *                    penetration): dist = -min(min_i(h_i - |p_i|), R - |v|), the sphere point stays c + v; otherwise (a vertex region) the sphere
+   *                    point is c + v R / |v| and dist = the distance between the two points.  None if dist > TOL.  dist > 0: the point is the
+   *                    midpoint of the two points (over a face or an edge that is the box point itself), the normal their difference box - sphere
+   *                    normalised, or -- when that is no longer than NEAR_ZERO -- the sphere-frame vector to the box point, normalised: the unit
+   *                    vector from the sphere's centre to p.  dist <= 0: the sphere point and that unit vector.  A centre inside the box gives
+   *                    v = 0 and a NaN normal, as in the reference; there is no fallback.  One pair gives at most one contact; canonical order:
+   *                    spheres on the plane, boxes, then the pairs in index order, both kinds mixed.
+   *   signed distance  BoxPrimitive::calc_signed_dist (BoxPrimitive.cpp:256-276, 788-836), a DIFFERENT function: the closest-point distance of c
+   *                    (the negative interior depth when c is inside) minus R; sphere point = centre + v (R + min(dist, 0)) / |v|, the centre if
+   *                    |v| = 0.  Conservative advancement, the contact threshold test and the stabiliser read this one.
+   *   row, velocity    the two-term form of the sphere pairs: A = the box's link, B = the sphere's, A's term first; a static box has no term (the
+   *                    row is B's term with -dir, the constraint velocity minus B's point velocity).
+   *   conservative     the sphere rule: dist > NEAR_ZERO -> dist / max(0, calc_max_dist(linkA, -n0, rmaxA) + calc_max_dist(linkB, n0, rmaxB)), n0 from
+   *   advancement      the signed-distance function's two points, B to A; a static box's term is 0.0 and still added first; dist <= 0 as for sphere pairs.
+   *   stabiliser       one row per pair: dist >= NEAR_ZERO -> the synthetic contact at A's closest point with normal n0; otherwise the contact
+   *                    above with TOL = NEAR_ZERO; Cn_v = dist - |eps| - NEAR_ZERO.  cstab_eval appends the pairs' signed distances in index order.
+   * Box against box between links and a static sphere are not built.  Models with a box-sphere pair or a static box step through their own kernels
+   * (mh_artic_bsp.hip, mh_artic_bsp_pose.hip); mh_debug_set(14, 1) sends pair, box and sphere models through them too (batches created after it).
+   * mh_artic_batch_create refuses (MH_ERR_INVALID_ARG): an unknown kind, an index outside the list the kind names, a box-sphere pair whose box and
+   * sphere sit on one link, a pair listed twice, a static box in no pair, box_link < -1. */
+  int    pair_kind[MH_ARTIC_MAX_PAIRS];            /* MH_ARTIC_PAIR_SPHERES (0): pair_a, pair_b index the sphere list; MH_ARTIC_PAIR_BOX_SPHERE (1): pair_a the box list */
 } mh_artic_model;
 
 /* B worlds resident on the GPU: joint positions q and velocities qd (B x nj each) + mh_world_aux (rand() stream, time,

@@ -19,6 +19,7 @@ MH_JOINT_REVOLUTE, MH_JOINT_PRISMATIC = 0, 1
 MH_ARTIC_MAX_SPHERES = 4
 MH_ARTIC_MAX_BOXES = 8
 MH_ARTIC_MAX_PAIRS = 6
+MH_ARTIC_PAIR_SPHERES, MH_ARTIC_PAIR_BOX_SPHERE = 0, 1      # mh_artic_model.pair_kind
 _NJ = MH_ARTIC_MAX_JOINTS
 _NS = MH_ARTIC_MAX_SPHERES
 _NB = MH_ARTIC_MAX_BOXES
@@ -38,7 +39,8 @@ class mh_artic_model(ctypes.Structure):
                 ("cp_nk", ctypes.c_int), ("cstab_max_iterations", ctypes.c_int), ("cstab_eps", ctypes.c_double),
                 ("nboxes", ctypes.c_int), ("box_link", ctypes.c_int * _NB), ("box_center", (ctypes.c_double * 3) * _NB),
                 ("box_R", (ctypes.c_double * 9) * _NB), ("box_len", (ctypes.c_double * 3) * _NB),
-                ("npairs", ctypes.c_int), ("pair_a", ctypes.c_int * _NP), ("pair_b", ctypes.c_int * _NP), ("sphere_no_plane", ctypes.c_int)]
+                ("npairs", ctypes.c_int), ("pair_a", ctypes.c_int * _NP), ("pair_b", ctypes.c_int * _NP), ("sphere_no_plane", ctypes.c_int),
+                ("pair_kind", ctypes.c_int * _NP)]
 
 
 MH_ARTIC_CRB, MH_ARTIC_FSAB = 0, 1      # moby_hip_artic.h: RCArticulatedBody::algorithm_type
@@ -222,6 +224,8 @@ def add_boxes(model, boxes, plane_normal=(0.0, 0.0, 1.0), plane_point=(0.0, 0.0,
               compliance=0.0, nk=4):
     """Box primitives on links against the model's one static plane (include/moby_hip_artic.h, mh_artic_model.nboxes):
     boxes = [(link, centre in the link frame, R (the box's axes in the link frame, 3x3), (xlen, ylen, zlen) full edge lengths), ...].
+    link = -1 is a static box: centre and R are its pose in the model frame; it never meets the plane and must appear in a box-sphere pair
+    (add_box_sphere_pairs).
     The plane and the ContactParameters are those of add_spheres, shared with the spheres (one set per model: the last call sets the
     parameters; a plane that disagrees with one already set is refused).  Returns the model."""
     assert 0 < len(boxes) <= MH_ARTIC_MAX_BOXES
@@ -229,7 +233,7 @@ def add_boxes(model, boxes, plane_normal=(0.0, 0.0, 1.0), plane_point=(0.0, 0.0,
     model.nboxes = len(boxes)
     for i, (link, c, R, dims) in enumerate(boxes):
         R = np.asarray(R, dtype=float).reshape(3, 3)
-        assert 0 <= link < model.nj and all(d > 0 for d in dims)
+        assert -1 <= link < model.nj and all(d > 0 for d in dims)
         model.box_link[i] = int(link)
         for k in range(3):
             model.box_center[i][k] = float(c[k]); model.box_len[i][k] = float(dims[k])
@@ -247,12 +251,28 @@ def add_pairs(model, pairs, no_plane=()):
     assert len(pairs) <= MH_ARTIC_MAX_PAIRS
     model.npairs = len(pairs)
     for k, (a, b) in enumerate(pairs):
-        model.pair_a[k] = int(a); model.pair_b[k] = int(b)
+        model.pair_a[k] = int(a); model.pair_b[k] = int(b); model.pair_kind[k] = MH_ARTIC_PAIR_SPHERES
     mask = 0
     for s in no_plane:
         assert 0 <= int(s) < MH_ARTIC_MAX_SPHERES
         mask |= 1 << int(s)
     model.sphere_no_plane = mask
+    return model
+
+
+def add_box_sphere_pairs(model, pairs, no_plane=()):
+    """Box-sphere contacts between links (include/moby_hip_artic.h, mh_artic_model.pair_kind): pairs = [(box, sphere), ...] name a box of the
+    model's box list (add_boxes first; a static box has link -1) and a sphere of its sphere list on a different link.  The box is the reference's
+    geometry A.  APPENDS to the pairs already set (add_pairs before it); no_plane lists further spheres that do not meet the plane.
+    mh_artic_batch_create checks the rest.  Returns the model."""
+    assert model.npairs + len(pairs) <= MH_ARTIC_MAX_PAIRS
+    for box, sph in pairs:
+        k = model.npairs
+        model.pair_a[k] = int(box); model.pair_b[k] = int(sph); model.pair_kind[k] = MH_ARTIC_PAIR_BOX_SPHERE
+        model.npairs = k + 1
+    for s in no_plane:
+        assert 0 <= int(s) < MH_ARTIC_MAX_SPHERES
+        model.sphere_no_plane |= 1 << int(s)
     return model
 
 

@@ -17,6 +17,7 @@
 //   MobyHip::add_link_sphere(io.model, finger_link, centre_in_link_frame, 0.03);     // <Sphere> CollisionGeometry on a link
 //   MobyHip::add_link_box(io.model, foot_link, centre_in_link_frame, R_in_link_frame, lengths);   // <Box> CollisionGeometry on a link
 //   MobyHip::add_sphere_pair(io.model, 0, 1);                                        // spheres 0 and 1 (on different links) can collide
+//   MobyHip::add_box_sphere_pair(io.model, 0, 1);                                    // box 0 and sphere 1 (on different links; the box may be static: link -1)
 //   MobyHip::set_ground_plane(io.model, normal, point_on_plane, /*epsilon*/ 0.0, /*mu_coulomb*/ 100.0);
 // step() then runs TimeSteppingSimulator::step in full: conservative advancement, mini-steps, contact + limit rows in one LCP.
 //
@@ -60,6 +61,18 @@ inline void add_sphere_pair(mh_artic_model& m, int a, int b, bool meets_plane_a 
   m.pair_a[k] = a; m.pair_b[k] = b;
   if (!meets_plane_a) m.sphere_no_plane |= 1 << a;
   if (!meets_plane_b) m.sphere_no_plane |= 1 << b;
+}
+// A box-sphere contact between links: box `box` of the model's box list (add_link_box first; link -1 = a static box whose centre and R are given
+// in the model frame) and sphere `sphere` of its sphere list, on different links; the box is the reference's geometry A
+// (include/moby_hip_artic.h, mh_artic_model.pair_kind).  The pair shares the ContactParameters of set_ground_plane.  sphere_meets_plane = false
+// takes the sphere off the plane.
+inline void add_box_sphere_pair(mh_artic_model& m, int box, int sphere, bool sphere_meets_plane = true)
+{
+  if (m.npairs >= MH_ARTIC_MAX_PAIRS) throw std::runtime_error("MobyHip::add_box_sphere_pair: more than MH_ARTIC_MAX_PAIRS pairs");
+  if (box < 0 || box >= m.nboxes || sphere < 0 || sphere >= m.nspheres) throw std::runtime_error("MobyHip::add_box_sphere_pair: a box of the box list and a sphere of the sphere list");
+  const int k = m.npairs++;
+  m.pair_a[k] = box; m.pair_b[k] = sphere; m.pair_kind[k] = MH_ARTIC_PAIR_BOX_SPHERE;
+  if (!sphere_meets_plane) m.sphere_no_plane |= 1 << sphere;
 }
 // The static PlanePrimitive (its +Y axis is the normal, PlanePrimitive.cpp) through `point`, and the ContactParameters of the
 // (robot, plane) pair; simulator constants at the reference's defaults (TimeSteppingSimulator.cpp:48, ConstraintSimulator.cpp:56)

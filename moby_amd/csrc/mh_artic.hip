@@ -38,6 +38,8 @@ struct Pairs {            // mh_artic_model's pair block (mh_artic_batch_create 
   int n;
   int a[MH_ARTIC_MAX_PAIRS], b[MH_ARTIC_MAX_PAIRS];
   int no_plane;           // mh_artic_model.sphere_no_plane
+  int kind[MH_ARTIC_MAX_PAIRS];   // mh_artic_model.pair_kind (behind what the pair kernels read: only the box-sphere kernels of mh_artic_bsp.hip look at it)
+  int nstatic;            // boxes with link -1
 };
 struct Model {            // mh_artic_model + what the kernel wants precomputed: ancestor masks
   // anc, fcos and fsin sit where they sat before the box block was appended to mh_artic_model -- over that block, which is therefore NOT valid
@@ -1036,6 +1038,8 @@ struct mh_artic_batch {
   int device;                // the HIP device the batch lives on (current at create); every entry point runs there (MH_ON_DEVICE)
   int B, nj, nspheres, cstab, algorithm;
   int nboxes;                // box primitives: the step goes through the box kernels (mh_artic_box.hip), as it does for spheres under mh_debug_set(12, 1)
+  int use_bsp;               // a box-sphere pair or a static box: the step goes through the box-sphere kernels (mh_artic_bsp.hip), as it does for every
+                             // model with geometry created under mh_debug_set(14, 1); use_pair is set with it (the workspace layout is the pair kernels')
   int use_pair;              // sphere pairs between links or a plane mask: the step goes through the pair kernels (mh_artic_pair.hip), as it does for
                              // every model with geometry created under mh_debug_set(13, 1)
   mh::artic::Model* d_model;
@@ -1062,6 +1066,9 @@ int artic_box_pose_launch(mh_artic_batch* ab, void* stream, double dt, int nstep
 int artic_pair_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
 int artic_pair_pose_launch(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
 size_t artic_pair_lds_bytes(int nj);
+// the box-sphere kernels (mh_artic_bsp.hip / mh_artic_bsp_pose.hip): artic_box_step hands a batch with use_bsp on to them; their LDS image is the pair kernels'
+int artic_bsp_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+int artic_bsp_pose_launch(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
 static inline bool artic_uses_box(const mh_artic_batch* ab) { return ab->use_pair != 0 || ab->nboxes > 0 || (ab->nspheres > 0 && mh_g_debug_artic_box != 0); }
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
@@ -1133,7 +1140,7 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   }
   if (model->nboxes < 0 || model->nboxes > MH_ARTIC_MAX_BOXES) return fail(MH_ERR_INVALID_ARG, "nboxes = %d outside [0, %d]", model->nboxes, MH_ARTIC_MAX_BOXES);
   for (int k = 0; k < model->nboxes; k++) {
-    if (model->box_link[k] < 0 || model->box_link[k] >= nj) return fail(MH_ERR_INVALID_ARG, "box %d: link %d outside [0, %d)", k, model->box_link[k], nj);
+    if (model->box_link[k] < -1 || model->box_link[k] >= nj) return fail(MH_ERR_INVALID_ARG, "box %d: link %d outside [-1, %d) (-1 = a static box)", k, model->box_link[k], nj);
     for (int c = 0; c < 3; c++) if (!(model->box_len[k][c] > 0.0) || !std::isfinite(model->box_len[k][c])) return fail(MH_ERR_INVALID_ARG, "box %d: edge lengths must be finite and > 0", k);
     const double* Rb = model->box_R[k];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {       // R R' = I
@@ -1145,21 +1152,43 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
     for (int c = 0; c < 9; c++) hm.bx.R[k][c] = Rb[c];
   }
   hm.bx.n = model->nboxes;
+  int nstatic = 0;
+  for (int k = 0; k < model->nboxes; k++) if (model->box_link[k] < 0) nstatic++;
   // sphere pairs between links
   if (model->npairs < 0 || model->npairs > MH_ARTIC_MAX_PAIRS) return fail(MH_ERR_INVALID_ARG, "npairs = %d outside [0, %d]", model->npairs, MH_ARTIC_MAX_PAIRS);
   for (int k = 0; k < model->npairs; k++) {
-    const int a = model->pair_a[k], b = model->pair_b[k];
+    const int a = model->pair_a[k], b = model->pair_b[k], kind = model->pair_kind[k];
+    if (kind != MH_ARTIC_PAIR_SPHERES && kind != MH_ARTIC_PAIR_BOX_SPHERE) return fail(MH_ERR_INVALID_ARG, "pair %d: kind %d is not built (0 = two spheres, 1 = a box and a sphere)", k, kind);
+    hm.pr.kind[k] = kind;
+    if (kind == MH_ARTIC_PAIR_BOX_SPHERE) {
+      if (a < 0 || a >= model->nboxes) return fail(MH_ERR_INVALID_ARG, "pair %d: box %d outside the box list [0, %d)", k, a, model->nboxes);
+      if (b < 0 || b >= model->nspheres) return fail(MH_ERR_INVALID_ARG, "pair %d: sphere %d outside the sphere list [0, %d)", k, b, model->nspheres);
+      if (model->box_link[a] == model->sphere_link[b]) return fail(MH_ERR_INVALID_ARG, "pair %d: box %d and sphere %d sit on the same link %d", k, a, b, model->box_link[a]);
+      for (int k2 = 0; k2 < k; k2++)
+        if (model->pair_kind[k2] == kind && model->pair_a[k2] == a && model->pair_b[k2] == b) return fail(MH_ERR_INVALID_ARG, "pair %d: box %d and sphere %d are pair %d already", k, a, b, k2);
+      hm.pr.a[k] = a; hm.pr.b[k] = b;
+      continue;
+    }
     if (a < 0 || a >= model->nspheres || b < 0 || b >= model->nspheres) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) outside the sphere list [0, %d)", k, a, b, model->nspheres);
     if (a == b) return fail(MH_ERR_INVALID_ARG, "pair %d: sphere %d against itself", k, a);
     if (model->sphere_link[a] == model->sphere_link[b]) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres %d and %d sit on the same link %d", k, a, b, model->sphere_link[a]);
     for (int k2 = 0; k2 < k; k2++)
-      if ((model->pair_a[k2] == a && model->pair_b[k2] == b) || (model->pair_a[k2] == b && model->pair_b[k2] == a)) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) are pair %d already", k, a, b, k2);
+      if (model->pair_kind[k2] == kind && ((model->pair_a[k2] == a && model->pair_b[k2] == b) || (model->pair_a[k2] == b && model->pair_b[k2] == a))) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) are pair %d already", k, a, b, k2);
     hm.pr.a[k] = a; hm.pr.b[k] = b;
   }
   if (model->sphere_no_plane < 0 || (model->sphere_no_plane >> model->nspheres) != 0) return fail(MH_ERR_INVALID_ARG, "sphere_no_plane = 0x%x has bits beyond the %d spheres", (unsigned)model->sphere_no_plane, model->nspheres);
-  hm.pr.n = model->npairs; hm.pr.no_plane = model->sphere_no_plane;
+  hm.pr.n = model->npairs; hm.pr.no_plane = model->sphere_no_plane; hm.pr.nstatic = nstatic;
+  bool has_bsp = false;
+  for (int k = 0; k < model->nboxes; k++) {
+    if (model->box_link[k] >= 0) continue;
+    bool paired = false;
+    for (int k2 = 0; k2 < model->npairs; k2++) paired = paired || (model->pair_kind[k2] == MH_ARTIC_PAIR_BOX_SPHERE && model->pair_a[k2] == k);
+    if (!paired) return fail(MH_ERR_INVALID_ARG, "box %d is static (link -1) and appears in no box-sphere pair", k);
+  }
+  for (int k = 0; k < model->npairs; k++) has_bsp = has_bsp || model->pair_kind[k] == MH_ARTIC_PAIR_BOX_SPHERE;
   const bool has_geom = model->nspheres > 0 || model->nboxes > 0;
-  const bool use_pair = model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
+  const bool use_bsp = has_bsp || nstatic > 0 || (has_geom && mh_g_debug_artic_bsp != 0);
+  const bool use_pair = use_bsp || model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
   if (use_pair && artic_pair_lds_bytes(nj) > 65536) return fail(MH_ERR_INVALID_ARG, "the pair kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, artic_pair_lds_bytes(nj));
   if (model->cstab_max_iterations < 0) return fail(MH_ERR_INVALID_ARG, "cstab_max_iterations = %d < 0", model->cstab_max_iterations);
   if (model->nspheres > 0 || model->nboxes > 0) {
@@ -1190,7 +1219,7 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   }
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
-  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->nboxes = model->nboxes; ab->use_pair = use_pair ? 1 : 0; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->nboxes = model->nboxes; ab->use_pair = use_pair ? 1 : 0; ab->use_bsp = use_bsp ? 1 : 0; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;

@@ -26,6 +26,7 @@ static int init_pow10()
 int artic_box_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D)
 {
   namespace ar = mh::artic;
+  if (ab->use_bsp) return artic_bsp_step(ab, stream, dt, nsteps, D);     // a box-sphere pair, a static box, or a batch created under mh_debug_set(14, 1)
   if (ab->use_pair) return artic_pair_step(ab, stream, dt, nsteps, D);   // sphere pairs, a plane mask, or a batch created under mh_debug_set(13, 1)
   if (ab->d_ws && ab->ws_stride < ar::WS_BOX)                  // a sphere batch created before mh_debug_set(12, 1): its workspace has the sphere kernels' layout
     return fail(MH_ERR_INVALID_ARG, "mh_debug_set(12, 1) applies to batches created after it (their workspace is sized for the box kernels at create)");

@@ -14,7 +14,8 @@
 // under divergent control flow.
 
 #ifdef MH_ARTIC_PAIR_TU
-// the pair kernels (mh_artic_pair.hip): the box kernels' sizes with room for the sphere pairs between links in the contact list
+// the pair kernels (mh_artic_pair.hip): the box kernels' sizes with room for the sphere pairs between links in the contact list.  The box-sphere
+// kernels (mh_artic_bsp.hip, MH_ARTIC_BSP_TU on top of the two switches) keep these sizes: a pair slot holds a pair of either kind
 constexpr int NS = MH_NOSLIP_MAX;
 constexpr int NCL = MH_ARTIC_MAX_SPHERES + 8 * MH_ARTIC_MAX_BOXES + MH_ARTIC_MAX_PAIRS;
 #elif defined(MH_ARTIC_BOX_TU)
@@ -73,6 +74,12 @@ constexpr int I_IDX = 0, I_LINK = 16, I_LINKB = I_LINK + NCL, I_SX = I_LINKB + N
 #define MH_BASE_ARG(M_, link_) , ((M_).anc[link_] & 1u) != 0u
 #define MH_ON_BASE && on_base
 #define MH_SKIP_MASKED(M_, s_) if (((M_).pr.no_plane >> (s_)) & 1) continue;
+#ifdef MH_ARTIC_BSP_TU
+// the box-sphere kernels (mh_artic_bsp.hip): a static box (link -1) has no plane work
+#define MH_SKIP_STATIC(M_, k_) if ((M_).bx.link[k_] < 0) continue;
+#else
+#define MH_SKIP_STATIC(M_, k_)
+#endif
 #else
 constexpr int I_IDX = 0, I_LINK = 16, I_SX = I_LINK + NCL, I_TX = I_SX + NS, I_NS = I_TX + NS, I_NT = I_NS + 1;
 #define MH_SET_LINKB(i, v)
@@ -80,6 +87,7 @@ constexpr int I_IDX = 0, I_LINK = 16, I_SX = I_LINK + NCL, I_TX = I_SX + NS, I_N
 #define MH_BASE_ARG(M_, link_)
 #define MH_ON_BASE
 #define MH_SKIP_MASKED(M_, s_)
+#define MH_SKIP_STATIC(M_, k_)
 #endif
 // the per-world HBM workspace: _MM and the Lemke LU workspace of the Drumwright-Shell / stabiliser LCP (2 x 64 x 64); the box kernels' stabiliser
 // adds Cn and Cn X for up to 64 contacts and the distances of the whole contact list behind them
@@ -333,6 +341,9 @@ MH_DEV bool pair_contact(const Model& M, const Lay& Y, const double* g, int k, d
 }
 // the constraint velocity of a contact between links la and lb (lb < 0: the plane): A's point velocity along d minus B's
 MH_DEV double pair_vel(const LayC& Z, const double* g, int la, int lb, const double* p, const double* d) {
+#ifdef MH_ARTIC_BSP_TU
+  if (la < 0) return -point_vel_dir(g + Z.V + 6 * lb, p, d);        // A is a static box: no term of its own
+#endif
   double v = point_vel_dir(g + Z.V + 6 * la, p, d);
   if (lb >= 0) v = v - point_vel_dir(g + Z.V + 6 * lb, p, d);
   return v;
@@ -380,7 +391,11 @@ MH_DEV double row_term(const mh_artic_model& m, const Lay& Y, const double* g, i
 // entry j of the row of a contact between links la and lb (lb < 0: the plane) at p along dir: A's term with dir plus B's with -dir, A's first;
 // a joint that is an ancestor of only one link gets that term alone, of neither 0.0 (ICH:1817-1895)
 MH_DEV double contact_row(const Model& M, const Lay& Y, const double* g, int la, int lb, int j, const double* p, const double* dir) {
+#ifdef MH_ARTIC_BSP_TU
+  const bool inA = la >= 0 && ((M.anc[la] >> j) & 1u) != 0u, inB = lb >= 0 && ((M.anc[lb] >> j) & 1u) != 0u;   // (a static box: B's term alone)
+#else
   const bool inA = ((M.anc[la] >> j) & 1u) != 0u, inB = lb >= 0 && ((M.anc[lb] >> j) & 1u) != 0u;
+#endif
   double val = 0.0;
   if (inA) val = row_term(M.m, Y, g, la, j, p, dir);
   if (inB) {
@@ -389,6 +404,117 @@ MH_DEV double contact_row(const Model& M, const Lay& Y, const double* g, int la,
     val = inA ? val + tb : tb;
   }
   return val;
+}
+#endif
+
+#ifdef MH_ARTIC_BSP_TU
+// ---- box-sphere pairs between links and static boxes (mh_artic_model.pair_kind; M.pr.kind[k] != 0: M.pr.a[k] indexes the box list, M.pr.b[k]
+// the sphere list; the box is the reference's geometry A).  Every lane computes the same numbers.  Operation order =
+// tests/native/artic_boxsphere_ref.cpp. ----
+// box b's pose in the model frame; a static box's is constant and read from the model
+MH_DEV void box_pose(const Model& M, const Lay& Y, const double* g, int b, double Rbg[9], double cb[3]) {
+  const Boxes& X = M.bx; const int l = X.link[b];
+  if (l < 0) { for (int c = 0; c < 9; c++) Rbg[c] = X.R[b][c]; for (int c = 0; c < 3; c++) cb[c] = X.center[b][c]; return; }
+  mat3mul(g + Y.R + 9 * l, X.R[b], Rbg);
+  double rc[3]; mat3vec(g + Y.R + 9 * l, X.center[b], rc);
+  for (int c = 0; c < 3; c++) cb[c] = g[Y.x + 3 * l + c] + rc[c];
+}
+// the sphere's centre cS (model frame), the same point c in the box's frame, the half lengths h
+MH_DEV void bsp_frame(const Model& M, const Lay& Y, const double* g, int k, double Rbg[9], double cb[3], double cS[3], double c[3], double h[3]) {
+  const int b = M.pr.a[k];
+  box_pose(M, Y, g, b, Rbg, cb); sphere_centre(M.m, Y, g, M.pr.b[k], cS);
+  const double d[3] = { cS[0] - cb[0], cS[1] - cb[1], cS[2] - cb[2] };
+  c[0] = (Rbg[0]*d[0] + Rbg[3]*d[1]) + Rbg[6]*d[2]; c[1] = (Rbg[1]*d[0] + Rbg[4]*d[1]) + Rbg[7]*d[2]; c[2] = (Rbg[2]*d[0] + Rbg[5]*d[1]) + Rbg[8]*d[2];
+  for (int i = 0; i < 3; i++) h[i] = M.bx.len[b][i] * 0.5;
+}
+// BoxPrimitive::calc_closest_points (BoxPrimitive.cpp:183-254; the QP's fixed point is the clamp) + find_contacts_box_sphere (CCD.inl:1208-1259)
+MH_DEV bool bsp_contact(const Model& M, const Lay& Y, const double* g, int k, double TOL, double pt[3], double n[3], double& dist) {
+  double Rbg[9], cb[3], cS[3], c[3], h[3]; bsp_frame(M, Y, g, k, Rbg, cb, cS, c, h);
+  const double Rs = M.m.sphere_radius[M.pr.b[k]];
+  double p[3], u[3];
+  for (int i = 0; i < 3; i++) { p[i] = (c[i] < -h[i]) ? -h[i] : ((c[i] > h[i]) ? h[i] : c[i]); u[i] = p[i] - c[i]; }
+  const double nrm = sqrt((u[0]*u[0] + u[1]*u[1]) + u[2]*u[2]);
+  if (fabs(p[0]) < h[0] || fabs(p[1]) < h[1] || fabs(p[2]) < h[2] || nrm < Rs) {     // an OR: every face and edge region, and every penetration
+    const double b1 = h[1] - fabs(p[1]), b2 = h[2] - fabs(p[2]);
+    const double b12 = (b2 < b1) ? b2 : b1, b0 = h[0] - fabs(p[0]);
+    const double bd = (b12 < b0) ? b12 : b0;
+    const double rn = Rs - nrm;
+    dist = -((rn < bd) ? rn : bd);
+  } else {                                                                             // a vertex region: the sphere point goes to the surface
+    const double sc = Rs / nrm;
+    for (int i = 0; i < 3; i++) u[i] = u[i] * sc;
+    const double e[3] = { (c[0] + u[0]) - p[0], (c[1] + u[1]) - p[1], (c[2] + u[2]) - p[2] };
+    dist = sqrt((e[0]*e[0] + e[1]*e[1]) + e[2]*e[2]);
+  }
+  if (dist > TOL) return false;
+  double ug[3], pr[3]; mat3vec(Rbg, u, ug); mat3vec(Rbg, p, pr);
+  const double sg[3] = { cS[0] + ug[0], cS[1] + ug[1], cS[2] + ug[2] };
+  const double ulen = sqrt((ug[0]*ug[0] + ug[1]*ug[1]) + ug[2]*ug[2]);
+  bool own = false;
+  if (dist > 0.0) {
+    const double pg[3] = { cb[0] + pr[0], cb[1] + pr[1], cb[2] + pr[2] };
+    const double nd[3] = { pg[0] - sg[0], pg[1] - sg[1], pg[2] - sg[2] };
+    const double nl = sqrt((nd[0]*nd[0] + nd[1]*nd[1]) + nd[2]*nd[2]);
+    for (int i = 0; i < 3; i++) pt[i] = (sg[i] + pg[i]) * 0.5;
+    if (nl > NEAR_ZERO_) { for (int i = 0; i < 3; i++) n[i] = nd[i] / nl; own = true; }
+  } else for (int i = 0; i < 3; i++) pt[i] = sg[i];
+  if (!own) for (int i = 0; i < 3; i++) n[i] = ug[i] / ulen;      // (a centre inside the box: 0 / 0, as in the reference)
+  return true;
+}
+// BoxPrimitive::calc_signed_dist for a sphere (BoxPrimitive.cpp:256-276, 788-836): pA the box point, pB the sphere point, model frame
+MH_DEV double bsp_sdist(const Model& M, const Lay& Y, const double* g, int k, double pA[3], double pB[3]) {
+  double Rbg[9], cb[3], cS[3], c[3], h[3]; bsp_frame(M, Y, g, k, Rbg, cb, cS, c, h);
+  const double Rs = M.m.sphere_radius[M.pr.b[k]];
+  double cl[3] = { c[0], c[1], c[2] };
+  bool inside = true; double sq = 0.0, in = -A_INF_;
+  for (int i = 0; i < 3; i++) {
+    if (c[i] < -h[i]) { const double dl = c[i] + h[i]; cl[i] = -h[i]; sq = sq + dl * dl; inside = false; }
+    else if (c[i] > h[i]) { const double dl = c[i] - h[i]; cl[i] = h[i]; sq = sq + dl * dl; inside = false; }
+    else if (inside) { const double f1 = fabs(h[i] - c[i]), f2 = fabs(c[i] + h[i]); const double dd = -((f2 < f1) ? f2 : f1); in = (in < dd) ? dd : in; }
+  }
+  const double dist = (inside ? in : sqrt(sq)) - Rs;
+  const double v[3] = { cl[0] - c[0], cl[1] - c[1], cl[2] - c[2] };
+  const double vn = sqrt((v[0]*v[0] + v[1]*v[1]) + v[2]*v[2]);
+  double pr[3]; mat3vec(Rbg, cl, pr);
+  for (int i = 0; i < 3; i++) pA[i] = cb[i] + pr[i];
+  if (vn == 0.0) { for (int i = 0; i < 3; i++) pB[i] = cS[i]; }
+  else {
+    double vg[3]; mat3vec(Rbg, v, vg);
+    const double sc = (Rs + ((0.0 < dist) ? 0.0 : dist)) / vn;
+    for (int i = 0; i < 3; i++) pB[i] = cS[i] + vg[i] * sc;
+  }
+  return dist;
+}
+// pair k's signed distance, either kind
+MH_DEV double any_dist(const Model& M, const Lay& Y, const double* g, int k) {
+  double a[3], b[3], n[3];
+  return M.pr.kind[k] ? bsp_sdist(M, Y, g, k, a, b) : pair_dist(M, Y, g, k, a, b, n);
+}
+// the sphere rule of conservative advancement for a box-sphere pair (CCD.cpp:138-235); a static box is a disabled body: calc_max_dist = 0 (CCD.cpp:589-590)
+MH_DEV double CA_bsp(const Model& M, const Lay& Y, const LayC& Z, const double* g, int k) {
+  const mh_artic_model& m = M.m;
+  const int bx = M.pr.a[k], sb = M.pr.b[k], la = M.bx.link[bx], lb = m.sphere_link[sb];
+  double pA[3], pB[3], p[3], nn[3], d2;
+  const double dist = bsp_sdist(M, Y, g, k, pA, pB);
+  if (!(dist > NEAR_ZERO_)) {
+    const bool has = bsp_contact(M, Y, g, k, NEAR_ZERO_, p, nn, d2);
+    if (has && fabs(pair_vel(Z, g, la, lb, p, nn)) < NEAR_ZERO_ * 10) return A_INF_;
+  }
+  if (dist <= 0.0) {
+    if (!bsp_contact(M, Y, g, k, NEAR_ZERO_, p, nn, d2)) return A_INF_;
+    if (pair_vel(Z, g, la, lb, p, nn) < -NEAR_ZERO_) return 0.0;
+    return A_INF_;
+  }
+  const double d0[3] = { pA[0] - pB[0], pA[1] - pB[1], pA[2] - pB[2] };
+  const double len = sqrt((d0[0]*d0[0] + d0[1]*d0[1]) + d0[2]*d0[2]);
+  const double n[3] = { d0[0] / len, d0[1] / len, d0[2] / len };
+  const double mn[3] = { -n[0], -n[1], -n[2] };
+  const double tA = (la >= 0) ? calc_max_dist(m, Y, g, la, mn, rmax_box(M, bx), (M.anc[la] & 1u) != 0u) : 0.0;
+  const double tB = calc_max_dist(m, Y, g, lb, n, rmax_of(m, sb), (M.anc[lb] & 1u) != 0u);
+  double total = tA + tB;
+  if (total < 0.0) total = 0.0;
+  const double cand = dist / total;
+  return (cand < A_INF_) ? cand : A_INF_;
 }
 #endif
 
@@ -835,9 +961,11 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
     double CA = A_INF_;
     for (int s = 0; s < m.nspheres; s++) { MH_SKIP_MASKED(M, s) const double e = CA_step(m, Y, Z, g, s MH_BASE_ARG(M, m.sphere_link[s])); CA = (e < CA) ? e : CA; }
 #ifdef MH_ARTIC_BOX_TU
-    for (int k = 0; k < M.bx.n; k++) { const double e = CA_box(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
+    for (int k = 0; k < M.bx.n; k++) { MH_SKIP_STATIC(M, k) const double e = CA_box(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
 #endif
-#ifdef MH_ARTIC_PAIR_TU
+#ifdef MH_ARTIC_BSP_TU
+    for (int k = 0; k < M.pr.n; k++) { const double e = M.pr.kind[k] ? CA_bsp(M, Y, Z, g, k) : CA_pair(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
+#elif defined(MH_ARTIC_PAIR_TU)
     for (int k = 0; k < M.pr.n; k++) { const double e = CA_pair(M, Y, Z, g, k); CA = (e < CA) ? e : CA; }
 #endif
     CA = uni(CA);
@@ -886,6 +1014,7 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_BOX_TU
   for (int k = 0; k < M.bx.n; k++) {                               // find_contacts_plane_generic: a contact at every vertex within the threshold
     double pa[3], pp[3];
+    MH_SKIP_STATIC(M, k)
     if (!(box_dist(M, Y, g, k, pa, pp) < m.contact_dist_thresh)) continue;
     for (int i = 0; i < 8; i++) {
       double v[3], q[3]; box_vertex(M, Y, g, k, i, v); to_plane(m, v, q);
@@ -904,12 +1033,21 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_PAIR_TU
   for (int k = 0; k < M.pr.n; k++) {                               // find_contacts_sphere_sphere: at most one contact per pair
     double p[3], n[3], dist;
+#ifdef MH_ARTIC_BSP_TU
+    const bool bsp = M.pr.kind[k] != 0;                            // find_contacts_box_sphere behind the signed-distance test (pdi.dist)
+    if (bsp) { if (!(any_dist(M, Y, g, k) < m.contact_dist_thresh) || !bsp_contact(M, Y, g, k, m.contact_dist_thresh, p, n, dist)) continue; }
+    else
+#endif
     if (!pair_contact(M, Y, g, k, m.contact_dist_thresh, p, n, dist) || !(dist < m.contact_dist_thresh)) continue;
     if (lane == 0) {
       double* c = g + Z.cp + 12 * nc;
       double sv[3], tv[3]; orthonormal_basis(n, sv, tv);
       for (int c2 = 0; c2 < 3; c2++) { c[c2] = p[c2]; c[3 + c2] = n[c2]; c[6 + c2] = sv[c2]; c[9 + c2] = tv[c2]; }
+#ifdef MH_ARTIC_BSP_TU
+      ints[I_LINK + nc] = bsp ? M.bx.link[M.pr.a[k]] : m.sphere_link[M.pr.a[k]];
+#else
       ints[I_LINK + nc] = m.sphere_link[M.pr.a[k]];
+#endif
       ints[I_LINKB + nc] = m.sphere_link[M.pr.b[k]];
     }
     nc++;
@@ -943,7 +1081,11 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
   // the boxes' distances follow the spheres' in uC; up to NCL contacts: their distances and Cn / Cn X live in the HBM workspace behind the LCP
 #ifdef MH_ARTIC_PAIR_TU
   // ... and the pairs' follow the boxes'; a sphere masked off the plane has no entry
+#ifdef MH_ARTIC_BSP_TU
+  const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres, ngeo = (nsph - popc((uint64_t)(unsigned)M.pr.no_plane)) + (M.bx.n - M.pr.nstatic) + M.pr.n;   // (a static box has no entry)
+#else
   const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres, ngeo = (nsph - popc((uint64_t)(unsigned)M.pr.no_plane)) + M.bx.n + M.pr.n;
+#endif
 #else
   const int nj = Y.nj, lane = lane_id(), nsph = m.nspheres, ngeo = nsph + M.bx.n;
 #endif
@@ -969,8 +1111,12 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
 #ifdef MH_ARTIC_PAIR_TU
     int o = 0;
     for (int s2 = 0; s2 < nsph; s2++) { MH_SKIP_MASKED(M, s2) double cp[3]; sphere_in_plane(m, Y, g, s2, cp); const double d = cp[1] + (-1.0 * m.sphere_radius[s2]); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
-    for (int k = 0; k < M.bx.n; k++) { double pa[3], pp[3]; const double d = box_dist(M, Y, g, k, pa, pp); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+    for (int k = 0; k < M.bx.n; k++) { MH_SKIP_STATIC(M, k) double pa[3], pp[3]; const double d = box_dist(M, Y, g, k, pa, pp); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+#ifdef MH_ARTIC_BSP_TU
+    for (int k = 0; k < M.pr.n; k++) { const double d = any_dist(M, Y, g, k); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+#else
     for (int k = 0; k < M.pr.n; k++) { double cA[3], cB[3], n[3]; const double d = pair_dist(M, Y, g, k, cA, cB, n); if (lane == 0) out[o] = d; o++; vio = (d < vio) ? d : vio; }
+#endif
     const double q0 = g[Y.q];
     const double a = (hi0 - q0) - 0.0, b2 = (q0 + 0.0) - lo0;
     if (lane < nj) { out[ngeo + 2 * lane] = a; out[ngeo + 2 * lane + 1] = b2; }
@@ -1027,6 +1173,7 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
 #ifdef MH_ARTIC_BOX_TU
     for (int k = 0; k < M.bx.n; k++) {                             // CStab:306-345 for (box, plane): one synthetic contact, or the vertices within NEAR_ZERO
       double pa[3], pp[3];
+      MH_SKIP_STATIC(M, k)
       const double low = box_dist(M, Y, g, k, pa, pp);
       if (low >= NEAR_ZERO_) {
         double pb[3]; from_plane(m, pp[0], 0.0, pp[2], pb);
@@ -1047,6 +1194,23 @@ __device__ __noinline__ void stabilize_contacts(const Model& M, const Lay& Y, co
 #ifdef MH_ARTIC_PAIR_TU
     for (int k = 0; k < M.pr.n; k++) {                             // CStab:306-345 for a sphere pair: the synthetic contact on A's surface, or find_contacts'
       double cA[3], cB[3], n[3], p[3];
+#ifdef MH_ARTIC_BSP_TU
+      if (M.pr.kind[k]) {                                          // ... for a box-sphere pair: A's closest point of the signed-distance function, normal B to A
+        double low = bsp_sdist(M, Y, g, k, cA, cB);
+        bool have = true;
+        if (low >= NEAR_ZERO_) {
+          const double d[3] = { cA[0] - cB[0], cA[1] - cB[1], cA[2] - cB[2] };
+          const double len = sqrt((d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]);
+          for (int c2 = 0; c2 < 3; c2++) { p[c2] = cA[c2]; n[c2] = d[c2] / len; }
+        } else have = bsp_contact(M, Y, g, k, NEAR_ZERO_, p, n, low);   // (signed_violation = the contact's own distance)
+        if (have) {
+          if (lane == 0) { double* c = g + Z.cp + 12 * nc; for (int c2 = 0; c2 < 3; c2++) { c[c2] = p[c2]; c[3 + c2] = n[c2]; }
+                           ints[I_LINK + nc] = M.bx.link[M.pr.a[k]]; ints[I_LINKB + nc] = m.sphere_link[M.pr.b[k]]; dist[nc] = low; }
+          nc++;
+        }
+        continue;
+      }
+#endif
       const double low = pair_dist(M, Y, g, k, cA, cB, n);
       const double rA = m.sphere_radius[M.pr.a[k]], rB = m.sphere_radius[M.pr.b[k]];
       if (low >= NEAR_ZERO_) { for (int c2 = 0; c2 < 3; c2++) p[c2] = cA[c2] - n[c2] * rA; }
@@ -1315,7 +1479,35 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   }
 }
 
-#if defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_POSE_TU)
+#if defined(MH_ARTIC_BSP_TU) && !defined(MH_ARTIC_POSE_TU)
+// the box-sphere kernels (mh_artic_bsp.hip): {plain, stab} x {undriven, driven} in angle coordinates; one world per workgroup's LDS image as the box kernels
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                             mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
+#elif defined(MH_ARTIC_BSP_TU)
+// the same four in pose coordinates (mh_artic_bsp_pose.hip)
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
+__global__ __launch_bounds__(64)
+void k_artic_step_bsp_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
+                                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+#elif defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_POSE_TU)
 // the pair kernels (mh_artic_pair.hip): {plain, stab} x {undriven, driven} in angle coordinates; one world per workgroup's LDS image as the box kernels
 __global__ __launch_bounds__(64)
 void k_artic_step_pair(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,

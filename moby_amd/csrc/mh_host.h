@@ -109,6 +109,7 @@ extern MH_HIDDEN int mh_g_debug_blk;
 extern MH_HIDDEN int mh_g_debug_fastgeom;
 extern MH_HIDDEN int mh_g_debug_artic_box;           // mh_debug_set(12, v): sphere-only articulated bodies through the box kernels (mh_artic_box.hip)
 extern MH_HIDDEN int mh_g_debug_artic_pair;          // mh_debug_set(13, v): articulated bodies with spheres or boxes through the pair kernels (mh_artic_pair.hip)
+extern MH_HIDDEN int mh_g_debug_artic_bsp;           // mh_debug_set(14, v): articulated bodies with spheres, boxes or pairs through the box-sphere kernels (mh_artic_bsp.hip)
 extern MH_HIDDEN int mh_g_debug_artic_pack;          // mh_debug_set(9, v): the articulated stepper with two worlds per wavefront (k_artic_step_p2)
 extern MH_HIDDEN int mh_g_debug_reglu;               // mh_debug_set(10, v): lcp_fast's register-resident dense LU (mh_lu_reg.inc)
 

@@ -956,7 +956,13 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
   std::vector<UrdfGeom> geoms;
   if (from_urdf) geoms = rob.geoms;
   else {
-    if (B0.has_cg && !floating) { UrdfGeom g; g.link = -1; g.id = base; g.sphere = false; g.radius = 0.0; g.center[0] = g.center[1] = g.center[2] = 0.0; geoms.push_back(g); }
+    if (B0.has_cg && !floating) {                                            // rides on the fixed base: static, its pose in the base (= model) frame
+      UrdfGeom g; g.link = -1; g.id = base; g.sphere = prims.count(B0.geom) && prims[B0.geom].type == MH_GEOM_SPHERE; g.radius = g.sphere ? prims[B0.geom].dim[0] : 0.0;
+      g.box = prims.count(B0.geom) && prims[B0.geom].type == MH_GEOM_BOX;
+      for (int k = 0; k < 3; k++) g.center[k] = (g.sphere || g.box) ? prims[B0.geom].o[k] : 0.0;
+      if (g.box) { for (int k = 0; k < 9; k++) g.R[k] = prims[B0.geom].R[k]; for (int k = 0; k < 3; k++) g.dims[k] = prims[B0.geom].dim[k]; }
+      geoms.push_back(g);
+    }
     // geometry that a FixedJoint welded onto model link `link` (frame: origin `org`, axes RT): the welded link's pose at q = 0 seen from there
     auto add_welded = [&](const XLink& T, int link, const double* org) {
       for (const XWeldGeom& w : T.wg) {
@@ -979,7 +985,7 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
       geoms.push_back(g);
     }
     if (floating) add_welded(B0, 5, B0.cx);
-    else for (const XWeldGeom& w : B0.wg) { UrdfGeom g; g.link = -1; g.id = w.id; g.sphere = false; g.radius = 0.0; g.center[0] = g.center[1] = g.center[2] = 0.0; geoms.push_back(g); }   // rides on the fixed base: static
+    else add_welded(B0, -1, B0.x);                                           // rides on the fixed base: static
     for (int i = nv; i < m.nj; i++) {
       const XLink& L = links[link_of[joints[order[i - nv]].out]];
       add_welded(L, i, joints[order[i - nv]].loc);
@@ -998,30 +1004,46 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
     }
   }
   // pairs of the body's own geometries that are not disabled (the whole body, or link by link): two spheres on different moving links become a
-  // sphere pair (mh_artic_model.npairs); anything else is refused -- geometries riding on one link cannot meet
+  // sphere pair, a Box and a Sphere on links of different roots a box-sphere pair (mh_artic_model.pair_kind) -- the Box may also ride on the
+  // fixed base (a static box, box_link = -1); a Box against a Sphere of its own chain and anything else is refused -- geometries riding on one link cannot meet
   std::vector<std::pair<size_t, size_t> > gpairs; std::vector<char> in_pair(geoms.size(), 0);
   if (!pair_disabled(abid, abid))
     for (size_t x = 0; x < geoms.size(); x++) for (size_t y = x + 1; y < geoms.size(); y++) {
       if (geoms[x].link == geoms[y].link || pair_disabled(geoms[x].id, geoms[y].id)) continue;
-      if (geoms[x].link < 0 || geoms[y].link < 0)
-        return fail("links %s and %s can collide: contact with geometry on the fixed base (a static obstacle) is not supported (add a <DisabledPair>)", geoms[x].id.c_str(), geoms[y].id.c_str());
-      if (!geoms[x].sphere || !geoms[y].sphere)
-        return fail("links %s and %s can collide: link-link contact is supported between two Spheres only, not for a Box or another primitive (add a <DisabledPair>)", geoms[x].id.c_str(), geoms[y].id.c_str());
-      gpairs.push_back(std::make_pair(x, y)); in_pair[x] = in_pair[y] = 1;
+      const UrdfGeom& gx = geoms[x]; const UrdfGeom& gy = geoms[y];
+      if (gx.box && gy.box)
+        return fail("links %s and %s can collide: box-box contact between links is not supported (add a <DisabledPair>)", gx.id.c_str(), gy.id.c_str());
+      if ((!gx.sphere && !gx.box) || (!gy.sphere && !gy.box))
+        return fail("links %s and %s can collide: link-link contact is supported between Spheres and between a Box and a Sphere only, not for another primitive (add a <DisabledPair>)", gx.id.c_str(), gy.id.c_str());
+      if ((gx.sphere && gx.link < 0) || (gy.sphere && gy.link < 0))
+        return fail("links %s and %s can collide: a static Sphere (a Sphere on the fixed base) is not supported, only a static Box (add a <DisabledPair>)", gx.id.c_str(), gy.id.c_str());
+      if ((gx.box || gy.box) && gx.link >= 0 && gy.link >= 0) {            // a Box and a Sphere of ONE chain (one link carries the other): not read as a pair
+        bool chain = false;
+        for (int l = gx.link; l >= 0; l = m.parent[l]) if (l == gy.link) chain = true;
+        for (int l = gy.link; l >= 0; l = m.parent[l]) if (l == gx.link) chain = true;
+        if (chain)
+          return fail("links %s and %s can collide: contact between two links of one chain (one carries the other) is supported between two Spheres only, not for a Box; "
+                      "a Box meets a Sphere on another root or from the fixed base (add a <DisabledPair>, or list the pair by hand: mh_artic_model.pair_kind)", gx.id.c_str(), gy.id.c_str());
+      }
+      if (gx.box) gpairs.push_back(std::make_pair(x, y)); else gpairs.push_back(std::make_pair(gy.box ? y : x, gy.box ? x : y));   // (the box first: geometry A)
+      in_pair[x] = in_pair[y] = 1;
     }
-  if (gpairs.size() > (size_t)MH_ARTIC_MAX_PAIRS) return fail("more than %d link-link sphere pairs (add <DisabledPair>s)", MH_ARTIC_MAX_PAIRS);
-  std::vector<int> sphere_of(geoms.size(), -1);
+  if (gpairs.size() > (size_t)MH_ARTIC_MAX_PAIRS) return fail("more than %d link-link pairs (add <DisabledPair>s)", MH_ARTIC_MAX_PAIRS);
+  std::vector<int> sphere_of(geoms.size(), -1), box_of(geoms.size(), -1);
   if (!plane_body.empty() || !gpairs.empty()) {
     for (size_t gi = 0; gi < geoms.size(); gi++) {
       const UrdfGeom& g = geoms[gi];
-      if (g.link < 0) continue;                                              // rides on the fixed base: static against the static plane
-      const bool meets = !plane_body.empty() && !(pair_disabled(g.id, plane_body) || pair_disabled(abid, plane_body));
+      if (g.link < 0 && !in_pair[gi]) continue;                              // rides on the fixed base: static against the static plane
+      const bool meets = g.link >= 0 && !plane_body.empty() && !(pair_disabled(g.id, plane_body) || pair_disabled(abid, plane_body));
       if (!meets && !in_pair[gi]) continue;
       if (g.box) {
         if (m.nboxes >= MH_ARTIC_MAX_BOXES) return fail("more than %d link boxes", MH_ARTIC_MAX_BOXES);
         if (!(g.dims[0] > 0.0 && g.dims[1] > 0.0 && g.dims[2] > 0.0)) return fail("link %s: a box needs three positive edge lengths", g.id.c_str());
+        if (!meets && g.link >= 0)
+          return fail("link %s: a Box in a box-sphere pair meets the plane too (there is no plane mask for boxes): the scene needs a plane and its pair with this link enabled", g.id.c_str());
         const int b = m.nboxes++;
-        m.box_link[b] = g.link;
+        box_of[gi] = b;
+        m.box_link[b] = g.link;                                              // (-1: a static box, its pose in the model frame)
         for (int k = 0; k < 3; k++) { m.box_center[b][k] = g.center[k]; m.box_len[b][k] = g.dims[k]; }
         for (int k = 0; k < 9; k++) m.box_R[b][k] = g.R[k];
         continue;
@@ -1034,7 +1056,11 @@ int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double*
       sphere_of[gi] = s;
       if (!meets) m.sphere_no_plane |= 1 << s;                               // in a pair only: its pair with the plane body is disabled, or there is no plane
     }
-    for (const auto& gp : gpairs) { const int k = m.npairs++; m.pair_a[k] = sphere_of[gp.first]; m.pair_b[k] = sphere_of[gp.second]; }
+    for (const auto& gp : gpairs) {
+      const int k = m.npairs++; const bool bsp = geoms[gp.first].box;
+      m.pair_kind[k] = bsp ? MH_ARTIC_PAIR_BOX_SPHERE : MH_ARTIC_PAIR_SPHERES;
+      m.pair_a[k] = bsp ? box_of[gp.first] : sphere_of[gp.first]; m.pair_b[k] = sphere_of[gp.second];
+    }
   }
   if (plane_body.empty() && !gpairs.empty()) {
     // no plane body: every sphere is masked off the plane; the plane frame only has to be a rotation, the parameters are the body's own pair's

@@ -1,0 +1,223 @@
+"""The box-sphere reference's ctypes face (tests/native/artic_boxsphere_ref.cpp) and the scenes shared by the CPU tests, the GPU tests, the fuzz
+tool and the bench of box-sphere contacts between links and static boxes."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+
+from moby_amd import artic as A
+
+from tests.artic_pair_ref import G, UP, _hinge, slider
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FACE, EDGE, VERTEX, INSIDE = 0, 1, 2, 3
+
+
+class BoxSphereRef:
+    """ctypes face of tests/native/artic_boxsphere_ref.cpp"""
+
+    def __init__(self, path):
+        self.lib = ctypes.CDLL(path)
+        self.lib.artic_boxsphere_ref_step.restype = None
+        self.lib.artic_pair_ref_step.restype = None
+        self.lib.artic_boxsphere_ref_regions.restype = None
+        for f in ("ca", "dist", "contact"):
+            getattr(self.lib, "artic_boxsphere_ref_" + f).restype = ctypes.c_int
+
+    def _step(self, fn, model, q, qd, aux, dt, nsteps, pose, drive):
+        keep = None
+        d = None
+        if drive is not None:
+            drive.check(q.shape[0], model.nj)
+            d = A.mh_artic_drive(terms=drive.terms, rows=drive.rows)
+            keep = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in drive.arrays.items() if a is not None}
+            for k, a in keep.items():
+                setattr(d, k, a.ctypes.data)
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        fn(ctypes.byref(model), int(q.shape[0]), ctypes.c_double(dt), int(nsteps), P(q), P(qd), P(aux),
+           None if pose is None else P(pose), None if d is None else ctypes.byref(d))
+        del keep
+
+    def step(self, model, q, qd, aux, dt, nsteps, pose=None, drive=None):
+        self._step(self.lib.artic_boxsphere_ref_step, model, q, qd, aux, dt, nsteps, pose, drive)
+
+    def pair_step(self, model, q, qd, aux, dt, nsteps, pose=None, drive=None):
+        """the pair reference (tests/native/artic_pair_ref.cpp, linked into the same library)"""
+        self._step(self.lib.artic_pair_ref_step, model, q, qd, aux, dt, nsteps, pose, drive)
+
+    def ca(self, model, q, qd):
+        """the conservative-advancement bounds of one state: unmasked spheres, link boxes, pairs"""
+        q = np.ascontiguousarray(q, dtype=np.float64).copy(); qd = np.ascontiguousarray(qd, dtype=np.float64).copy()
+        out = np.zeros(32)
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        n = self.lib.artic_boxsphere_ref_ca(ctypes.byref(model), P(q), P(qd), P(out))
+        return out[:n]
+
+    def contact(self, model, q, k, tol):
+        """pair k's contact at q through the reference's contact entry: (found, point, normal, distance, region)"""
+        q = np.ascontiguousarray(q, dtype=np.float64).copy(); z = np.zeros_like(q); out = np.zeros(8)
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        has = self.lib.artic_boxsphere_ref_contact(ctypes.byref(model), P(q), P(z), int(k), ctypes.c_double(tol), P(out))
+        return bool(has), out[0:3].copy(), out[3:6].copy(), float(out[6]), int(out[7])
+
+    def regions(self, model, q, pose=None):
+        """(region, signed distance) of every pair of every world of q (B x nj): two B x npairs arrays; region -1 for a sphere pair"""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        reg = np.zeros((B, max(model.npairs, 1)), dtype=np.int32); dist = np.zeros((B, max(model.npairs, 1)))
+        if model.npairs == 0:
+            return reg[:, :0], dist[:, :0]
+        reg = np.zeros((B, model.npairs), dtype=np.int32); dist = np.zeros((B, model.npairs))
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self.lib.artic_boxsphere_ref_regions(ctypes.byref(model), B, P(q), None if pose is None else P(np.ascontiguousarray(pose)), P(reg), P(dist))
+        return reg, dist
+
+
+def build_boxsphere_ref(tmpdir):
+    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
+    so = str(tmpdir / "libartic_boxsphere_ref.so")
+    nat = os.path.join(ROOT, "tests", "native")
+    srcs = ("artic_boxsphere_ref.cpp", "artic_pair_ref.cpp", "artic_box_ref.cpp", "artic_drive_ref.cpp", "artic_pose_ref.cpp")
+    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle")] + [os.path.join(nat, f) for f in srcs] + ["-o", so])
+    return BoxSphereRef(so)
+
+
+def track(ref, model, q, qd, dt, nsteps, pose=None):
+    """steps the reference one step at a time from (q, qd) and records, per world, the regions in which a box-sphere pair was within the contact
+    threshold of its box, and whether a sphere's centre was ever inside a box.  Returns (touched: B x 4 bool over FACE .. INSIDE, q, qd, aux)."""
+    from moby_amd import scene as S
+    B = q.shape[0]
+    q = q.copy(); qd = qd.copy(); aux = S.new_aux(B)
+    pose = None if pose is None else pose.copy()
+    touched = np.zeros((B, 4), dtype=bool)
+    kinds = np.array([model.pair_kind[k] for k in range(model.npairs)])
+    for _ in range(nsteps):
+        ref.step(model, q, qd, aux, dt, 1, pose=pose)
+        reg, dist = ref.regions(model, q, pose)
+        for k in np.nonzero(kinds == A.MH_ARTIC_PAIR_BOX_SPHERE)[0]:
+            near = dist[:, k] < 1e-4
+            for r in range(4):
+                touched[:, r] |= (near & (reg[:, k] == r)) if r != INSIDE else (reg[:, k] == INSIDE)
+    return touched, q, qd, aux, pose
+
+
+def aim(ref, m, sampler, B, seed, k=None, speed=(0.5, 2.0), gap=(0.004, 0.05), share=(0.6, 0.3, 0.1)):
+    """B initial states for model m, chosen with the reference: sampler(rng, N) draws N candidate q; a world is given a target region of
+    box-sphere pair k (default: the first one; face, edge, vertex in the shares given) and the first candidate whose sphere is over that region with a signed distance
+    inside `gap`, every box-sphere pair clear of its box; its qd is the sampler's small random velocity plus the joint velocity along which pair
+    k's signed distance falls at a rate drawn from `speed` (the gradient by central differences through the reference).  No candidate has a
+    sphere's centre inside a box."""
+    rng = np.random.default_rng(seed)
+    nj = m.nj
+    want = np.repeat(np.arange(3), np.ceil(np.array(share) * B).astype(int))[:B]
+    want = np.concatenate([want, np.zeros(B - len(want), dtype=want.dtype)])
+    q = np.zeros((B, nj)); qd = np.zeros((B, nj)); done = np.zeros(B, dtype=bool)
+    bsp = [j for j in range(m.npairs) if m.pair_kind[j] == A.MH_ARTIC_PAIR_BOX_SPHERE]
+    if k is None: k = bsp[0]
+    for _ in range(200):
+        cq, cqd = sampler(rng, 4096)
+        reg, dist = ref.regions(m, cq)
+        ok = (dist[:, bsp] > gap[0]).all(axis=1) & (dist[:, k] < gap[1])
+        for r in range(3):
+            cand = np.nonzero(ok & (reg[:, k] == r))[0]
+            need = np.nonzero(~done & (want == r))[0]
+            n = min(len(cand), len(need))
+            q[need[:n]] = cq[cand[:n]]; qd[need[:n]] = cqd[cand[:n]]; done[need[:n]] = True
+        if done.all(): break
+    assert done.all(), "no candidate for regions %r" % sorted(set(want[~done]))
+    h = 1e-6
+    grad = np.zeros((B, nj))
+    for j in range(nj):
+        qp = q.copy(); qp[:, j] += h; qm = q.copy(); qm[:, j] -= h
+        grad[:, j] = (ref.regions(m, qp)[1][:, k] - ref.regions(m, qm)[1][:, k]) / (2 * h)
+    g2 = (grad * grad).sum(axis=1)
+    assert (g2 > 1e-12).all()
+    qd -= grad * (rng.uniform(speed[0], speed[1], B) / g2)[:, None]
+    return q, qd
+
+
+def _yaw(x0, lo=-0.6, hi=0.6):
+    return dict(parent=-1, type=A.MH_JOINT_REVOLUTE, R0=np.eye(3), x0=x0, axis=(0.0, 1.0, 0.0), com=(0.0, 0.0, 0.0), inertia=np.eye(3) * 0.02,
+                mass=0.2, lo=lo, hi=hi)
+
+
+def _uniform(lo, hi, vel):
+    lo = np.asarray(lo, dtype=float); hi = np.asarray(hi, dtype=float); vel = np.asarray(vel, dtype=float)
+    return lambda rng, N: (rng.uniform(lo, hi, (N, len(lo))), rng.uniform(-vel, vel, (N, len(lo))))
+
+
+# ---- scenes (gravity along -y, the plane y = 0): name(mu, eps, iters) -> (model, sampler, dt); states come from aim() ----
+def arm_static(mu=100.0, eps=0.3, iters=10):
+    """a planar two-link arm on a yawing base hinge whose tip sphere comes down onto a static box beside it: the box's top face, its edges and
+    its corners are in reach"""
+    links = [_yaw((0.0, 1.0, 0.0)), _hinge(0, (0.0, 1.0, 0.0), (0.25, 0.0, 0.0)), _hinge(1, (0.5, 1.0, 0.0), (0.2, 0.0, 0.0), lo=-2.2, hi=2.2, restitution=0.1)]
+    m = A.model_from_links(links, gravity=G)
+    A.add_spheres(m, [(2, (0.4, 0.0, 0.0), 0.06)], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_boxes(m, [(-1, (0.75, 0.45, 0.0), np.eye(3), (0.5, 0.3, 0.24))], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_box_sphere_pairs(m, [(0, 0)])
+    m.cstab_max_iterations = iters
+    return m, _uniform((-0.55, -0.9, -1.2), (0.55, 0.2, 0.6), (0.3, 0.3, 0.5)), 1e-3
+
+
+def arm_slider_box(mu=100.0, eps=0.3, iters=10):
+    """the same arm over a box that rides on a second-root slider along x and rests on the plane"""
+    links = [_yaw((0.0, 0.8, 0.0)), _hinge(0, (0.0, 0.8, 0.0), (0.25, 0.0, 0.0)), _hinge(1, (0.5, 0.8, 0.0), (0.2, 0.0, 0.0), lo=-2.2, hi=2.2, restitution=0.1),
+             slider((0.8, 0.15, 0.0), (1.0, 0.0, 0.0), mass=0.6, inertia=0.05)]
+    m = A.model_from_links(links, gravity=G)
+    A.add_spheres(m, [(2, (0.4, 0.0, 0.0), 0.06)], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_boxes(m, [(3, (0.0, 0.0, 0.0), np.eye(3), (0.4, 0.3, 0.24))], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_box_sphere_pairs(m, [(0, 0)])
+    m.cstab_max_iterations = iters
+    return m, _uniform((-0.55, -1.1, -1.2, -0.15), (0.55, 0.0, 0.6, 0.15), (0.3, 0.3, 0.5, 0.3)), 1e-3
+
+
+def floating_box_pendulum(mu=100.0, eps=0.3, iters=10):
+    """a floating base carrying a box (it can land on the plane), and a pendulum on a second root whose bob hits the box"""
+    pend = _hinge(-1, (0.0, 1.1, 0.0), (0.0, -0.5, 0.0), mass=0.5)
+    m = A.model_from_links([pend], gravity=G, floating_base=dict(R0=np.eye(3), x0=(0.0, 0.35, 0.0), mass=2.0, inertia=np.diag([0.2, 0.3, 0.25])))
+    m.parent[6] = -1                                               # the pendulum hangs from the world
+    for k, v in enumerate((0.0, 1.1, 0.0)): m.trel[6][k] = v
+    A.add_spheres(m, [(6, (0.0, -0.5, 0.0), 0.07)], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_boxes(m, [(5, (0.0, 0.0, 0.0), np.eye(3), (0.4, 0.3, 0.3))], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_box_sphere_pairs(m, [(0, 0)], no_plane=(0,))
+    m.cstab_max_iterations = iters
+    return m, _uniform((-0.35, 0.0, -0.3, -0.3, -0.3, -0.3, -0.6), (0.35, 0.08, 0.3, 0.3, 0.3, 0.3, 0.6), (0.2, 0.2, 0.2, 0.5, 0.5, 0.5, 0.5)), 1e-3
+
+
+def mixed_all(mu=100.0, eps=0.3, iters=10):
+    """artic_pair_ref.mixed_box with the arm's tip sphere and the pendulum's bob also meeting a static box: a sphere pair, two box-sphere pairs
+    and the plane contacts of a sphere and a box in one list"""
+    arm = _hinge(-1, (0.3, 0.4, 0.0), (0.2, 0.0, 0.0), mass=0.3, lo=-0.8, hi=0.8, restitution=0.2)
+    pend = _hinge(-1, (0.85, 0.9, 0.0), (0.0, -0.5, 0.0), mass=0.5)
+    m = A.model_from_links([arm, pend], gravity=G, floating_base=dict(R0=np.eye(3), x0=(0.0, 0.4, 0.0), mass=2.0, inertia=np.diag([0.2, 0.3, 0.25])))
+    m.parent[7] = -1
+    for k, v in enumerate((0.85, 0.9, 0.0)): m.trel[7][k] = v
+    A.add_spheres(m, [(6, (0.4, 0.0, 0.0), 0.05), (7, (0.0, -0.5, 0.0), 0.08)], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_boxes(m, [(5, (0.0, 0.0, 0.0), np.eye(3), (0.4, 0.3, 0.35)), (-1, (0.78, 0.1, 0.0), np.eye(3), (0.3, 0.2, 0.2))],
+                plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_pairs(m, [(0, 1)], no_plane=(1,))
+    A.add_box_sphere_pairs(m, [(1, 0), (1, 1)])
+    m.cstab_max_iterations = iters
+    lo = (-0.25, 0.0, -0.3, -0.1, -0.3, -0.1, -0.8, -0.1); hi = (0.15, 0.1, 0.3, 0.1, 0.3, 0.1, 0.1, 0.4)
+    return m, _uniform(lo, hi, (0.2, 0.2, 0.2, 0.5, 0.5, 0.5, 0.5, 1.0)), 1e-3
+
+
+def long_arm_static(mu=100.0, eps=0.2, iters=10):
+    """a 12-joint chain (a yawing base hinge and eleven planar hinges) whose tip sphere drapes onto a static box: from 12 joints on the C X C'
+    blocks live in the HBM workspace"""
+    links = [_yaw((0.0, 0.9, 0.0))]
+    for k in range(11):
+        links.append(_hinge(k, (0.1 * k, 0.9, 0.0), (0.05, 0.0, 0.0), mass=0.1, lo=-0.5 if k else None, hi=0.5 if k else None, restitution=0.1))
+    m = A.model_from_links(links, gravity=G)
+    A.add_spheres(m, [(11, (0.1, 0.0, 0.0), 0.05)], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_boxes(m, [(-1, (1.3, 0.45, 0.0), np.eye(3), (0.5, 0.3, 0.24))], plane_normal=UP, epsilon=eps, mu_coulomb=mu)
+    A.add_box_sphere_pairs(m, [(0, 0)])
+    m.cstab_max_iterations = iters
+    lo = [-0.4, -0.5] + [-0.15] * 10; hi = [0.4, 0.1] + [0.08] * 10
+    return m, _uniform(lo, hi, [0.3] * 12), 1e-3
+
+
+SCENES = dict(arm_static=arm_static, arm_slider_box=arm_slider_box, floating_box_pendulum=floating_box_pendulum, mixed_all=mixed_all,
+              long_arm_static=long_arm_static)
