@@ -1,4 +1,4 @@
-// mh_artic_contacts.inc -- included by mh_artic.hip inside namespace mh::artic.
+// mh_artic_contacts.inc -- included by mh_artic_dev.h inside namespace mh::artic.
 //
 // The articulated stepper for bodies whose links carry sphere primitives (mh_artic_model.nspheres > 0) against one static plane:
 // TimeSteppingSimulator::step in full (TSS:52-222) -- conservative advancement over the (sphere, plane) pairs with the ARTICULATED
@@ -8,7 +8,7 @@
 // (ICH:530-626, ICH-QP:94-497) below that.  Operation order = oracle/artic.hpp (handle_impacts, do_mini_step), bit for bit.
 //
 // A kernel of its own (k_artic_step_contacts): config 5's kernel keeps its 10 KB LDS image and its register budget.  One
-// wavefront per world; the link quantities of mh_artic.hip's Lay first, then the contact work area below (8 KB at 10 joints + three arrays inside the dead forward-dynamics arrays).
+// wavefront per world; the link quantities of mh_artic_dev.h's Lay first, then the contact work area below (8 KB at 10 joints + three arrays inside the dead forward-dynamics arrays).
 // Element-wise products run one output per lane with the oracle's inner loop; the greedy tangent set (<= 8 Cholesky
 // factorisations of <= 8 x 8) and the Schur-complement assembly run on lane 0 out of LDS -- no private arrays, no barriers
 // under divergent control flow.
@@ -43,7 +43,7 @@ struct LayC {
   int qsave, V, cp, C, XC, G, CL, Cv, Lv, MM, qq, QX, W, Yy, YXv, t2, imp, l, A, art, ints, total;
   // The arrays that live across calls (qsave, V, the contact list, ints) and most temporaries sit behind the config-5 image; the
   // three largest temporaries (MM, the LU scratch A, the C X C' blocks G) go into the forward-dynamics arrays that are dead while
-  // the impact handler runs (I6 .. Iv of mh_artic.hip's Lay: composite inertias, RNEA velocities / accelerations / forces --
+  // the impact handler runs (I6 .. Iv of mh_artic_dev.h's Lay: composite inertias, RNEA velocities / accelerations / forces --
   // rebuilt by the next dynamics call; R, x, S, H, L, X are NOT in there) when they fit: 18 KB instead of 25 KB at 10 joints.
   __host__ __device__ LayC(int base, int n, int arena, int arena_size) {
     int o = base, a = arena;
@@ -1479,91 +1479,36 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   }
 }
 
-#if defined(MH_ARTIC_BSP_TU) && !defined(MH_ARTIC_POSE_TU)
-// the box-sphere kernels (mh_artic_bsp.hip): {plain, stab} x {undriven, driven} in angle coordinates; one world per workgroup's LDS image as the box kernels
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                             mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
-#elif defined(MH_ARTIC_BSP_TU)
-// the same four in pose coordinates (mh_artic_bsp_pose.hip)
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_bsp_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
-#elif defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_POSE_TU)
-// the pair kernels (mh_artic_pair.hip): {plain, stab} x {undriven, driven} in angle coordinates; one world per workgroup's LDS image as the box kernels
-__global__ __launch_bounds__(64)
-void k_artic_step_pair(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                             mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
-#elif defined(MH_ARTIC_PAIR_TU)
-// the same four in pose coordinates (mh_artic_pair_pose.hip)
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_pair_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                       mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
-#elif defined(MH_ARTIC_BOX_TU) && !defined(MH_ARTIC_POSE_TU)
-// the box kernels (mh_artic_box.hip): {plain, stab} x {undriven, driven} in angle coordinates; their LDS image holds one world per SIMD or two
-// (DESIGN 4.4), so no waves-per-EU bound
-__global__ __launch_bounds__(64)
-void k_artic_step_box(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                      mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
-__global__ __launch_bounds__(64)
-void k_artic_step_box_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
-__global__ __launch_bounds__(64)
-void k_artic_step_box_stab(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                           mh_world_aux* __restrict__ auxg, double* __restrict__ wsg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr); }
-__global__ __launch_bounds__(64)
-void k_artic_step_box_stab_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D); }
-#elif defined(MH_ARTIC_BOX_TU)
-// the same four in pose coordinates (mh_artic_box_pose.hip)
-__global__ __launch_bounds__(64)
-void k_artic_step_box_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                           mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_box_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                 mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<false>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_box_stab_pose(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr, poseg); }
-__global__ __launch_bounds__(64)
-void k_artic_step_box_stab_pose_drive(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg,
-                                      mh_world_aux* __restrict__ auxg, double* __restrict__ wsg, double* __restrict__ poseg, mh_artic_drive D) { artic_contacts_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D, poseg); }
+#ifdef MH_ARTIC_BOX_TU
+// the geometry kernels, four per code object: k_artic_step_<fam>[_stab][_pose][_drive], {plain, stab} x {undriven, driven}, <fam> the file's
+// family token MH_ARTIC_GEOM (box, pair, bsp) and _pose (with the B x 7 poses as one more argument) under MH_ARTIC_POSE_TU.  The drive is a
+// pointer in the body, NULL = undriven.  One world per workgroup; the LDS image holds one world per SIMD or two (DESIGN 4.4), so no
+// waves-per-EU bound
+#ifndef MH_ARTIC_GEOM
+#error "a geometry translation unit (MH_ARTIC_BOX_TU) names its family: #define MH_ARTIC_GEOM box | pair | bsp"
+#endif
+#ifdef MH_ARTIC_POSE_TU
+#define MH_GEOM_KERNEL_(fam, stab, drive) k_artic_step_##fam##stab##_pose##drive
+#define MH_GEOM_POSE_PARAM , double* __restrict__ poseg
+#define MH_GEOM_POSE_ARG , poseg
+#else
+#define MH_GEOM_KERNEL_(fam, stab, drive) k_artic_step_##fam##stab##drive
+#define MH_GEOM_POSE_PARAM
+#define MH_GEOM_POSE_ARG
+#endif
+#define MH_GEOM_KERNEL_X(fam, stab, drive) MH_GEOM_KERNEL_(fam, stab, drive)      // (the token is expanded before it is pasted)
+#define MH_GEOM_KERNEL(stab, drive) MH_GEOM_KERNEL_X(MH_ARTIC_GEOM, stab, drive)
+#define MH_GEOM_STAMP(STAB, stab) \
+__global__ __launch_bounds__(64) \
+void MH_GEOM_KERNEL(stab, )(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg, \
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg MH_GEOM_POSE_PARAM) \
+{ artic_contacts_body<STAB>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr MH_GEOM_POSE_ARG); } \
+__global__ __launch_bounds__(64) \
+void MH_GEOM_KERNEL(stab, _drive)(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg, \
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg MH_GEOM_POSE_PARAM, mh_artic_drive D) \
+{ artic_contacts_body<STAB>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D MH_GEOM_POSE_ARG); }
+MH_GEOM_STAMP(false, )
+MH_GEOM_STAMP(true, _stab)
 #elif !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)
 // 2 waves per SIMD = the 8 worlds per CU the 18 KB LDS image allows
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))

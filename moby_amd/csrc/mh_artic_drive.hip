@@ -1,27 +1,12 @@
 // mh_artic_drive.hip -- the driven articulated step (include/moby_hip_artic.h: mh_artic_drive, mh_artic_batch_step_driven).
 //
-// The step kernels of mh_artic.hip with the drive switched in by MH_ARTIC_DRIVE_TU, compiled as a code object of their own: mh_artic.hip
+// The step kernels of mh_artic_dev.h with the drive switched in by MH_ARTIC_DRIVE_TU, compiled as a code object of their own: mh_artic.hip
 // (MH_ARTIC_DRIVE_TU unset) holds the undriven kernels and every other entry point, this file the driven kernels and their launcher.  The
 // preprocessor, not a template parameter, keeps the undriven kernels' source exactly what it was before drives existed, and with it their
 // code (byte-identical ISA): a DRIVE template parameter, dead in the undriven instantiations, changed the register allocation of
 // k_artic_step_w3 / w5 / contacts_stab (w5: six more spilled SGPRs).
 #define MH_ARTIC_DRIVE_TU 1
-#include "mh_artic.hip"
-
-// this code object's copy of the regularisation ladder's powers of ten (mh_artic_batch_create fills mh_artic.hip's), once per device
-static int init_pow10()
-{
-  static std::mutex mu; static std::vector<char> done;
-  std::lock_guard<std::mutex> lk(mu);
-  int dev = 0; MH_HIP(hipGetDevice(&dev));
-  if ((int)done.size() <= dev) done.resize(dev + 1, 0);
-  if (!done[dev]) {
-    mh::Pow10Table p10; for (int i = 0; i < 64; i++) p10.v[i] = std::pow(10.0, (double)(i - 32));   // LCP.cpp:285
-    MH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mh::artic::c_pow10a), &p10, sizeof(p10)));
-    done[dev] = 1;
-  }
-  return MH_OK;
-}
+#include "mh_artic_dev.h"
 
 extern "C" {
 
@@ -37,7 +22,7 @@ int mh_artic_batch_step_driven(mh_artic_batch* ab, void* stream, double dt, int 
   if (rc != MH_OK) return rc;
   if (nsteps == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
-  if (artic_uses_box(ab)) return artic_box_step(ab, stream, dt, nsteps, &D);
+  if (artic_geom_family(ab) != MH_ARTIC_FAM_NONE) return artic_geom_step(ab, stream, dt, nsteps, &D);
   if (ab->base_coords == MH_ARTIC_BASE_POSE) return artic_pose_step(ab, stream, dt, nsteps, &D);
   if (init_pow10() != MH_OK) return MH_ERR_HIP;
   const ar::Model* M = ab->d_model;

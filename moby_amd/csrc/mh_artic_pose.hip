@@ -1,26 +1,11 @@
 // mh_artic_pose.hip -- the articulated step in pose coordinates (include/moby_hip_artic.h: MH_ARTIC_BASE_POSE, mh_artic_batch_set_base_coords).
 //
-// The kernels of mh_artic.hip / mh_artic_contacts.inc with the floating base's pose switched in by MH_ARTIC_POSE_TU, compiled as a code object of
+// The kernels of mh_artic_dev.h / mh_artic_contacts.inc with the floating base's pose switched in by MH_ARTIC_POSE_TU, compiled as a code object of
 // their own, as mh_artic_drive.hip does for drives: the angle-coordinate kernels of mh_artic.hip and mh_artic_drive.hip keep their code byte for
 // byte.  Here: the step at the default four-waves budget, the stabilising step and both contact steps, each undriven and driven; the forward
 // dynamics / link poses and Jacobian kernels; the fold of the switch from angles; and the pose entry points of the C ABI.
 #define MH_ARTIC_POSE_TU 1
-#include "mh_artic.hip"
-
-// this code object's copy of the regularisation ladder's powers of ten (mh_artic_batch_create fills mh_artic.hip's), once per device
-static int init_pow10()
-{
-  static std::mutex mu; static std::vector<char> done;
-  std::lock_guard<std::mutex> lk(mu);
-  int dev = 0; MH_HIP(hipGetDevice(&dev));
-  if ((int)done.size() <= dev) done.resize(dev + 1, 0);
-  if (!done[dev]) {
-    mh::Pow10Table p10; for (int i = 0; i < 64; i++) p10.v[i] = std::pow(10.0, (double)(i - 32));   // LCP.cpp:285
-    MH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mh::artic::c_pow10a), &p10, sizeof(p10)));
-    done[dev] = 1;
-  }
-  return MH_OK;
-}
+#include "mh_artic_dev.h"
 
 int artic_pose_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D)
 {
