@@ -440,11 +440,26 @@ MH_DEV bool lcp_fast_wave(int n, const MatT& M, double lam, LuScratch S,
     const uint64_t bmask = vmask & ~nbmask;
     // both draws of the iteration (LCP.cpp:147 then :153/:172): every path takes the w draw when a basic
     // variable exists and then the z draw when a nonbasic one does, in that order
+    //
+    // Decision shortcuts.  The draws' results are read below only through `wsel > -zero_tol` and `zsel < -zero_tol` (then minw / minz, and
+    // `tie` in the repeat test); wsel / zsel are each ONE of the candidates.  If no basic w fails `w > -zero_tol`, the w branch is not
+    // taken whichever lane the draw picks: the reduction, the tie ballot and the selection are skipped, the draw itself (rng.next()) is
+    // still consumed, minw = -1 takes the same way out.  A NaN among the w's (or a NaN tolerance) fails the test and goes through
+    // rand_min_wave with std::min_element's NaN semantics.  Likewise no z can be removed when no nonbasic z has `z < -zero_tol`; a NaN
+    // among the z's takes the full path.  `tie` is read only inside "w branch taken AND z branch taken": on that path neither shortcut
+    // fired, so it holds both draws' contributions as before; on every other path nothing reads it.  The final z (`is_nb ? zv : 0`)
+    // depends on neither draw.
     double wsel = 0.0; int minw = -1;
     bool tie = false;
-    if (bmask != 0ull) minw = rand_min_wave(w, bmask, zero_tol, rng, wsel, tie);
+    if (bmask != 0ull) {
+      if (ballot(is_b && !(w > -zero_tol)) == 0ull) (void)rng.next();
+      else minw = rand_min_wave(w, bmask, zero_tol, rng, wsel, tie);
+    }
     double zsel = 0.0; int minz = -1;
-    if (k > 0) minz = rand_min_wave(zv, nbmask, zero_tol, rng, zsel, tie);
+    if (k > 0) {
+      if (ballot(is_nb && !(zv >= -zero_tol)) == 0ull) (void)rng.next();
+      else minz = rand_min_wave(zv, nbmask, zero_tol, rng, zsel, tie);
+    }
     lp_tock(LP_RANDMIN, tg);
     if (minw < 0 || wsel > -zero_tol) {
       if (minz >= 0 && zsel < -zero_tol) {
