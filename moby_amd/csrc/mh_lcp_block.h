@@ -49,6 +49,7 @@ struct Ws {
   int* flag;      // 1 = nonbasic
   int* pos;       // position of variable i in list (-1 if basic)
   int* bv;        // Lemke: basis by position
+  size_t cap;     // doubles of this problem's slot, from A on: ws_doubles(the launch's n)
 };
 MH_DEV size_t ws_doubles(int n) { return (size_t)n * n + 5 * (size_t)n; }
 MH_DEV size_t ws_ints(int n) { return 4 * (size_t)n; }
@@ -596,7 +597,8 @@ MH_DEV bool lcp_fast(const Mat& M, double lam, const Ws& W, const double* q, dou
     const int k = build_list(n, W);
     bp_tock(BP_LIST, tq); tq = bp_tick();
 #ifdef MH_BLK_HAS_REGLU
-    if (k > 0 && k <= RL_KMAX && reg_lu) {                  // the whole system in the registers of the sixteen waves (mh_lu_reg.inc)
+    // (U, k columns of RL_ROWS doubles from W.A on, must fit the slot: always at launch n >= RL_ROWS, not with a geometry forced below it)
+    if (k > 0 && k <= RL_KMAX && reg_lu && (size_t)k * RL_ROWS <= W.cap) {  // the whole system in the registers of the sixteen waves (mh_lu_reg.inc)
       for (int i = t; i < k; i += T) s_list[i] = W.list[i];
       sync();
       bp_tock(BP_GATHER, tq);
@@ -1001,6 +1003,7 @@ void k_lcp_block(int B, int n, const double* __restrict__ Mg, int ld, long strid
   // per-problem sizes: strides of q / z / M / the workspace stay those of the largest problem (the launch's n), M is
   // compact (ld = its own n); problems of at most 64 rows belong to the wave solver of the same call
   const int nstride = n;
+  W.cap = ws_doubles(nstride);
   if (n_arr) { n = n_arr[bw]; ld = n; if (n <= MH_LCP_MAX_N_WAVE) { if (task_worlds > 0 && t == 0) status[b] = -1; continue; } }
   W.A = wd; W.b = wd + (size_t)n * n; W.w = W.b + n; W.x = W.w + n; W.d = W.x + n; W.art = W.d + n;
   W.list = wi; W.flag = wi + n; W.pos = wi + 2 * (size_t)n; W.bv = wi + 3 * (size_t)n;
