@@ -64,7 +64,7 @@ typedef struct mh_lcp_opts {
 /* library / device ------------------------------------------------------- */
 /* 100 * major + minor.  101: mh_impact_batch_lu_work / mh_big_batch_lu_work fill B x 4 doubles per call (100: B x 2) -- a caller built against the
  * two-column layout must check for >= 101 and size its buffer accordingly (#define MH_VERSION is what this header describes). */
-#define MH_VERSION 101
+#define MH_VERSION 102   /* 102: recurrent forces and per-world body wrenches in the many-worlds stepper (mh_world_forces, mh_world_batch_set_forces / _step_wrench) */
 int         mh_version(void);
 const char* mh_last_error(void);
 int         mh_device_count(void);
@@ -296,9 +296,51 @@ int mh_world_batch_occupancy(mh_world_batch* wb);   /* diagnostic: resident work
 int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* phase_cycles, int nphase);
 int mh_world_profile_phase_count(void);            /* entries per world of the stamped launch (the four totals follow them) */
 
+/* Recurrent forces of the scene and per-world body wrenches, inside the step.  Replaces Simulator::precalc_fwd_dyn (src/Simulator.cpp:319-350): the
+ * accumulators are cleared, then the simulator's recurrent forces run, then the body's controller, once per MINI-STEP (TimeSteppingSimulator.cpp:173),
+ * immediately before that mini-step's forward dynamics: positions are the mini-step's, v and omega still its starting velocities.  For body b (mass m,
+ * rotation R of its quaternion, row-major; all vectors in world axes at the COM, as MH_BODY_STATE is) the terms accumulate in this fixed order, every
+ * operation rounded on its own, three-term sums as (a + b) + c, an absent term left out (not added as zero):
+ *   1. gravity                                   F = g m                                            (no torque)
+ *   2. Stokes drag (StokesDragForce.cpp:39-44)   F = F + v (-stokes_b[b])            T = omega (-stokes_b_ang[b])
+ *   3. damping (DampingForce.cpp:32-51)          vi = R' v, wi = R' omega, fb = vi (-(kl[b] + |vi| klsq[b])), tb = wi (-(ka[b] + |wi| kasq[b]))
+ *                                                F = F + R fb                        T = T + R tb   (T = R tb when it is the first torque term)
+ *   4. the caller's wrench (f, tau) of this world, body and schedule row
+ *                                                F = F + f                           T = T + tau    (T = tau when it is the first torque term)
+ * then xdd = F / m and omega' = Jw^-1 (T - omega x (Jw omega)) -- or Jw^-1 (-(omega x (Jw omega))), the expression of the plain step, when no torque
+ * term is present.  The coefficients belong to the SCENE (one set for all worlds of the batch: a DampingForce body without a <Gains> child has zero gains and
+ * still carries the term); the wrench is per world.  Conservative advancement, contact generation, the impact handler and the stabiliser never read forces. */
+#define MH_FORCE_STOKES  1
+#define MH_FORCE_DAMPING 2
+typedef struct mh_world_forces {           /* recurrent forces of the scene: shared by all worlds of the batch */
+  int    terms;                            /* MH_FORCE_* bits; 0 = none */
+  double stokes_b[MH_MAX_BODIES], stokes_b_ang[MH_MAX_BODIES];
+  double damp_kl[MH_MAX_BODIES], damp_ka[MH_MAX_BODIES], damp_klsq[MH_MAX_BODIES], damp_kasq[MH_MAX_BODIES];
+} mh_world_forces;
+/* Stores the scene's recurrent forces in the batch (HOST pointer; copied).  NULL or terms == 0 clears them: the batch launches the plain kernels again.
+ * MH_ERR_INVALID_ARG: unknown bits in `terms`, or a non-finite coefficient in an array of a term that is set (all MH_MAX_BODIES entries are looked at:
+ * zero the unused ones).  Once stored, mh_world_batch_step, _step_ids and _profile honour them too -- they belong to the scene.  A batch with stored
+ * forces, and any launch with a wrench, runs the FORCED code objects (mh_world_{small,wheel,large}_forces.hip: same variants, same launch bounds);
+ * mh_world_batch_occupancy then reports those -- it reports the forced kernel while forces are STORED; a batch stepped with a wrench alone also launches the
+ * forced object of its variant but is reported as the plain one (to query the forced kernel of such a batch, store any term, ask, and clear it).  The forced launch of _profile is the forced production kernel, which has no stamps: it steps the worlds
+ * and reports zero cycles.  Not to be called while a launch of the batch is in flight. */
+int mh_world_batch_set_forces(mh_world_batch* wb, const mh_world_forces* host);
+/* mh_world_batch_step (ids_dev == NULL: the whole batch, `count` ignored) or _step_ids (ids_dev: a DEVICE array of `count` world indices) with a wrench
+ * schedule: wrench_dev is a DEVICE array of rows x B x nb x 6 doubles (fx fy fz tx ty tz; B = the worlds of the BATCH: a world reads the entries at its own
+ * index in the batch, also when ids_dev selects a subset).  rows == 1: row 0 holds for the whole launch; rows >= nsteps: every mini-step of step s reads
+ * row s.  wrench_dev == NULL: the stored recurrent forces only; with none stored the call IS mh_world_batch_step / _step_ids.  MH_ERR_INVALID_ARG:
+ * rows < 1, 1 < rows < nsteps, traj_dev together with ids_dev.  A world carrying MH_WORLD_LCP_FAILED is passed over, as in every launch. */
+int mh_world_batch_step_wrench(mh_world_batch* wb, void* stream, double dt, int nsteps, double* traj_dev,
+                               const int* ids_dev, int count, const double* wrench_dev, int rows);
+
 /* Host convenience: create + upload + step + download (+ trajectory) + destroy. */
 int mh_world_step_batch(const mh_scene* scene, int B, double dt, int nsteps,
                         double* state, mh_world_aux* aux, double* traj);
+/* The same under the scene's recurrent forces (NULL or terms == 0: none, which is mh_world_step_batch).  It exists for callers that hold no
+ * device memory of their own: the regress runner (moby-hip-regress: a scene file with drag from the reference's command line, trajectory rows on
+ * the host) and moby_amd.world.WorldBatch(forces=) go through it; a wrench needs a DEVICE array and therefore a resident batch. */
+int mh_world_step_batch_forces(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
+                               double* state, mh_world_aux* aux, double* traj);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@
 //   sim.step(1e-3);                 // Simulator::step(dt): every world advances by dt; returns dt
 //   sim.step(1e-3, 1000);           // the same step 1000 times inside ONE launch
 //   sim.current_time;               // Simulator::current_time of world 0
+//   sim.set_forces(forces);         // the simulator's recurrent forces besides gravity (StokesDragForce, DampingForce): mh_world_forces
+//   sim.step_wrench(1e-3, wrench_dev);   // ... and what the bodies' controllers add_force this step: a DEVICE array B x nb x 6
 //   sim.get_generalized_coordinates_euler(w, b, q);   // x y z qx qy qz qw of body b of world w
 //
 // Conventions kept from the reference: step() returns the step size; bodies are addressed in id order
@@ -43,6 +45,19 @@ class BatchedTimeSteppingSimulator {
   /// Simulator::step(dt), for every world; nsteps > 1 repeats it inside one launch
   double step(double dt, int nsteps = 1) {
     if (mh_world_batch_step(_wb, /*stream=*/NULL, dt, nsteps, /*traj=*/NULL) != MH_OK) throw std::runtime_error(mh_last_error());
+    _dirty = true;
+    current_time += dt * nsteps;
+    return dt;
+  }
+  /// The simulator's recurrent forces besides gravity (Simulator::recurrent_forces: StokesDragForce, DampingForce), evaluated once per mini-step like the
+  /// reference's; they hold for every later step of every world.  clear_forces() returns to gravity alone.
+  void set_forces(const mh_world_forces& forces) { if (mh_world_batch_set_forces(_wb, &forces) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  void clear_forces() { if (mh_world_batch_set_forces(_wb, NULL) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  /// Simulator::step(dt) with the wrenches the bodies' controllers would add_force: wrench_dev is a DEVICE array of rows x B x nb x 6 doubles
+  /// (fx fy fz tx ty tz, world axes at the COM); rows == 1 holds it for all nsteps, rows >= nsteps is one row per step.  NULL: recurrent forces only.
+  /// (A name of its own, not an overload of step: step(dt, NULL) would be ambiguous between a null pointer and nsteps = 0.)
+  double step_wrench(double dt, const double* wrench_dev, int nsteps = 1, int rows = 1) {
+    if (mh_world_batch_step_wrench(_wb, /*stream=*/NULL, dt, nsteps, /*traj=*/NULL, /*ids=*/NULL, 0, wrench_dev, rows) != MH_OK) throw std::runtime_error(mh_last_error());
     _dirty = true;
     current_time += dt * nsteps;
     return dt;

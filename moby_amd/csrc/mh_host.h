@@ -102,6 +102,18 @@ MH_HIDDEN const mh_world_variant* mh_world_variant_large();
 MH_HIDDEN const mh_world_variant* mh_world_variant_small_prof();     // the same kernels with the phase profiler's stamps compiled in (mh_world_*_prof.hip)
 MH_HIDDEN const mh_world_variant* mh_world_variant_wheel_prof();
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_prof();
+// the same three with recurrent forces and the caller's wrench in the forward dynamics (mh_world_*_forces.hip): the plain arguments, then the stored terms
+// (device copy of mh_world_forces, or NULL), the wrench schedule (rows x B x nb x 6 doubles, or NULL) and its rows
+typedef void (*mh_world_forced_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*,
+                                       const mh_world_forces*, const double*, int);
+struct mh_world_forced_variant {
+  mh_world_forced_kernel kernel;
+  int ph_count;
+  hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
+};
+MH_HIDDEN const mh_world_forced_variant* mh_world_variant_small_forces();
+MH_HIDDEN const mh_world_forced_variant* mh_world_variant_wheel_forces();
+MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_forces();
 
 // mh_debug_set keys 1 / 2 (test hooks; defined in mh_capi.hip)
 extern MH_HIDDEN int mh_g_debug_ka;

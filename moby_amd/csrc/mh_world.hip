@@ -35,6 +35,8 @@ hipError_t init_tables()
   const mh_world_variant* vs[6] = { mh_world_variant_small(), mh_world_variant_wheel(), mh_world_variant_large(),
                                     mh_world_variant_small_prof(), mh_world_variant_wheel_prof(), mh_world_variant_large_prof() };     // (one copy of the tables per code object)
   for (int i = 0; i < 6 && g_tables_err == hipSuccess; i++) g_tables_err = vs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  const mh_world_forced_variant* fs[3] = { mh_world_variant_small_forces(), mh_world_variant_wheel_forces(), mh_world_variant_large_forces() };
+  for (int i = 0; i < 3 && g_tables_err == hipSuccess; i++) g_tables_err = fs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   return g_tables_err;
 }
 hipError_t tables_for_current_device()
@@ -114,7 +116,27 @@ struct mh_world_batch {
   double* d_lu_ws;
   double* d_state;
   mh_world_aux* d_aux;
+  mh_world_forced_kernel fkernel;   // the same variant built with MHW_FORCES: launched while forces are stored or when a wrench is passed
+  bool has_forces;                  // mh_world_batch_set_forces stored terms != 0
+  mh_world_forces* d_forces;        // their device copy (allocated by the first set_forces)
 };
+
+namespace {
+// the one launch behind every stepping entry: the plain kernel, or the forced one when the batch stores forces or the caller passes a wrench
+int launch_step(mh_world_batch* wb, hipStream_t stream, int grid, double dt, int nsteps, double* traj_dev, unsigned long long* prof, const int* ids_dev,
+                const double* wrench_dev, int rows)
+{
+  if (wb->has_forces || wrench_dev)
+    hipLaunchKernelGGL(wb->fkernel, dim3(grid), dim3(64), 0, stream,
+                       (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev,
+                       (const mh_world_forces*)(wb->has_forces ? wb->d_forces : nullptr), wrench_dev, rows);
+  else
+    hipLaunchKernelGGL(wb->kernel, dim3(grid), dim3(64), 0, stream,
+                       (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev);
+  MH_HIP(hipGetLastError());
+  return MH_OK;
+}
+}  // namespace
 
 // diagnostic: blocks per CU the runtime's occupancy query reports for the kernel this batch uses
 int mh_world_batch_occupancy(mh_world_batch* wb);
@@ -123,7 +145,8 @@ int mh_world_batch_occupancy(mh_world_batch* wb)
   if (!wb) return fail(MH_ERR_INVALID_ARG, "null batch");
   MH_ON_DEVICE(wb);
   int n = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->kernel, 64, 0);
+  hipError_t e = wb->has_forces ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->fkernel, 64, 0)
+                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->kernel, 64, 0);
   if (e != hipSuccess) return fail(MH_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
   return n;
 }
@@ -156,6 +179,8 @@ int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
     if (!noslip && !box && scene->nb <= 4 && npairs <= 6 && scene->lcp_n_max > 0 && scene->lcp_n_max <= 56) { wb->variant = 0; wb->kernel = mh_world_variant_small()->kernel; }
     else if (noslip && !box && scene->nb <= 2 && npairs <= 3) { wb->variant = 2; wb->kernel = mh_world_variant_wheel()->kernel; }
     else { wb->variant = 1; wb->kernel = mh_world_variant_large()->kernel; }
+    wb->fkernel = (wb->variant == 0 ? mh_world_variant_small_forces() : wb->variant == 2 ? mh_world_variant_wheel_forces() : mh_world_variant_large_forces())->kernel;
+    wb->has_forces = false; wb->d_forces = nullptr;
   }
   wb->d_scene = nullptr; wb->d_state = nullptr; wb->d_aux = nullptr; wb->d_lu_ws = nullptr;
   // device scene record, followed by the spoke-tip table p1 = (cos(theta) R, sin(theta) R), theta = pi i 2 / N
@@ -193,6 +218,7 @@ int mh_world_batch_destroy(mh_world_batch* wb)
   if (wb->d_state) (void)hipFree(wb->d_state);
   if (wb->d_aux) (void)hipFree(wb->d_aux);
   if (wb->d_lu_ws) (void)hipFree(wb->d_lu_ws);
+  if (wb->d_forces) (void)hipFree(wb->d_forces);
   delete wb;
   return MH_OK;
 }
@@ -213,11 +239,7 @@ int mh_world_batch_step(mh_world_batch* wb, void* stream, double dt, int nsteps,
   if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
   if (nsteps == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
-  hipLaunchKernelGGL(wb->kernel, dim3(wb->B), dim3(64), 0, (hipStream_t)stream,
-                     (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka,
-                     (unsigned long long*)nullptr, (const int*)nullptr);
-  MH_HIP(hipGetLastError());
-  return MH_OK;
+  return launch_step(wb, (hipStream_t)stream, wb->B, dt, nsteps, traj_dev, nullptr, nullptr, nullptr, 1);
 }
 
 // nsteps x step(dt) of the worlds ids[0 .. count) only (device pointer), on the given stream: worlds are independent, so a batch can be
@@ -230,11 +252,43 @@ int mh_world_batch_step_ids(mh_world_batch* wb, void* stream, double dt, int nst
   if (nsteps < 0 || count < 0 || count > wb->B) return fail(MH_ERR_INVALID_ARG, "bad step count (%d) or id count (%d of %d)", nsteps, count, wb->B);
   if (nsteps == 0 || count == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
-  hipLaunchKernelGGL(wb->kernel, dim3(count), dim3(64), 0, (hipStream_t)stream,
-                     (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, (double*)nullptr, wb->nmax, wb->d_lu_ws, mh_g_debug_ka,
-                     (unsigned long long*)nullptr, ids_dev);
-  MH_HIP(hipGetLastError());
+  return launch_step(wb, (hipStream_t)stream, count, dt, nsteps, nullptr, nullptr, ids_dev, nullptr, 1);
+}
+
+int mh_world_batch_set_forces(mh_world_batch* wb, const mh_world_forces* host)
+{
+  const int terms = host ? host->terms : 0;
+  if (terms & ~(MH_FORCE_STOKES | MH_FORCE_DAMPING)) return fail(MH_ERR_INVALID_ARG, "forces: unknown bits in terms (0x%x)", terms);
+  if (terms) {
+    const double* arr[6] = { host->stokes_b, host->stokes_b_ang, host->damp_kl, host->damp_ka, host->damp_klsq, host->damp_kasq };
+    static const char* const nm[6] = { "stokes_b", "stokes_b_ang", "damp_kl", "damp_ka", "damp_klsq", "damp_kasq" };
+    for (int k = 0; k < 6; k++) {
+      if (!(terms & (k < 2 ? MH_FORCE_STOKES : MH_FORCE_DAMPING))) continue;
+      for (int b = 0; b < MH_MAX_BODIES; b++) if (!std::isfinite(arr[k][b])) return fail(MH_ERR_INVALID_ARG, "forces: %s[%d] is not finite", nm[k], b);
+    }
+  }
+  if (!wb) return fail(MH_ERR_INVALID_ARG, "null batch");
+  MH_ON_DEVICE(wb);
+  if (!terms) { wb->has_forces = false; return MH_OK; }
+  if (!wb->d_forces) MH_HIP(hipMalloc(&wb->d_forces, sizeof(mh_world_forces)));
+  MH_HIP(hipMemcpy(wb->d_forces, host, sizeof(mh_world_forces), hipMemcpyHostToDevice));
+  wb->has_forces = true;
   return MH_OK;
+}
+
+int mh_world_batch_step_wrench(mh_world_batch* wb, void* stream, double dt, int nsteps, double* traj_dev,
+                               const int* ids_dev, int count, const double* wrench_dev, int rows)
+{
+  if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
+  if (rows < 1) return fail(MH_ERR_INVALID_ARG, "wrench: rows = %d (must be >= 1)", rows);
+  if (rows > 1 && rows < nsteps) return fail(MH_ERR_INVALID_ARG, "wrench: %d rows for %d steps (1 row, or one per step)", rows, nsteps);
+  if (traj_dev && ids_dev) return fail(MH_ERR_INVALID_ARG, "a trajectory buffer cannot be combined with an id list");
+  if (!wb) return fail(MH_ERR_INVALID_ARG, "null batch");
+  MH_ON_DEVICE(wb);
+  if (ids_dev && (count < 0 || count > wb->B)) return fail(MH_ERR_INVALID_ARG, "bad id count (%d of %d)", count, wb->B);
+  if (nsteps == 0 || (ids_dev && count == 0)) return MH_OK;
+  if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
+  return launch_step(wb, (hipStream_t)stream, ids_dev ? count : wb->B, dt, nsteps, traj_dev, nullptr, ids_dev, wrench_dev, rows);
 }
 
 int mh_world_profile_phase_count(void) { return mh_world_variant_large()->ph_count; }
@@ -251,6 +305,9 @@ int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* ph
   MH_HIP(hipMemset(dprof, 0, sz));
   // the PROFILE build of the batch's variant: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
   const mh_world_kernel kprof = (wb->variant == 0 ? mh_world_variant_small_prof() : wb->variant == 2 ? mh_world_variant_wheel_prof() : mh_world_variant_large_prof())->kernel;
+  // (a batch with stored forces: the forced production kernel -- it steps the worlds under their forces and has no stamps, so every cycle count is 0)
+  if (wb->has_forces) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
+  else
   hipLaunchKernelGGL(kprof, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
                      (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, (double*)nullptr, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, dprof, (const int*)nullptr);
   hipError_t e = hipDeviceSynchronize();
@@ -351,6 +408,12 @@ int mh_world_batch_device_ptrs(mh_world_batch* wb, double** state_dev, mh_world_
 int mh_world_step_batch(const mh_scene* scene, int B, double dt, int nsteps,
                         double* state, mh_world_aux* aux, double* traj)
 {
+  return mh_world_step_batch_forces(scene, nullptr, B, dt, nsteps, state, aux, traj);
+}
+
+int mh_world_step_batch_forces(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
+                               double* state, mh_world_aux* aux, double* traj)
+{
   if (B == 0 || nsteps == 0) return MH_OK;
   if (B < 0 || nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative batch or step count");
   if (!state || !aux) return fail(MH_ERR_INVALID_ARG, "null state/aux");
@@ -360,6 +423,7 @@ int mh_world_step_batch(const mh_scene* scene, int B, double dt, int nsteps,
   double* dtraj = nullptr;
   const size_t sz_tr = (size_t)B * nsteps * scene->nb * 7 * sizeof(double);
   rc = mh_world_batch_upload(wb, state, aux);
+  if (rc == MH_OK && forces) rc = mh_world_batch_set_forces(wb, forces);
   if (rc == MH_OK && traj && hipMalloc(&dtraj, sz_tr) != hipSuccess) rc = fail(MH_ERR_HIP, "trajectory allocation failed");
   if (rc == MH_OK) rc = mh_world_batch_step(wb, nullptr, dt, nsteps, dtraj);
   if (rc == MH_OK) rc = mh_world_batch_download(wb, state, aux);

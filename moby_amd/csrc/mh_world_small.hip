@@ -6,9 +6,17 @@
 #ifdef MH_PROFILE_BUILD      /* mh_world_small_prof.hip: the same kernel with the s_memtime stamps compiled in (mh_world_batch_profile) */
 #define MHW_NS small_prof
 #define MHW_VARIANT_GETTER mh_world_variant_small_prof
+#elif defined(MH_FORCES_BUILD) /* mh_world_small_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
+#define MHW_NS small_forces
+#define MHW_VARIANT_GETTER mh_world_variant_small_forces
+#define MHW_VARIANT_T mh_world_forced_variant
+#define MHW_FORCES 1
 #else
 #define MHW_NS small
 #define MHW_VARIANT_GETTER mh_world_variant_small
+#endif
+#ifndef MHW_VARIANT_T
+#define MHW_VARIANT_T mh_world_variant
 #endif
 #define MHW_NOSLIP 0
 #define MHW_BOX 0
@@ -28,8 +36,8 @@ static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void*
   return e;
 }
 
-const mh_world_variant* MHW_VARIANT_GETTER()
+const MHW_VARIANT_T* MHW_VARIANT_GETTER()
 {
-  static const mh_world_variant v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
+  static const MHW_VARIANT_T v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
   return &v;
 }

@@ -38,7 +38,8 @@
 //
 // This file is compiled once per variant: the includer defines MHW_NS (namespace), MHW_NB, MHW_MAX_PAIRS,
 // MHW_MAX_CONTACTS, MHW_MAX_ROWS, MHW_MAX_GROWS, MHW_WAVES_PER_SIMD and the feature switches MHW_NOSLIP
-// (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).
+// (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).  MHW_FORCES (1 in mh_world_*_forces.hip, undefined = 0 elsewhere) adds the scene's
+// recurrent forces and the caller's wrench to the forward dynamics; every line it adds sits under #if MHW_FORCES.
 #include "mh_world_common.h"
 
 #define MHW_NS_MAXC ((MHW_MAX_CONTACTS < 6) ? MHW_MAX_CONTACTS : 6)   /* contacts of a no-slip island */
@@ -137,6 +138,16 @@ enum { PH_BROAD_CA = 0, PH_INTEGRATE, PH_FWDDYN, PH_CONTACTS, PH_ISLANDS, PH_PDA
        PH_LP0, PH_COUNT = PH_LP0 + LP_COUNT };
 __shared__ unsigned long long g_cnt[CN_COUNT];
 __shared__ unsigned long long g_pacc[PH_COUNT];
+#if MHW_FORCES
+// Recurrent forces of the scene and the caller's wrench (include/moby_hip.h: mh_world_forces, mh_world_batch_step_wrench).  An image of its own beside
+// gd, so that the plain variants' image is the text it was: 6 coefficients per body, cached at launch, and this step's wrench row, staged once per
+// step (a step runs one to three mini-steps and each reads the row; one global read per step, issued before the step's broad phase, instead of one
+// per mini-step in front of the forward dynamics that waits for it).  12 MHW_NB doubles: 384 bytes in the small variant, 16 worlds per CU kept.
+enum { F_SB = 0, F_SBA = MHW_NB, F_KL = 2 * MHW_NB, F_KA = 3 * MHW_NB, F_KLSQ = 4 * MHW_NB, F_KASQ = 5 * MHW_NB, F_WR = 6 * MHW_NB, F_END = 12 * MHW_NB };
+#define MHW_FORCE_WRENCH 0x100               /* g_fterms: a wrench row is staged (beside the MH_FORCE_* bits of the stored terms) */
+__shared__ double gf[F_END];
+__shared__ int g_fterms;
+#endif
 
 #define MHW_FN __device__ __noinline__
 // (measured with tools/variants.sh: the impulse application / constraint-velocity update, the island search and
@@ -573,8 +584,60 @@ MH_DEV void integrate_positions(double hh) {
   }
   wave_sync();
 }
+#if MHW_FORCES
+// The same with the scene's recurrent forces and the caller's wrench (Simulator::precalc_fwd_dyn, Simulator.cpp:319-350: accumulators cleared, recurrent
+// forces, then the controller, once per mini-step): positions are this mini-step's, v and omega still its starting velocities.  Terms accumulate in the
+// canonical order gravity, Stokes drag (StokesDragForce.cpp:39-44), damping (DampingForce.cpp:32-51: velocities into the body frame, the wrench back),
+// caller wrench; an absent term is left out, not added as zero.  Every operation rounds on its own; world axes at the COM throughout.
+MH_DEV void integrate_velocities_forced(double h, int ft) {
+  const int lane = lane_id();
+  compute_xinv();
+  if (lane < gi[I_NB]) {
+    const int b = lane;
+    const double m = gd[D_MASS + b];
+    V3 F = v3(gd[D_GRAV] * m, gd[D_GRAV + 1] * m, gd[D_GRAV + 2] * m);
+    V3 T = v3(0.0, 0.0, 0.0);
+    bool has_t = false;
+    const V3 v = Vl(b), w = Wa(b);
+    if (ft & MH_FORCE_STOKES) {
+      F = F + v * (-gf[F_SB + b]);
+      T = w * (-gf[F_SBA + b]); has_t = true;
+    }
+    if (ft & MH_FORCE_DAMPING) {
+      double R[9]; rot(b, R);                                      // the rotation inertia_world() formed Jw from: same function, same quaternion
+      const V3 vi = v3((R[0]*v.x + R[3]*v.y) + R[6]*v.z, (R[1]*v.x + R[4]*v.y) + R[7]*v.z, (R[2]*v.x + R[5]*v.y) + R[8]*v.z);
+      const V3 wi = v3((R[0]*w.x + R[3]*w.y) + R[6]*w.z, (R[1]*w.x + R[4]*w.y) + R[7]*w.z, (R[2]*w.x + R[5]*w.y) + R[8]*w.z);
+      const V3 fb = vi * (-(gf[F_KL + b] + norm(vi) * gf[F_KLSQ + b]));
+      const V3 tb = wi * (-(gf[F_KA + b] + norm(wi) * gf[F_KASQ + b]));
+      const V3 fw = v3((R[0]*fb.x + R[1]*fb.y) + R[2]*fb.z, (R[3]*fb.x + R[4]*fb.y) + R[5]*fb.z, (R[6]*fb.x + R[7]*fb.y) + R[8]*fb.z);
+      const V3 tw = v3((R[0]*tb.x + R[1]*tb.y) + R[2]*tb.z, (R[3]*tb.x + R[4]*tb.y) + R[5]*tb.z, (R[6]*tb.x + R[7]*tb.y) + R[8]*tb.z);
+      F = F + fw;
+      T = has_t ? T + tw : tw; has_t = true;
+    }
+    if (ft & MHW_FORCE_WRENCH) {
+      const double* r = gf + F_WR + 6*b;
+      F = F + v3(r[0], r[1], r[2]);
+      const V3 tq = v3(r[3], r[4], r[5]);
+      T = has_t ? T + tq : tq; has_t = true;
+    }
+    const V3 xdd = F / m;
+    const double* Jw = gd + D_JW + 9*b;
+    const V3 Jww = v3((Jw[0]*w.x + Jw[1]*w.y) + Jw[2]*w.z, (Jw[3]*w.x + Jw[4]*w.y) + Jw[5]*w.z, (Jw[6]*w.x + Jw[7]*w.y) + Jw[8]*w.z);
+    const V3 tau = has_t ? T - cross(w, Jww) : -cross(w, Jww);
+    const double* Ji = gd + D_XINV + 10*b + 1;
+    const V3 wd = v3((Ji[0]*tau.x + Ji[1]*tau.y) + Ji[2]*tau.z, (Ji[3]*tau.x + Ji[4]*tau.y) + Ji[5]*tau.z, (Ji[6]*tau.x + Ji[7]*tau.y) + Ji[8]*tau.z);
+    const V3 vn = v + xdd * h, wn = w + wd * h;
+    gd[D_ST + 13*b+7] = vn.x; gd[D_ST + 13*b+8] = vn.y; gd[D_ST + 13*b+9] = vn.z;
+    gd[D_ST + 13*b+10] = wn.x; gd[D_ST + 13*b+11] = wn.y; gd[D_ST + 13*b+12] = wn.z;
+  }
+  wave_sync();
+}
+#endif
 // forward dynamics + velocity integration (TSS:173-192; GravityForce.cpp:33-69)
 MH_DEV void integrate_velocities(double h) {
+#if MHW_FORCES
+  { const int ft = uni(g_fterms); if (ft != 0) { integrate_velocities_forced(h, ft); return; } }   // no term at all: the text below, as it was
+#endif
   const int lane = lane_id();
   compute_xinv();
   if (lane < gi[I_NB]) {
@@ -1678,7 +1741,11 @@ MH_DEV bool world_step(double dt) {                                // TSS:52-111
 __global__ __launch_bounds__(64, MHW_WAVES_PER_SIMD)
 void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nsteps, double* __restrict__ state,
                      mh_world_aux* __restrict__ aux, double* __restrict__ traj, int nmax, double* __restrict__ lu_ws, int ka,
-                     unsigned long long* __restrict__ prof, const int* __restrict__ ids)
+                     unsigned long long* __restrict__ prof, const int* __restrict__ ids
+#if MHW_FORCES
+                     , const mh_world_forces* __restrict__ frc, const double* __restrict__ wrench, int wrows   // stored terms (or NULL), rows x B x nb x 6 wrench (or NULL)
+#endif
+                     )
 {
   const int w = ids ? ids[blockIdx.x] : (int)blockIdx.x;      // ids: a subset of the batch in its own launch (mh_world_batch_step_ids)
   if ((unsigned)w >= (unsigned)B) return;                     // B: the worlds of the BATCH (an id outside it is ignored, never dereferenced)
@@ -1711,6 +1778,16 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
     gd[D_PEPS + lane] = sc.cp_epsilon[lane]; gd[D_PCOMP + lane] = sc.cp_compliance[lane];
     gi[I_PNK + lane] = sc.cp_nk[lane]; gi[I_PEN + lane] = sc.pair_enabled[lane];
   }
+#if MHW_FORCES
+  { const int ft = frc ? frc->terms : 0;
+    if (lane < nb) {
+      const bool st = (ft & MH_FORCE_STOKES) != 0, dm = (ft & MH_FORCE_DAMPING) != 0;
+      gf[F_SB + lane] = st ? frc->stokes_b[lane] : 0.0; gf[F_SBA + lane] = st ? frc->stokes_b_ang[lane] : 0.0;
+      gf[F_KL + lane] = dm ? frc->damp_kl[lane] : 0.0; gf[F_KA + lane] = dm ? frc->damp_ka[lane] : 0.0;
+      gf[F_KLSQ + lane] = dm ? frc->damp_klsq[lane] : 0.0; gf[F_KASQ + lane] = dm ? frc->damp_kasq[lane] : 0.0;
+    }
+    if (lane == 0) g_fterms = (ft & (MH_FORCE_STOKES | MH_FORCE_DAMPING)) | (wrench ? MHW_FORCE_WRENCH : 0); }
+#endif
   mh_world_aux* a = aux + w;
   if (lane == 0) {
     gd[D_MINSTEP] = sc.min_step_size; gd[D_THRESH] = sc.contact_dist_thresh; gd[D_CSTABEPS] = sc.cstab_eps; gd[D_TIME] = a->time;
@@ -1739,6 +1816,13 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
   wave_sync();
   bool dead = thrown();                                       // a world whose handler threw in an earlier launch is not stepped again
   for (int s = 0; s < nsteps; s++) {
+#if MHW_FORCES
+    if (wrench && !dead && (s == 0 || wrows > 1)) {            // this step's wrench row of THIS world (its index in the batch, also under ids): rows == 1 holds row 0
+      wave_sync();
+      if (lane < 6 * nb) gf[F_WR + lane] = wrench[((size_t)(wrows > 1 ? s : 0) * B + w) * (size_t)(6 * nb) + lane];
+      wave_sync();
+    }
+#endif
     if (!dead) dead = world_step(dt);
     if (traj) {
       wave_sync();

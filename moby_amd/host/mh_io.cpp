@@ -17,6 +17,7 @@
 #include <strings.h>
 #include <vector>
 #include "../../include/moby_hip_io.h"
+#include "../../include/moby_hip_io_forces.h"
 
 namespace {
 
@@ -451,9 +452,15 @@ extern "C" {
 
 const char* mh_io_last_error(void) { return g_err; }
 
-int mh_io_load_xml(const char* path, mh_io_scene* out)
+}  // extern "C"
+
+namespace {
+struct DampGains { std::string body; double kl = 0.0, ka = 0.0, klsq = 0.0, kasq = 0.0; };
+// forces == NULL: mh_io_load_xml (gravity is the one recurrent force it takes); otherwise mh_io_load_xml_forces
+int load_xml_scene(const char* path, mh_io_scene* out, mh_world_forces* forces)
 {
   if (!path || !out) return fail("null argument");
+  if (forces) std::memset(forces, 0, sizeof(*forces));
   xmlDoc* doc = xmlReadFile(path, nullptr, XML_PARSE_NONET | XML_PARSE_NOERROR | XML_PARSE_NOWARNING);
   if (!doc) return fail("cannot parse %s", path);
   struct Guard { xmlDoc* d; ~Guard() { xmlFreeDoc(d); } } guard{doc};
@@ -491,6 +498,27 @@ int mh_io_load_xml(const char* path, mh_io_scene* out)
   std::map<std::string, std::vector<double> > gravs;
   { std::vector<xmlNode*> v; collect(root, "GravityForce", v);
     for (xmlNode* n : v) { const Attrs a = attrs_of(n); std::vector<double> g = numbers(a.str("accel")); if (g.size() != 3) return fail("GravityForce %s: bad accel", a.str("id").c_str()); gravs[a.str("id")] = g; } }
+  // ---- Stokes drag (StokesDragForce.cpp:68-85) and damping (DampingForce.cpp:115-175): read by mh_io_load_xml_forces only ----
+  std::map<std::string, std::pair<double, double> > stokes;
+  std::map<std::string, std::vector<DampGains> > damps;
+  if (forces) {
+    std::vector<xmlNode*> v; collect(root, "StokesDragForce", v);
+    for (xmlNode* n : v) { const Attrs a = attrs_of(n);
+      stokes[a.str("id")] = std::make_pair(a.has("drag-b") ? std::atof(a.str("drag-b").c_str()) : 0.0, a.has("drag-b-ang") ? std::atof(a.str("drag-b-ang").c_str()) : 0.0); }
+    v.clear(); collect(root, "DampingForce", v);
+    for (xmlNode* n : v) { const Attrs a = attrs_of(n); std::vector<DampGains>& gs = damps[a.str("id")];
+      for (xmlNode* c = n->children; c; c = c->next) {
+        if (c->type != XML_ELEMENT_NODE || strcmp((const char*)c->name, "Gains") != 0) continue;
+        const Attrs ca = attrs_of(c); DampGains g;
+        if (!ca.has("body-id")) return fail("DampingForce %s: Gains without body-id", a.str("id").c_str());
+        g.body = ca.str("body-id");
+        if (ca.has("klinear")) g.kl = std::atof(ca.str("klinear").c_str());
+        if (ca.has("kangular")) g.ka = std::atof(ca.str("kangular").c_str());
+        if (ca.has("klinear-sq")) g.klsq = std::atof(ca.str("klinear-sq").c_str());
+        if (ca.has("kangular-sq")) g.kasq = std::atof(ca.str("kangular-sq").c_str());
+        gs.push_back(g);
+      } }
+  }
   // ---- collision detection plugin: only the rimless wheel's ----
   std::map<std::string, std::string> plugins;
   { std::vector<xmlNode*> v; collect(root, "CollisionDetectionPlugin", v);
@@ -562,6 +590,7 @@ int mh_io_load_xml(const char* path, mh_io_scene* out)
   }
   std::vector<std::string> dyn; std::string ground; std::vector<CP> cps; std::vector<std::pair<std::string, std::string> > disabled;
   bool have_g = false; double g[3] = {0, 0, 0};
+  int last_kind = -1; std::string stokes_id, damp_id;        // the simulator's list must read gravity, Stokes drag, damping: the order the stepper accumulates in
   for (xmlNode* c = sim->children; c; c = c->next) {
     if (c->type != XML_ELEMENT_NODE) continue;
     const Attrs ca = attrs_of(c); const char* nm = (const char*)c->name;
@@ -572,8 +601,20 @@ int mh_io_load_xml(const char* path, mh_io_scene* out)
       else { if (!ground.empty()) return fail("more than one disabled body"); ground = it->first; }
     } else if (strcmp(nm, "RecurrentForce") == 0) {
       auto it = gravs.find(ca.str("recurrent-force-id"));
+      if (it == gravs.end() && forces) {                                                // Simulator.cpp:921-951: pushed onto every body, in the order listed
+        const std::string rid = ca.str("recurrent-force-id");
+        const int kind = stokes.count(rid) ? 1 : (damps.count(rid) ? 2 : -1);
+        if (kind < 0) return fail("simulator: unknown recurrent force %s (GravityForce, StokesDragForce and DampingForce are supported)", rid.c_str());
+        if (kind < last_kind) return fail("simulator: recurrent forces must be listed in the order gravity, Stokes drag, damping (%s comes too late)", rid.c_str());
+        if (kind == 1) { if (!stokes_id.empty()) return fail("more than one Stokes drag force"); stokes_id = rid; }
+        else { if (!damp_id.empty()) return fail("more than one damping force"); damp_id = rid; }
+        last_kind = kind;
+        continue;
+      }
       if (it == gravs.end()) return fail("simulator: only GravityForce recurrent forces are supported (%s)", ca.str("recurrent-force-id").c_str());
       if (have_g) return fail("more than one gravity force");
+      if (last_kind > 0) return fail("simulator: recurrent forces must be listed in the order gravity, Stokes drag, damping (%s comes too late)", ca.str("recurrent-force-id").c_str());
+      last_kind = 0;
       have_g = true; for (int i = 0; i < 3; i++) g[i] = it->second[i];
     } else if (strcmp(nm, "DisabledPair") == 0) disabled.push_back(std::make_pair(ca.str("object1-id"), ca.str("object2-id")));
     else if (strcmp(nm, "ContactParameters") == 0) {                                   // ContactParameters.cpp:46-135
@@ -623,6 +664,21 @@ int mh_io_load_xml(const char* path, mh_io_scene* out)
     for (int i = 0; i < 9; i++) sc.plane_R[i] = R[i];
     for (int i = 0; i < 3; i++) sc.plane_o[i] = G.x[i] + it->second.o[i];
   }
+  if (forces) {
+    if (!stokes_id.empty()) {
+      forces->terms |= MH_FORCE_STOKES;
+      for (int b = 0; b < nb; b++) { forces->stokes_b[b] = stokes[stokes_id].first; forces->stokes_b_ang[b] = stokes[stokes_id].second; }
+    }
+    if (!damp_id.empty()) {                              // a body without a Gains child has zero gains and still carries the term (DampingForce.cpp:54-67)
+      forces->terms |= MH_FORCE_DAMPING;
+      for (const DampGains& dg : damps[damp_id]) {
+        auto bi = index.find(dg.body);
+        if (bi == index.end() || bi->second >= nb) return fail("DampingForce %s: Gains names %s, which is not an enabled body of the simulator", damp_id.c_str(), dg.body.c_str());
+        const int b = bi->second;
+        forces->damp_kl[b] = dg.kl; forces->damp_ka[b] = dg.ka; forces->damp_klsq[b] = dg.klsq; forces->damp_kasq[b] = dg.kasq;
+      }
+    }
+  }
   const int ntot = nb + sc.has_ground;
   auto pidx = [&](int i, int j) { if (i > j) std::swap(i, j); return i * ntot - (i * (i + 1)) / 2 + (j - i - 1); };
   for (const CP& p : cps) {
@@ -636,6 +692,17 @@ int mh_io_load_xml(const char* path, mh_io_scene* out)
   }
   if (xmlNode* drv = first(root, "DRIVER")) { const Attrs da = attrs_of(drv); if (da.has("step-size")) out->step_size = std::atof(da.str("step-size").c_str()); }
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mh_io_load_xml(const char* path, mh_io_scene* out) { return load_xml_scene(path, out, nullptr); }
+
+int mh_io_load_xml_forces(const char* path, mh_io_scene* out, mh_world_forces* forces)
+{
+  if (!forces) return fail("null argument");
+  return load_xml_scene(path, out, forces);
 }
 
 int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double* qd0, double* step_size)

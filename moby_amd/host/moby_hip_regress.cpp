@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 #include <sstream>
-#include "../../include/moby_hip_io.h"
+#include "../../include/moby_hip_io_forces.h"
 #include "../../include/moby_hip_artic.h"
 
 int main(int argc, char** argv)
@@ -48,8 +48,8 @@ int main(int argc, char** argv)
     }
   }
   if (!(step_size > 0.0 && step_size < 1.0) || B < 1 || chunk < 1) { std::cerr << "regress: bad options" << std::endl; return -1; }
-  mh_io_scene io;
-  if (mh_io_load_xml(argv[2], &io) != 0) {
+  mh_io_scene io; mh_world_forces forces;                         // the scene's Stokes drag / damping, if it lists any (moby_hip_io_forces.h)
+  if (mh_io_load_xml_forces(argv[2], &io, &forces) != 0) {
     const std::string why = mh_io_last_error();
     mh_io_artic ar; double q0[MH_ARTIC_MAX_JOINTS], qd0[MH_ARTIC_MAX_JOINTS], file_dt = 0.0;
     if (mh_io_load_xml_artic(argv[2], &ar, q0, qd0, &file_dt) != 0) {
@@ -117,7 +117,7 @@ int main(int argc, char** argv)
     { double tt = t_now; unsigned long it = iter;
       while (n < chunk) { n++; it++; tt += step_size; if (it >= max_iter || tt > max_time) break; } }
     const clock_t pre = clock();
-    if (mh_world_step_batch(&io.scene, B, step_size, n, st.data(), aux.data(), traj.data()) != MH_OK) { std::cerr << "regress: " << mh_last_error() << std::endl; return -1; }
+    if (mh_world_step_batch_forces(&io.scene, &forces, B, step_size, n, st.data(), aux.data(), traj.data()) != MH_OK) { std::cerr << "regress: " << mh_last_error() << std::endl; return -1; }
     total_t += (clock() - pre) / (double)CLOCKS_PER_SEC;
     for (int s = 0; s < n; s++) {
       mh_io_format_row(t_now, row.data(), nb, buf, (int)sizeof(buf));

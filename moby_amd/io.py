@@ -30,6 +30,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.mh_io_load_xml.restype = ctypes.c_int
         lib.mh_io_load_xml.argtypes = [ctypes.c_char_p, ctypes.POINTER(mh_io_scene)]
+        lib.mh_io_load_xml_forces.restype = ctypes.c_int
+        lib.mh_io_load_xml_forces.argtypes = [ctypes.c_char_p, ctypes.POINTER(mh_io_scene), ctypes.POINTER(S.mh_world_forces)]
         lib.mh_io_last_error.restype = ctypes.c_char_p
         lib.mh_io_format_row.restype = ctypes.c_int
         lib.mh_io_format_row.argtypes = [ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
@@ -44,11 +46,23 @@ class SceneError(RuntimeError):
     pass
 
 
+def load_xml_forces(path):
+    """load_xml for a scene that may list <StokesDragForce> / <DampingForce> among the simulator's recurrent forces (include/moby_hip_io_forces.h):
+    -> (mh_scene, state, body ids, step size, mh_world_forces); forces.terms == 0 when it lists none."""
+    forces = S.mh_world_forces()
+    return _load_xml(path, forces) + (forces,)
+
+
 def load_xml(path):
     """-> (mh_scene, state (1, nb*13), body ids (enabled bodies in id order, then the ground), step size)."""
+    return _load_xml(path, None)
+
+
+def _load_xml(path, forces):
     lib = load()
     io = mh_io_scene()
-    if lib.mh_io_load_xml(os.fsencode(path), ctypes.byref(io)) != 0:
+    rc = lib.mh_io_load_xml(os.fsencode(path), ctypes.byref(io)) if forces is None else lib.mh_io_load_xml_forces(os.fsencode(path), ctypes.byref(io), ctypes.byref(forces))
+    if rc != 0:
         raise SceneError(lib.mh_io_last_error().decode("utf-8", "replace"))
     sc = S.mh_scene()
     ctypes.memmove(ctypes.addressof(sc), ctypes.addressof(io.scene), ctypes.sizeof(S.mh_scene))

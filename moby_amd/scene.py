@@ -71,6 +71,36 @@ AUX_DTYPE = np.dtype([
 assert AUX_DTYPE.itemsize == ctypes.sizeof(mh_world_aux), (AUX_DTYPE.itemsize, ctypes.sizeof(mh_world_aux))
 
 
+MH_FORCE_STOKES, MH_FORCE_DAMPING = 1, 2
+
+
+class mh_world_forces(ctypes.Structure):
+    """Recurrent forces of a scene (include/moby_hip.h): one set of coefficients for all worlds of a batch."""
+    _fields_ = [("terms", ctypes.c_int),
+                ("stokes_b", ctypes.c_double * MH_MAX_BODIES), ("stokes_b_ang", ctypes.c_double * MH_MAX_BODIES),
+                ("damp_kl", ctypes.c_double * MH_MAX_BODIES), ("damp_ka", ctypes.c_double * MH_MAX_BODIES),
+                ("damp_klsq", ctypes.c_double * MH_MAX_BODIES), ("damp_kasq", ctypes.c_double * MH_MAX_BODIES)]
+
+
+def make_forces(nb, stokes=None, damping=None):
+    """``mh_world_forces`` for a scene of nb bodies.  stokes: (b, b_ang) as ``<StokesDragForce drag-b drag-b-ang>`` gives them (every body
+    alike), or a pair of per-body sequences; damping: (klinear, kangular, klinear_sq, kangular_sq) for every body, or a sequence of such
+    4-tuples per body, as the ``<Gains>`` children of a ``<DampingForce>`` state them.  A term that is None is absent."""
+    f = mh_world_forces()
+    if stokes is not None:
+        f.terms |= MH_FORCE_STOKES
+        b, ba = (np.broadcast_to(np.asarray(x, dtype=np.float64), (nb,)) for x in stokes)
+        for k in range(nb):
+            f.stokes_b[k] = b[k]
+            f.stokes_b_ang[k] = ba[k]
+    if damping is not None:
+        f.terms |= MH_FORCE_DAMPING
+        g = np.broadcast_to(np.asarray(damping, dtype=np.float64), (nb, 4))
+        for k in range(nb):
+            f.damp_kl[k], f.damp_ka[k], f.damp_klsq[k], f.damp_kasq[k] = g[k]
+    return f
+
+
 def rpy_to_quat(roll, pitch, yaw):
     """Quatd::rpy as Ravelin forms it (half-angle products, ZYX), x y z w.  The XML readers turn every ``rpy`` attribute
     into a quaternion first (XMLTree.cpp / RigidBody.cpp:201-210, Primitive.cpp:273-279)."""

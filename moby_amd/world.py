@@ -16,14 +16,18 @@ from . import scene as S
 class WorldBatch:
     """B worlds of one scene; numpy host arrays in/out (copies through the library)."""
 
-    def __init__(self, scene, state, aux=None, seed=1):
+    def __init__(self, scene, state, aux=None, seed=1, forces=None):
         self.scene = scene
         self.state = np.ascontiguousarray(state, dtype=np.float64)
         self.B = self.state.shape[0]
         assert self.state.shape[1] == scene.nb * S.MH_BODY_STATE
         self.aux = S.new_aux(self.B, seed) if aux is None else aux
+        self.forces = forces       # S.mh_world_forces (S.make_forces) or None: the scene's recurrent forces
 
-    def step(self, dt, nsteps=1, want_traj=False):
+    def step(self, dt, nsteps=1, want_traj=False, wrench=None):
+        """wrench: (B, nb, 6) or (rows >= nsteps, B, nb, 6) host array (fx fy fz tx ty tz per world and body), or None."""
+        if self.forces is not None or wrench is not None:
+            return self._step_forced(dt, nsteps, want_traj, wrench)
         lib = _lib.load()
         traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
         rc = lib.mh_world_step_batch(ctypes.addressof(self.scene), self.B, float(dt), int(nsteps),
@@ -31,6 +35,28 @@ class WorldBatch:
                                      None if traj is None else traj.ctypes.data)
         _lib.check(rc)
         return traj
+
+    def _step_forced(self, dt, nsteps, want_traj, wrench):
+        """forces alone: the host convenience mh_world_step_batch_forces; with a wrench: the same round trip through a device batch, which is what
+        takes one (a DEVICE array)"""
+        if wrench is None:
+            traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
+            _lib.check(_lib.load().mh_world_step_batch_forces(ctypes.addressof(self.scene), ctypes.addressof(self.forces), self.B, float(dt), int(nsteps),
+                                                              self.state.ctypes.data, self.aux.ctypes.data, None if traj is None else traj.ctypes.data))
+            return traj
+        import torch
+        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux)
+        try:
+            if self.forces is not None:
+                dev.set_forces(self.forces)
+            traj = torch.zeros((self.B, nsteps, self.scene.nb, 7), dtype=torch.float64, device="cuda") if want_traj else None
+            w = None if wrench is None else torch.as_tensor(np.ascontiguousarray(wrench, dtype=np.float64), device="cuda")
+            dev.step(dt, nsteps, traj_ptr=None if traj is None else traj.data_ptr(), wrench=w)
+            self.state[...], aux = dev.download()
+            self.aux[...] = aux
+        finally:
+            dev.close()
+        return None if traj is None else traj.cpu().numpy()
 
     def regress_rows(self):
         """(B, 1 + 7*nb): current_time followed by the Euler coordinates of every body."""
@@ -52,12 +78,48 @@ class WorldBatchDevice:
         aux = S.new_aux(self.B, seed) if aux is None else np.ascontiguousarray(aux)      # aux given: resume from a checkpoint
         _lib.check(lib.mh_world_batch_upload(self.handle, st.ctypes.data, aux.ctypes.data))
 
-    def step(self, dt, nsteps=1, stream=None, traj_ptr=None):
-        _lib.check(_lib.load().mh_world_batch_step(self.handle, stream, float(dt), int(nsteps), traj_ptr))
+    def set_forces(self, forces):
+        """The scene's recurrent forces (S.mh_world_forces from S.make_forces / io.load_xml_forces; None clears them): every later step honours them."""
+        _lib.check(_lib.load().mh_world_batch_set_forces(self.handle, None if forces is None else ctypes.addressof(forces)))
 
-    def step_ids(self, dt, nsteps, ids_dev_ptr, count, stream=None):
-        """nsteps of the worlds listed in a DEVICE int32 array (e.g. a torch tensor's data_ptr()) on `stream` (mh_world_batch_step_ids)."""
-        _lib.check(_lib.load().mh_world_batch_step_ids(self.handle, stream, float(dt), int(nsteps), ctypes.c_void_p(int(ids_dev_ptr)), int(count)))
+    def _wrench_args(self, wrench, rows):
+        """(device pointer, rows) of a wrench schedule: a float64 torch tensor on the batch's device shaped (B, nb, 6) or (rows, B, nb, 6), or a raw
+        device pointer with `rows` given (rows x B x nb x 6 doubles)."""
+        if hasattr(wrench, "data_ptr"):
+            nb = self.scene.nb
+            if not (wrench.is_cuda and wrench.is_contiguous() and str(wrench.dtype) == "torch.float64"):
+                raise ValueError("wrench: a contiguous float64 tensor on the device is needed")
+            shape = tuple(wrench.shape)
+            if shape == (self.B, nb, 6):
+                shape = (1,) + shape
+            if shape[1:] != (self.B, nb, 6) or (rows is not None and int(rows) != shape[0]):
+                raise ValueError("wrench: shape %s, expected ([rows,] %d, %d, 6)" % (tuple(wrench.shape), self.B, nb))
+            return ctypes.c_void_p(wrench.data_ptr()), shape[0]
+        return ctypes.c_void_p(int(wrench)), 1 if rows is None else int(rows)
+
+    def step(self, dt, nsteps=1, stream=None, traj_ptr=None, wrench=None, rows=None):
+        """wrench: per-world body wrenches for this launch (see _wrench_args; rows == 1 holds for the launch, rows >= nsteps is one row per step)."""
+        if wrench is None:
+            _lib.check(_lib.load().mh_world_batch_step(self.handle, stream, float(dt), int(nsteps), traj_ptr))
+            return
+        ptr, rows = self._wrench_args(wrench, rows)
+        _lib.check(_lib.load().mh_world_batch_step_wrench(self.handle, stream, float(dt), int(nsteps), traj_ptr, None, 0, ptr, rows))
+
+    def step_ids(self, dt, nsteps, ids_dev_ptr, count, stream=None, wrench=None, rows=None):
+        """nsteps of the worlds listed in a DEVICE int32 array (e.g. a torch tensor's data_ptr()) on `stream` (mh_world_batch_step_ids); with a
+        wrench, each listed world reads the schedule at its own index in the batch."""
+        if wrench is None:
+            _lib.check(_lib.load().mh_world_batch_step_ids(self.handle, stream, float(dt), int(nsteps), ctypes.c_void_p(int(ids_dev_ptr)), int(count)))
+            return
+        ptr, rows = self._wrench_args(wrench, rows)
+        _lib.check(_lib.load().mh_world_batch_step_wrench(self.handle, stream, float(dt), int(nsteps), None, ctypes.c_void_p(int(ids_dev_ptr)), int(count), ptr, rows))
+
+    def occupancy(self):
+        """resident workgroups per CU of the kernel this batch launches now (runtime query; the forced kernel once forces are stored)"""
+        n = _lib.load().mh_world_batch_occupancy(self.handle)
+        if n < 0:
+            _lib.check(n)
+        return n
 
     def download(self):
         st = np.zeros((self.B, self.scene.nb * S.MH_BODY_STATE))

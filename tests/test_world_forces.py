@@ -1,0 +1,173 @@
+"""Recurrent forces and per-world body wrenches of the many-worlds stepper (include/moby_hip.h: mh_world_forces, mh_world_batch_set_forces,
+mh_world_batch_step_wrench) without a GPU: the forced reference (tests/native/world_force_ref.cpp, a restatement of oracle::World::fwd_dyn /
+do_mini_step / step with the terms) pinned to the oracle -- with no terms it IS oracle_world_step_batch -- and to the recurrence written out in
+numpy; what the terms must do physically (hover, terminal velocity, the friction cone); the ctypes mirror and the argument checks of the new entry
+points.  The reference's ctypes face and the batches shared with the GPU tests live in tests/world_force_ref.py."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from moby_amd import scene as S
+from tests.world_force_ref import G, assert_aux_equal, cone_batch, hover_batch, reference
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="session")
+def force_ref():
+    return reference()
+
+
+# ---- pins ---------------------------------------------------------------------------------------------------------------------------------------
+PIN_A = {
+    "stack": lambda: (S.sphere_stack_scene(), S.sphere_stack_state(5), 0.01, 60),
+    "wheel": lambda: (S.rimless_wheel_scene(), S.rimless_wheel_state((0.24, 0.4)), 0.001, 300),
+    "box": lambda: (S.box_scene(mu_coulomb=0.1), S.box_state(w=(0.0, 10.0, 0.0)), 0.01, 100),
+    "ball": lambda: (S.bouncing_ball_scene(), np.tile(S.bouncing_ball_state(1), (2, 1)) + np.array([[0.0] * 13, [0.0, 0.7] + [0.0] * 11]), 0.025, 150),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PIN_A))
+def test_reference_without_terms_is_the_oracle(oracle, force_ref, name):
+    """pin A: no forces, terms == 0 and a NULL wrench step exactly as oracle_world_step_batch: states and whole aux records"""
+    sc, st0, dt, n = PIN_A[name]()
+    B = st0.shape[0]
+    st_o, aux_o = st0.copy(), S.new_aux(B)
+    oracle.world_step_batch(sc, st_o, aux_o, dt, n)
+    assert (aux_o["lcp_solves"] > 0).all()
+    for forces in (None, S.mh_world_forces()):
+        st_r, aux_r = st0.copy(), S.new_aux(B)
+        force_ref.step(sc, st_r, aux_r, dt, n, forces)
+        np.testing.assert_array_equal(st_r, st_o)
+        assert_aux_equal(aux_r, aux_o)
+        assert aux_r.tobytes() == aux_o.tobytes()
+
+
+def test_zero_coefficients_change_nothing_on_the_sphere_stack(oracle, force_ref):
+    """both terms present with all coefficients zero: v (-0) and R (R' v (-0)) add signed zeros only"""
+    sc, st0, dt, n = PIN_A["stack"]()
+    st_o, aux_o = st0.copy(), S.new_aux(5)
+    oracle.world_step_batch(sc, st_o, aux_o, dt, n)
+    st_r, aux_r = st0.copy(), S.new_aux(5)
+    force_ref.step(sc, st_r, aux_r, dt, n, S.make_forces(3, stokes=(0.0, 0.0), damping=(0.0, 0.0, 0.0, 0.0)))
+    np.testing.assert_array_equal(st_r, st_o)
+    assert_aux_equal(aux_r, aux_o)
+
+
+def test_stokes_and_wrench_follow_the_recurrence_bit_for_bit(force_ref):
+    """pin B: one free body, no ground: every step is one mini-step of h = dt and v += ((g m + v (-b)) + f) / m h, each operation rounded on its own"""
+    m, b, dt = 1.7, 0.45, 0.01
+    sc = S.make_scene([0.5], [m], (0.3, -G, 0.1))
+    f = np.array([0.7, 2.5, -1.1])
+    wrench = np.zeros((1, 1, 6)); wrench[0, 0, :3] = f
+    st = np.zeros((1, 13)); st[0, 6] = 1.0; st[0, 7:10] = (0.4, -0.2, 0.9)
+    v = st[0, 7:10].copy()
+    g = np.array([sc.gravity[k] for k in range(3)])
+    aux = S.new_aux(1)
+    forces = S.make_forces(1, stokes=(b, 0.0))
+    for _ in range(20):
+        force_ref.step(sc, st, aux, dt, 1, forces, wrench)
+        F = g * m
+        F = F + v * (-b)
+        F = F + f
+        v = v + (F / m) * dt
+        np.testing.assert_array_equal(st[0, 7:10], v)
+    assert aux["mini_steps"][0] == 20 and aux["status"][0] == 0
+
+
+def test_a_wrench_that_cancels_gravity_leaves_the_velocities_untouched(force_ref):
+    """hover: f_y = -(g_y m_b) makes F_y = g m + (-(g m)) = 0 exactly, for every mass: 50 steps change no linear velocity by a bit"""
+    sc, st0, wrench = hover_batch()
+    st, aux = st0.copy(), S.new_aux(st0.shape[0])
+    force_ref.step(sc, st, aux, 0.01, 50, None, wrench)
+    v0 = st0.reshape(-1, sc.nb, 13)[:, :, 7:10]; v1 = st.reshape(-1, sc.nb, 13)[:, :, 7:10]
+    np.testing.assert_array_equal(v1, v0)
+    assert (aux["status"] == 0).all() and (aux["lcp_solves"] == 0).all()
+    assert np.abs(st - st0).max() > 1e-3                   # ... while the bodies drift and turn
+
+
+def test_terminal_velocity_under_stokes_drag(force_ref):
+    """m = 2, b = 20, h = 0.01: v <- 0.9 v + g h contracts to g m / b; after 400 steps 0.9^400 ~ 5e-19 of the start is left and the round-off of the
+    iteration sums to at most eps / (1 - 0.9) ~ 2e-15 relative: the bound 1e-13 is derived, not measured (measured: 6.7e-16)"""
+    m, b = 2.0, 20.0
+    sc = S.make_scene([0.5], [m], (0.0, -G, 0.0))
+    st = np.zeros((1, 13)); st[0, 6] = 1.0
+    aux = S.new_aux(1)
+    force_ref.step(sc, st, aux, 0.01, 400, S.make_forces(1, stokes=(b, 0.0)))
+    want = -G * m / b
+    rel = abs(st[0, 8] - want) / abs(want)
+    print("terminal velocity: relative error %.3g" % rel)
+    assert rel < 1e-13
+    assert st[0, 7] == 0.0 and st[0, 9] == 0.0
+
+
+def test_a_push_inside_the_friction_cone_does_not_move_the_box(force_ref):
+    """mu m g = 4.905 N: pushes of 0, 2 and 4 N leave the box where it is, 8 N slides it past x = 1 in a second"""
+    sc, st0, wrench = cone_batch()
+    st, aux = st0.copy(), S.new_aux(4)
+    force_ref.step(sc, st, aux, 0.01, 100, None, wrench)
+    print("friction cone: x =", st[:, 0])
+    assert np.abs(st[:3, 0]).max() < 1e-9
+    assert st[3, 0] > 1.0
+    assert (aux["status"] == 0).all()
+
+
+# ---- the C side ------------------------------------------------------------------------------------------------------------------------------
+def test_forces_mirror_has_the_c_struct_size(tmp_path):
+    src = tmp_path / "frc.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moby_hip.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %d %d %d\\n", sizeof(mh_world_forces), offsetof(mh_world_forces, stokes_b), offsetof(mh_world_forces, damp_kasq),\n'
+                   '  MH_FORCE_STOKES, MH_FORCE_DAMPING, MH_VERSION); return 0; }\n')
+    exe = str(tmp_path / "frc")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    F = S.mh_world_forces
+    assert got == [ctypes.sizeof(F), F.stokes_b.offset, F.damp_kasq.offset, S.MH_FORCE_STOKES, S.MH_FORCE_DAMPING, 102]
+
+
+def test_make_forces_fills_per_body_coefficients():
+    f = S.make_forces(3, stokes=(0.3, [0.1, 0.2, 0.3]), damping=[(1, 2, 3, 4), (5, 6, 7, 8), (0, 0, 0, 0)])
+    assert f.terms == S.MH_FORCE_STOKES | S.MH_FORCE_DAMPING
+    assert list(f.stokes_b)[:4] == [0.3, 0.3, 0.3, 0.0] and list(f.stokes_b_ang)[:3] == [0.1, 0.2, 0.3]
+    assert (f.damp_kl[1], f.damp_ka[1], f.damp_klsq[1], f.damp_kasq[1]) == (5.0, 6.0, 7.0, 8.0) and f.damp_kl[2] == 0.0
+    assert S.make_forces(2).terms == 0 and S.make_forces(2, damping=(1, 0, 0, 0)).terms == S.MH_FORCE_DAMPING
+
+
+def test_argument_validation_of_the_new_entry_points_without_gpu():
+    """values are checked before the batch is touched, so every refusal can be had without a device"""
+    from moby_amd import _lib
+    lib = _lib.load()
+    assert lib.mh_version() >= 102
+    err = lambda: lib.mh_last_error().decode()
+    f = S.make_forces(2, stokes=(0.1, 0.1))
+    f.terms |= 8
+    assert lib.mh_world_batch_set_forces(None, ctypes.addressof(f)) == _lib.MH_ERR_INVALID_ARG and "unknown bits" in err()
+    f = S.make_forces(2, damping=(0.1, float("nan"), 0.0, 0.0))
+    assert lib.mh_world_batch_set_forces(None, ctypes.addressof(f)) == _lib.MH_ERR_INVALID_ARG and "damp_ka[0] is not finite" in err()
+    f = S.make_forces(2, stokes=(float("inf"), 0.0))
+    assert lib.mh_world_batch_set_forces(None, ctypes.addressof(f)) == _lib.MH_ERR_INVALID_ARG and "stokes_b[0] is not finite" in err()
+    f = S.make_forces(2, stokes=(0.1, 0.0)); f.damp_kl[0] = float("nan")            # ... but a term that is not set is not looked at
+    assert lib.mh_world_batch_set_forces(None, ctypes.addressof(f)) == _lib.MH_ERR_INVALID_ARG and "null batch" in err()
+    assert lib.mh_world_batch_set_forces(None, None) == _lib.MH_ERR_INVALID_ARG and "null batch" in err()
+    buf = np.zeros(64)
+    step = lambda nsteps, traj, ids, rows: lib.mh_world_batch_step_wrench(None, None, 0.01, nsteps, traj, ids, 1, buf.ctypes.data, rows)
+    assert step(10, None, None, 0) == _lib.MH_ERR_INVALID_ARG and "rows = 0" in err()
+    assert step(10, None, None, -3) == _lib.MH_ERR_INVALID_ARG and "rows" in err()
+    assert step(10, None, None, 5) == _lib.MH_ERR_INVALID_ARG and "5 rows for 10 steps" in err()
+    assert step(10, buf.ctypes.data, buf.ctypes.data, 1) == _lib.MH_ERR_INVALID_ARG and "trajectory" in err()
+    assert step(-1, None, None, 1) == _lib.MH_ERR_INVALID_ARG and "negative" in err()
+    assert step(10, None, None, 1) == _lib.MH_ERR_INVALID_ARG and "null batch" in err()
+    assert step(10, None, None, 10) == _lib.MH_ERR_INVALID_ARG and "null batch" in err()
+    assert step(10, None, None, 12) == _lib.MH_ERR_INVALID_ARG and "null batch" in err()
+
+
+def test_cpp_adapter_takes_forces_and_a_wrench(tmp_path):
+    """MobyHipSimulator.h: set_forces + step_wrench(dt, wrench) build with plain g++ against the C ABI"""
+    src = tmp_path / "frc.cpp"
+    src.write_text('#include "MobyHipSimulator.h"\n'
+                   'void f(MobyHip::BatchedTimeSteppingSimulator& sim, const mh_world_forces& fr, const double* wrench_dev) {\n'
+                   '  sim.set_forces(fr); sim.step_wrench(0.01, wrench_dev); sim.step_wrench(0.01, NULL); sim.step_wrench(0.01, wrench_dev, 20, 20); sim.step(0.01, 0); sim.clear_forces(); }\n')
+    subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "moby_amd", "cpp"), str(src)])
