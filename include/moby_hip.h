@@ -65,6 +65,10 @@ typedef struct mh_lcp_opts {
 /* 100 * major + minor.  101: mh_impact_batch_lu_work / mh_big_batch_lu_work fill B x 4 doubles per call (100: B x 2) -- a caller built against the
  * two-column layout must check for >= 101 and size its buffer accordingly (#define MH_VERSION is what this header describes). */
 #define MH_VERSION 102   /* 102: recurrent forces and per-world body wrenches in the many-worlds stepper (mh_world_forces, mh_world_batch_set_forces / _step_wrench) */
+/* Box-sphere contacts between free bodies in the many-worlds stepper (mh_world_batch_create accepts scenes with such pairs enabled; "Box-sphere pairs"
+ * below) add no entry point and change no layout, so MH_VERSION stays 102; a caller that needs to know tests this macro, and at run time
+ * mh_world_batch_create's answer to such a scene (MH_ERR_INVALID_ARG from a library without the feature). */
+#define MH_WORLD_BOX_SPHERE 1
 int         mh_version(void);
 const char* mh_last_error(void);
 int         mh_device_count(void);
@@ -133,13 +137,42 @@ int mh_lcp_solve_batch(int kind, int B, int n,
  * ConstraintStabilization::stabilize (src/ConstraintStabilization.cpp:167).
  *
  * Scene scope of this build: up to MH_MAX_BODIES free rigid bodies with sphere,
- * box (against the plane only) or rimless-wheel spokes geometry plus one static
- * plane (the closed-form pairs of CCD.inl:804-886, 1164-1207 and of example/
+ * box (against the plane and against spheres) or rimless-wheel spokes geometry plus
+ * one static plane (the closed-form pairs of CCD.inl:804-886, 1164-1259 and of example/
  * rimless-wheel/coldet-plugin.cpp), gravity, per-pair ContactParameters; impact
  * models: Drumwright-Shell QP->LCP and, for islands whose contacts all have
  * mu-coulomb >= 100, the no-slip model (ImpactConstraintHandler.cpp:1009-1417).
  * Body ids are 0..nb-1 in the order the reference sorts them (by id string); the
  * ground plane, when present, has id nb.  Pair p enumerates (i<j) lexicographically.
+ *
+ * Box-sphere pairs.  A pair of two enabled bodies, one MH_GEOM_BOX and one MH_GEOM_SPHERE, may be enabled and is stepped.  Pair p = (i < j) keeps its
+ * bodies in id order everywhere; the box is the reference's geometry A of the CONTACT whichever body has the lower id (CCD.inl:15,26 swaps the
+ * arguments so that it is).  The frames are the bodies' own: box centre = the body's COM, box axes = the rotation of its quaternion (a box body has no
+ * primitive offset).  With c the sphere's centre in the box's frame, h the half lengths, R the radius, p = clamp(c, -h, h) (the fixed point of the
+ * reference's projected-gradient QP, BoxPrimitive.cpp:183-254), v = p - c:
+ *   contact          find_contacts_box_sphere (CCD.inl:1208-1259), created as (box, sphere): contact_geom1 = the box, contact_geom2 = the sphere, the
+ *                    normal points from the sphere towards the box.  If any |p_i| < h_i or |v| < R (every face and edge region, and every
+ *                    penetration): dist = -min(min_i(h_i - |p_i|), R - |v|), the sphere point stays c + v; otherwise (a vertex region) the sphere
+ *                    point is c + v R / |v| and dist = the distance between the two points.  None if dist > TOL.  dist > 0: the point is the
+ *                    midpoint of the two points, the normal their difference box - sphere normalised, or -- when that is no longer than
+ *                    NEAR_ZERO -- the unit vector from the sphere's centre to p.  dist <= 0: the sphere point and that unit vector.  A centre
+ *                    inside the box gives v = 0 and a NaN normal, as in the reference; there is no fallback.  A pair gives at most one contact.
+ *   signed distance  BoxPrimitive::calc_signed_dist for a sphere (BoxPrimitive.cpp:256-276, 788-836), a DIFFERENT function: the closest-point
+ *                    distance of c (the negative interior depth when c is inside) minus R; box point = p, sphere point = centre + v (R + min(dist, 0))
+ *                    / |v|, the centre if |v| = 0.  With the sphere as the lower id, SpherePrimitive::calc_signed_dist(Primitive)
+ *                    (SpherePrimitive.cpp:282-290) forwards to the box with the point arguments swapped, so the points stay with their bodies:
+ *                    the first point is on body i, the second on body j.  The contact list reads THIS distance for its
+ *                    < contact_dist_thresh test (ConstraintSimulator.cpp:488-537) and then the contact function's own for the contact.
+ *   conservative     the pair contains a sphere: the sphere rule (CCD.cpp:121-235).  dist > NEAR_ZERO -> dist / max(0, calc_max_dist(i, -n0, rmax_i)
+ *   advancement      + calc_max_dist(j, n0, rmax_j)), n0 from the signed-distance function's two points, j to i; rmax of the box is its full
+ *                    diagonal, of the sphere its radius.  dist <= NEAR_ZERO: the contact above with TOL = NEAR_ZERO, as for sphere pairs.
+ *   stabiliser       one row per pair: dist >= NEAR_ZERO -> the synthetic contact at body i's closest point with normal (pb - pa) / |pb - pa|;
+ *                    otherwise the contact above with TOL = NEAR_ZERO.  The line search reads the signed distance.
+ *   broad phase      the swept-bounds overlap test like any other pair; the box's bounding radius is its half diagonal.
+ * Canonical contact order is unchanged: pairs in pair-list order, a pair's contacts in generator order.  Such a scene steps through code objects of its
+ * own (mh_world_large_bsp.hip, mh_world_large_bsp_forces.hip: the large variant built with MHW_BSP); every other scene launches what it did.
+ * NOT built: box against box (mh_world_batch_create refuses an enabled box-box pair), static boxes among free bodies, and the pair in the
+ * large-world stepper (moby_hip_stack.h), which keeps its refusal.
  */
 #define MH_MAX_BODIES 8
 #define MH_MAX_PAIRS  36            /* C(MH_MAX_BODIES + 1, 2) */
@@ -148,8 +181,8 @@ int mh_lcp_solve_batch(int kind, int B, int n,
 #define MH_GEOM_SPOKES 1            /* rimless wheel: N point "spoke tips" at radius R in the body's x-z plane
                                        (example/rimless-wheel/coldet-plugin.cpp:104-137, params.h:4-6); it is
                                        only ever tested against the ground plane, and always (plugin :53-74) */
-#define MH_GEOM_BOX 2               /* BoxPrimitive, tested against the ground plane only (vertex-plane contacts,
-                                       CCD.inl:848-886); box-box / box-sphere pairs must be disabled */
+#define MH_GEOM_BOX 2               /* BoxPrimitive, tested against the ground plane (vertex-plane contacts, CCD.inl:848-886)
+                                       and against spheres ("Box-sphere pairs" above); box-box pairs must be disabled */
 #define MH_GEOM_PIN 3               /* a body point (geom_dim, body frame) held at the global origin by six frictionless contacts with
                                        normals +-y, +-z, +-x: the collision plugin of example/contact-constrained-pendulum
                                        (contact-constrained-pendulum-coldet-plugin.cpp:53-146).  Large-world stepper (moby_hip_stack.h)
@@ -248,6 +281,8 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    their own kernels; include/moby_hip_artic.h, mh_artic_model.npairs).
                                             key 14: articulated bodies with link spheres, boxes or sphere pairs stepped by the box-sphere kernels (1, for batches created
                                                    after it; default 0: their own kernels; include/moby_hip_artic.h, mh_artic_model.pair_kind).
+                                            key 15: world batches that would take the large variant stepped by its box-sphere build, mh_world_large_bsp*.hip (1, for
+                                                   batches created after it; default 0: only scenes with an enabled box-sphere pair; for A/B runs).
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);
@@ -323,7 +358,8 @@ typedef struct mh_world_forces {           /* recurrent forces of the scene: sha
  * forces, and any launch with a wrench, runs the FORCED code objects (mh_world_{small,wheel,large}_forces.hip: same variants, same launch bounds);
  * mh_world_batch_occupancy then reports those -- it reports the forced kernel while forces are STORED; a batch stepped with a wrench alone also launches the
  * forced object of its variant but is reported as the plain one (to query the forced kernel of such a batch, store any term, ask, and clear it).  The forced launch of _profile is the forced production kernel, which has no stamps: it steps the worlds
- * and reports zero cycles.  Not to be called while a launch of the batch is in flight. */
+ * and reports zero cycles.  Likewise a batch on the box-sphere build (an enabled box-sphere pair, or key 15): there is no stamped build of it, _profile launches
+ * the production object (plain or forced), steps the worlds and reports zero cycles; mh_world_batch_occupancy reports the object the batch launches.  Not to be called while a launch of the batch is in flight. */
 int mh_world_batch_set_forces(mh_world_batch* wb, const mh_world_forces* host);
 /* mh_world_batch_step (ids_dev == NULL: the whole batch, `count` ignored) or _step_ids (ids_dev: a DEVICE array of `count` world indices) with a wrench
  * schedule: wrench_dev is a DEVICE array of rows x B x nb x 6 doubles (fx fy fz tx ty tz; B = the worlds of the BATCH: a world reads the entries at its own

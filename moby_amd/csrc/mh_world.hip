@@ -8,6 +8,7 @@
 #include <algorithm>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
+#include "mh_world_bsp.h"
 
 namespace mh {
 // layouts of the constant tables of mh_world_common.h / mh_lcp_wave.h (checked by size in upload_tables)
@@ -32,11 +33,13 @@ hipError_t init_tables()
     }
   mh::Pow10TableH p10;
   for (int i = 0; i < 64; i++) p10.v[i] = std::pow(10.0, (double)(i - 32)); // LCP.cpp:285
-  const mh_world_variant* vs[6] = { mh_world_variant_small(), mh_world_variant_wheel(), mh_world_variant_large(),
-                                    mh_world_variant_small_prof(), mh_world_variant_wheel_prof(), mh_world_variant_large_prof() };     // (one copy of the tables per code object)
-  for (int i = 0; i < 6 && g_tables_err == hipSuccess; i++) g_tables_err = vs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
-  const mh_world_forced_variant* fs[3] = { mh_world_variant_small_forces(), mh_world_variant_wheel_forces(), mh_world_variant_large_forces() };
-  for (int i = 0; i < 3 && g_tables_err == hipSuccess; i++) g_tables_err = fs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  const mh_world_variant* vs[7] = { mh_world_variant_small(), mh_world_variant_wheel(), mh_world_variant_large(),
+                                    mh_world_variant_small_prof(), mh_world_variant_wheel_prof(), mh_world_variant_large_prof(),
+                                    mh_world_variant_large_bsp() };     // (one copy of the tables per code object)
+  for (int i = 0; i < 7 && g_tables_err == hipSuccess; i++) g_tables_err = vs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  const mh_world_forced_variant* fs[4] = { mh_world_variant_small_forces(), mh_world_variant_wheel_forces(), mh_world_variant_large_forces(),
+                                           mh_world_variant_large_bsp_forces() };
+  for (int i = 0; i < 4 && g_tables_err == hipSuccess; i++) g_tables_err = fs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   return g_tables_err;
 }
 hipError_t tables_for_current_device()
@@ -60,10 +63,9 @@ int check_scene(const mh_scene* sc)
       return fail(MH_ERR_INVALID_ARG, "body %d: geometry type %d is not built (sphere, spokes, box)", b, sc->geom_type[b]);
     if (sc->geom_type[b] == MH_GEOM_BOX) {
       if (!(sc->geom_dim[b][1] > 0.0) || !(sc->geom_dim[b][2] > 0.0)) return fail(MH_ERR_INVALID_ARG, "body %d: box edge lengths must be > 0", b);
-      for (int o = 0; o < sc->nb; o++) if (o != b) {
-        const int i = o < b ? o : b, j = o < b ? b : o;
-        if (sc->pair_enabled[i * ntot - (i * (i + 1)) / 2 + (j - i - 1)])
-          return fail(MH_ERR_INVALID_ARG, "bodies %d,%d: box-box / box-sphere contact is not built; disable the pair (only box-plane is)", i, j);
+      for (int o = b + 1; o < sc->nb; o++) if (sc->geom_type[o] == MH_GEOM_BOX) {
+        if (sc->pair_enabled[b * ntot - (b * (b + 1)) / 2 + (o - b - 1)])
+          return fail(MH_ERR_INVALID_ARG, "bodies %d,%d: box-box contact is not built; disable the pair (box-plane and box-sphere are)", b, o);
       }
     }
     if (sc->geom_type[b] == MH_GEOM_SPOKES) {
@@ -110,6 +112,7 @@ struct mh_world_batch {
   int B;
   int nmax;
   int variant;               // 0 small, 1 large, 2 wheel
+  bool bsp;                  // the large variant's box-sphere build (mh_world_large_bsp*.hip): an enabled box-sphere pair, or mh_debug_set(15, 1) at create
   mh_world_kernel kernel;
   int ph_count;
   mh_scene* d_scene;
@@ -179,7 +182,15 @@ int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
     if (!noslip && !box && scene->nb <= 4 && npairs <= 6 && scene->lcp_n_max > 0 && scene->lcp_n_max <= 56) { wb->variant = 0; wb->kernel = mh_world_variant_small()->kernel; }
     else if (noslip && !box && scene->nb <= 2 && npairs <= 3) { wb->variant = 2; wb->kernel = mh_world_variant_wheel()->kernel; }
     else { wb->variant = 1; wb->kernel = mh_world_variant_large()->kernel; }
-    wb->fkernel = (wb->variant == 0 ? mh_world_variant_small_forces() : wb->variant == 2 ? mh_world_variant_wheel_forces() : mh_world_variant_large_forces())->kernel;
+    // an enabled pair of a box and a sphere (two free bodies) needs the large variant's box-sphere build; every other scene takes what it took
+    bool bsp = false;
+    for (int i = 0; i < scene->nb; i++) for (int j = i + 1; j < scene->nb; j++) {
+      const int gi_ = scene->geom_type[i], gj_ = scene->geom_type[j];
+      if (((gi_ == MH_GEOM_BOX && gj_ == MH_GEOM_SPHERE) || (gi_ == MH_GEOM_SPHERE && gj_ == MH_GEOM_BOX)) && scene->pair_enabled[i * ntot - (i * (i + 1)) / 2 + (j - i - 1)]) bsp = true;
+    }
+    wb->bsp = wb->variant == 1 && (bsp || mh_g_debug_world_bsp != 0);
+    if (wb->bsp) wb->kernel = mh_world_variant_large_bsp()->kernel;
+    wb->fkernel = wb->bsp ? mh_world_variant_large_bsp_forces()->kernel : (wb->variant == 0 ? mh_world_variant_small_forces() : wb->variant == 2 ? mh_world_variant_wheel_forces() : mh_world_variant_large_forces())->kernel;
     wb->has_forces = false; wb->d_forces = nullptr;
   }
   wb->d_scene = nullptr; wb->d_state = nullptr; wb->d_aux = nullptr; wb->d_lu_ws = nullptr;
@@ -306,7 +317,8 @@ int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* ph
   // the PROFILE build of the batch's variant: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
   const mh_world_kernel kprof = (wb->variant == 0 ? mh_world_variant_small_prof() : wb->variant == 2 ? mh_world_variant_wheel_prof() : mh_world_variant_large_prof())->kernel;
   // (a batch with stored forces: the forced production kernel -- it steps the worlds under their forces and has no stamps, so every cycle count is 0)
-  if (wb->has_forces) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
+  // (a batch on the box-sphere build: likewise, there is no stamped build of it -- the production kernel steps the worlds, every cycle count is 0)
+  if (wb->has_forces || wb->bsp) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
   else
   hipLaunchKernelGGL(kprof, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
                      (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, (double*)nullptr, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, dprof, (const int*)nullptr);

@@ -1,0 +1,41 @@
+// The "large" variant of the many-worlds kernel (mh_world_wave.inc) with box-sphere contacts between free bodies (MHW_BSP): what a batch launches when its
+// scene enables at least one box-sphere pair, or under mh_debug_set(15, 1).  The constants are mh_world_large.hip's: <= 8 bodies, <= 36 pairs, <= 40 contacts,
+// <= 24 rows per island, every feature.  A translation unit of its own, so that the plain large kernels stay the code objects they were.
+#include <hip/hip_runtime.h>
+#include "../../include/moby_hip.h"
+#include "mh_host.h"
+#include "mh_world_bsp.h"
+#if defined(MH_FORCES_BUILD)   /* mh_world_large_bsp_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
+#define MHW_NS large_bsp_forces
+#define MHW_VARIANT_GETTER mh_world_variant_large_bsp_forces
+#define MHW_VARIANT_T mh_world_forced_variant
+#define MHW_FORCES 1
+#else
+#define MHW_NS large_bsp
+#define MHW_VARIANT_GETTER mh_world_variant_large_bsp
+#define MHW_VARIANT_T mh_world_variant
+#endif
+#define MHW_BSP 1
+#define MHW_NOSLIP 1
+#define MHW_BOX 1
+#define MHW_NB MH_MAX_BODIES
+#define MHW_MAX_PAIRS MH_MAX_PAIRS
+#define MHW_MAX_CONTACTS 40   /* the stabiliser lists one contact per candidate pair (up to 36), a box adds up to 8 */
+#define MHW_MAX_ROWS 24
+#define MHW_MAX_GROWS 24
+#define MHW_WAVES_PER_SIMD 2
+#include "mh_world_wave.inc"
+
+static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes)
+{
+  if (fric_bytes != sizeof(mh::FricTable) || pow10_bytes != sizeof(mh::Pow10Table)) return hipErrorInvalidValue;
+  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_fric), fric, fric_bytes);
+  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_pow10), pow10, pow10_bytes);
+  return e;
+}
+
+const MHW_VARIANT_T* MHW_VARIANT_GETTER()
+{
+  static const MHW_VARIANT_T v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
+  return &v;
+}

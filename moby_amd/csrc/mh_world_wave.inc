@@ -40,6 +40,8 @@
 // MHW_MAX_CONTACTS, MHW_MAX_ROWS, MHW_MAX_GROWS, MHW_WAVES_PER_SIMD and the feature switches MHW_NOSLIP
 // (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).  MHW_FORCES (1 in mh_world_*_forces.hip, undefined = 0 elsewhere) adds the scene's
 // recurrent forces and the caller's wrench to the forward dynamics; every line it adds sits under #if MHW_FORCES.
+// MHW_BSP (1 in mh_world_large_bsp*.hip, undefined = 0 elsewhere; needs MHW_BOX) adds box-sphere contacts between two free bodies (include/moby_hip.h,
+// "box-sphere pairs"); every line it adds or alters sits under #if MHW_BSP, so the other code objects compile from the text they had.
 #include "mh_world_common.h"
 
 #define MHW_NS_MAXC ((MHW_MAX_CONTACTS < 6) ? MHW_MAX_CONTACTS : 6)   /* contacts of a no-slip island */
@@ -257,6 +259,79 @@ MH_DEV bool collinear(V3 a, V3 b, V3 c) {                           // CompGeom.
          rel_equal((b.x-a.x)*(c.y-a.y), (b.y-a.y)*(c.x-a.x));
 }
 #endif
+#if MHW_BSP
+// ---- box-sphere pairs of two free bodies (include/moby_hip.h).  The box is the reference's geometry A whichever body has the lower id; the frames are
+// the bodies' own (box centre = COM, box axes = rot(box)).  Operation order = tests/native/world_boxsphere_ref.cpp (= artic_boxsphere_ref.cpp):
+// three-term sums as (a + b) + c.  Each function forms the box rotation once. ----
+MH_DEV bool is_sphere(int b) { return b < gi[I_NB] && gi[I_GEOM + b] == MH_GEOM_SPHERE; }
+MH_DEV bool is_ground(int b) { return b == gi[I_NB]; }
+MH_DEV bool bsp_pair(int a, int b, int& bx, int& sp) {
+  if (is_box(a) && is_sphere(b)) { bx = a; sp = b; return true; }
+  if (is_sphere(a) && is_box(b)) { bx = b; sp = a; return true; }
+  return false;
+}
+MH_DEV V3 mat_v(const double R[9], V3 p) { return v3((R[0]*p.x + R[1]*p.y) + R[2]*p.z, (R[3]*p.x + R[4]*p.y) + R[5]*p.z, (R[6]*p.x + R[7]*p.y) + R[8]*p.z); }
+MH_DEV V3 matT_v(const double R[9], V3 p) { return v3((R[0]*p.x + R[3]*p.y) + R[6]*p.z, (R[1]*p.x + R[4]*p.y) + R[7]*p.z, (R[2]*p.x + R[5]*p.y) + R[8]*p.z); }
+MH_DEV double clampd(double c, double h) { return (c < -h) ? -h : ((c > h) ? h : c); }
+// BoxPrimitive::calc_closest_points (BoxPrimitive.cpp:183-254; the QP's fixed point is the clamp) + find_contacts_box_sphere (CCD.inl:1208-1259)
+MH_DEV int bsp_contact(int bx, int sp, double TOL, V3& pt, V3& n, double& dist) {
+  double R[9]; rot(bx, R);
+  const V3 cb = X(bx), cS = X(sp);
+  const V3 c = matT_v(R, cS - cb);
+  const V3 h = v3(gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5);
+  const double Rs = gd[D_RADIUS + sp];
+  const V3 p = v3(clampd(c.x, h.x), clampd(c.y, h.y), clampd(c.z, h.z));
+  V3 u = p - c;
+  const double nrm = norm(u);
+  if (fabs(p.x) < h.x || fabs(p.y) < h.y || fabs(p.z) < h.z || nrm < Rs) {             // an OR: every face and edge region, and every penetration
+    const double b1 = h.y - fabs(p.y), b2 = h.z - fabs(p.z);
+    const double b12 = (b2 < b1) ? b2 : b1, b0 = h.x - fabs(p.x);
+    const double bd = (b12 < b0) ? b12 : b0;
+    const double rn = Rs - nrm;
+    dist = -((rn < bd) ? rn : bd);
+  } else {                                                                             // a vertex region: the sphere point goes to the surface
+    u = u * (Rs / nrm);
+    dist = norm((c + u) - p);
+  }
+  if (dist > TOL) return 0;
+  const V3 ug = mat_v(R, u);
+  const V3 sg = cS + ug;
+  bool own = false;
+  if (dist > 0.0) {
+    const V3 pg = cb + mat_v(R, p);
+    const V3 nd = pg - sg;
+    const double nl = norm(nd);
+    pt = (sg + pg) * 0.5;
+    if (nl > MH_NEAR_ZERO) { n = nd / nl; own = true; }
+  } else pt = sg;
+  if (!own) n = ug / norm(ug);                                                         // (a centre inside the box: 0 / 0, as in the reference)
+  return 1;
+}
+// BoxPrimitive::calc_signed_dist for a sphere (BoxPrimitive.cpp:256-276, 788-836): pA the box point, pB the sphere point
+MH_DEV double bsp_sdist(int bx, int sp, V3& pA, V3& pB) {
+  double R[9]; rot(bx, R);
+  const V3 cb = X(bx), cS = X(sp);
+  const V3 cv = matT_v(R, cS - cb);
+  const double c[3] = { cv.x, cv.y, cv.z };
+  const double h[3] = { gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5 };
+  const double Rs = gd[D_RADIUS + sp];
+  double cl[3] = { c[0], c[1], c[2] };
+  bool inside = true; double sq = 0.0, in = -MHW_INF;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    if (c[i] < -h[i]) { const double dl = c[i] + h[i]; cl[i] = -h[i]; sq = sq + dl * dl; inside = false; }
+    else if (c[i] > h[i]) { const double dl = c[i] - h[i]; cl[i] = h[i]; sq = sq + dl * dl; inside = false; }
+    else if (inside) { const double f1 = fabs(h[i] - c[i]), f2 = fabs(c[i] + h[i]); const double dd = -((f2 < f1) ? f2 : f1); in = (in < dd) ? dd : in; }
+  }
+  const double dist = (inside ? in : sqrt(sq)) - Rs;
+  const V3 v = v3(cl[0] - c[0], cl[1] - c[1], cl[2] - c[2]);
+  const double vn = norm(v);
+  pA = cb + mat_v(R, v3(cl[0], cl[1], cl[2]));
+  if (vn == 0.0) pB = cS;
+  else pB = cS + mat_v(R, v) * ((Rs + ((0.0 < dist) ? 0.0 : dist)) / vn);
+  return dist;
+}
+#endif
 
 // ---- pair-lane geometry ---------------------------------------------------------------------
 // swept bounds of body b (BoundingSphere.cpp:71-95, SSL.cpp:550-579, DummyBV.h:53-56)
@@ -280,8 +355,13 @@ MHW_FN int broad_phase(double dt, int out_off) {
       // the wheel is removed from CCD's body list and (ground, wheel) is appended unconditionally,
       // after CCD's pairs (coldet-plugin.cpp:53-74)
       spk = true; keep = is_spokes(a) && b == gi[I_NB];
+#if MHW_BSP
+    } else if (is_box(a) && is_box(b)) {
+      keep = false;                                                 // box-box: rejected by check_scene unless disabled (box-sphere: swept bounds, below)
+#else
     } else if ((is_box(a) || is_box(b)) && b != gi[I_NB]) {
       keep = false;                                                 // box-box / box-sphere: rejected by check_scene unless disabled
+#endif
     } else {
       V3 loa, hia, lob, hib; bounds(a, dt, loa, hia); bounds(b, dt, lob, hib);
       keep = (loa.x <= hib.x && lob.x <= hia.x) && (loa.y <= hib.y && lob.y <= hia.y) && (loa.z <= hib.z && lob.z <= hia.z);
@@ -316,6 +396,15 @@ MHW_FN PairGeom pair_geom(int p) {
     g.dist = min_dist; g.a = gi[I_NB]; g.b = w;
     return g;
   }
+#endif
+#if MHW_BSP
+  { int bx, sp;
+    if (bsp_pair(g.a, g.b, bx, sp)) {
+      // a sphere as A forwards to the box with the point arguments swapped (SpherePrimitive.cpp:282-290): the points stay with their bodies
+      V3 pbox, psph; g.dist = bsp_sdist(bx, sp, pbox, psph);
+      if (bx == g.a) { g.pa = pbox; g.pb = psph; } else { g.pa = psph; g.pb = pbox; }
+      return g;
+    } }
 #endif
 #if MHW_BOX
   if (is_box(g.a)) {
@@ -371,6 +460,13 @@ MH_DEV ContactGeom contact_geom(int p, double TOL) {
 MH_DEV ContactGeom contact_geom_body(int p, double TOL) {
   ContactGeom c; c.has = 0; c.g1 = 0; c.g2 = 0; c.pt = v3(0.0, 0.0, 0.0); c.n = v3(0.0, 0.0, 0.0); c.dist = 0.0;
   int a, b; pair_bodies(p, a, b);
+#if MHW_BSP
+  { int bx, sp;
+    if (bsp_pair(a, b, bx, sp)) {                                   // created as (box, sphere): the normal points from the sphere towards the box
+      c.has = bsp_contact(bx, sp, TOL, c.pt, c.n, c.dist); c.g1 = bx; c.g2 = sp;
+      return c;
+    } }
+#endif
   if (enabled(a) && enabled(b)) {
     const V3 cA = X(a), cB = X(b);
     const double rA = gd[D_RADIUS + a], rB = gd[D_RADIUS + b];
@@ -410,8 +506,12 @@ MH_DEV double ca_step(int p) {
     // calc_next_CA_Euler_step reports "never" (coldet-plugin.cpp:205-208); _rmax of the wheel is 0
     if (g.dist <= 0.0) return MHW_INF;
   } else
-#if MHW_BOX
+#if MHW_BSP
+  if (is_box(g.a) && is_ground(g.b)) {                              // box against the plane; a box-sphere pair follows the sphere rule below
+#elif MHW_BOX
   if (is_box(g.a)) {
+#endif
+#if MHW_BOX
     if (g.dist <= 0.0) {
       // calc_next_CA_Euler_step_generic (CCD.cpp:238-405) for plane (geom1) / box (geom2)
       const unsigned m = box_contact_mask(g.a, MH_NEAR_ZERO);
@@ -459,7 +559,11 @@ MH_DEV double ca_step(int p) {
     if (c.has && fabs(rel_vel(c.g1, c.g2, c.pt, c.n)) < MH_NEAR_ZERO * 10) return MHW_INF;
   }
   // CA_generic
+#if MHW_BSP
+  if (g.dist <= 0.0 && !is_spokes(g.b) && !(is_box(g.a) && is_ground(g.b))) {
+#else
   if (g.dist <= 0.0 && !is_spokes(g.b) && !is_box(g.a)) {
+#endif
     if (!have_c) c = contact_geom(p, MH_NEAR_ZERO);
     if (!c.has) return MHW_INF;
     if (rel_vel(c.g1, c.g2, c.pt, c.n) < -MH_NEAR_ZERO) return 0.0;
@@ -722,7 +826,11 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
       c.n = nn / norm(nn); c.pt = g.pa; c.g1 = g.a; c.g2 = g.b; c.dist = g.dist; c.has = 1; cnt = 1;
     } else if (mode == 1 || g.dist < thresh) {
       const double TOL = (mode == 1) ? MH_NEAR_ZERO : thresh;
+#if MHW_BSP
+      if (is_box(g.a) && is_ground(g.b)) { bx = g.a; bmask = box_contact_mask(bx, TOL); cnt = popc((uint64_t)bmask); }
+#else
       if (is_box(g.a)) { bx = g.a; bmask = box_contact_mask(bx, TOL); cnt = popc((uint64_t)bmask); }
+#endif
       else { c = contact_geom(p, TOL); cnt = c.has; }
     }
   }

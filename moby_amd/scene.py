@@ -5,6 +5,7 @@ builders for the reference scenes the BASELINE configs name:
 
 * ``sphere_stack_scene``   /root/reference/example/stacks/sphere-stack.xml
 * ``bouncing_ball_scene``  /root/reference/example/bouncing-ball/bouncing-ball.xml
+* ``ball_on_crate_scene``  a box and a sphere with their pair enabled (no reference example: tests/scenes/ball_on_crate.xml)
 
 Body order = the order programs/regress.cpp:82-93 prints them (sorted by id);
 the static ground is the last id.
@@ -347,6 +348,48 @@ def box_state(pos=(0.0, 0.5, 0.0), quat=(0.0, 0.0, 0.0, 1.0), v=(0.0, 0.0, 0.0),
     st[0, 7:10] = v
     st[0, 10:13] = w
     return st
+
+
+def add_box(sc, b, dims, mass):
+    """body b of sc becomes a box: edge lengths, mass, inertia as BoxPrimitive::calc_mass_properties (BoxPrimitive.cpp:692-712)"""
+    x, y, z = dims
+    sc.geom_type[b] = MH_GEOM_BOX
+    for k in range(3):
+        sc.geom_dim[b][k] = dims[k]
+    sc.mass[b] = mass
+    M = mass / 12.0
+    for k, j in enumerate((M * (y * y + z * z), M * (x * x + z * z), M * (x * x + y * y))):
+        sc.inertia[b][k] = j
+
+
+def ball_on_crate_scene(box_dims=(1.0, 0.5, 0.8), box_mass=3.0, radius=0.25, ball_mass=0.5, sphere_first=False, epsilon=0.2, mu_coulomb=0.4, nk=4,
+                        gravity=(0.0, -9.81, 0.0), ground=True, cstab_max_iterations=MH_CSTAB_DEFAULT_MAX_ITERATIONS):
+    """A box and a sphere (+ the plane y = 0 unless ground is False), every pair enabled with the same ContactParameters: the box-sphere pair of the
+    many-worlds stepper (include/moby_hip.h, "Box-sphere pairs").  Body 0 is the box and body 1 the sphere, or the other way round with sphere_first
+    (tests/scenes/ball_on_crate.xml is the sphere_first order: ids sort as ball < crate)."""
+    bx, sp = (1, 0) if sphere_first else (0, 1)
+    radii = [radius, radius]
+    sc = make_scene(radii, [ball_mass, ball_mass], gravity, ground_rpy=(0.0, 0.0, 0.0) if ground else None)
+    add_box(sc, bx, box_dims, box_mass)
+    ntot = 2 + sc.has_ground
+    for p in range(ntot * (ntot - 1) // 2):
+        sc.cp_epsilon[p] = epsilon
+        sc.cp_mu_coulomb[p] = mu_coulomb
+        sc.cp_nk[p] = nk
+    sc.cstab_max_iterations = cstab_max_iterations
+    sc.lcp_n_max = 64
+    return sc
+
+
+def ball_on_crate_state(B=1, gap=2e-3, speed=1.0, box_dims=(1.0, 0.5, 0.8), radius=0.25, sphere_first=False):
+    """(B, 2*13): the box at rest on the plane, the sphere `gap` above the middle of its top face moving down at `speed`"""
+    bx, sp = (1, 0) if sphere_first else (0, 1)
+    st = np.zeros((B, 2, MH_BODY_STATE))
+    st[:, :, 6] = 1.0
+    st[:, bx, 1] = 0.5 * box_dims[1]
+    st[:, sp, 1] = box_dims[1] + radius + gap
+    st[:, sp, 8] = -speed
+    return st.reshape(B, 2 * MH_BODY_STATE)
 
 
 def glibc_srand_state(seed=1):

@@ -1,0 +1,275 @@
+"""TEST INFRASTRUCTURE shared by tests/test_world_boxsphere.py and tests/test_world_boxsphere_gpu.py: the ctypes face of the box-sphere reference
+(tests/native/world_boxsphere_ref.cpp), built once per process, the batches the tests run and their reference results, computed once and read-only."""
+import ctypes
+import functools
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+
+from moby_amd import scene as S
+from moby_amd.synth import world_uniforms
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCENE_XML = os.path.join(ROOT, "tests", "scenes", "ball_on_crate.xml")
+FACE, EDGE, VERTEX, PENETRATING, NONE = range(5)     # columns of the region census
+FATAL = S.MH_WORLD_LCP_FAILED | S.MH_WORLD_UNSUPPORTED | S.MH_WORLD_STALLED
+BOX_DIMS = (1.0, 0.5, 0.8)
+RADIUS = 0.25
+
+
+class BoxSphereRef:
+    """ctypes face of tests/native/world_boxsphere_ref.cpp"""
+
+    def __init__(self, path):
+        self.lib = ctypes.CDLL(path)
+        for f in ("world_boxsphere_ref_step", "world_boxsphere_ref_contact", "world_boxsphere_ref_dist", "world_boxsphere_ref_pair"):
+            getattr(self.lib, f).restype = None
+
+    def step(self, sc, state, aux, dt, nsteps, want_traj=False, want_census=False, forces=None, wrench=None):
+        """B worlds x nsteps in place -> (trajectory (B, nsteps, nb, 7) or None, census (B, nsteps, 5) or None); forces: S.mh_world_forces or None,
+        wrench: (B, nb, 6) or (rows, B, nb, 6) host array or None"""
+        B = state.shape[0]
+        P = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        traj = np.zeros((B, nsteps, sc.nb, 7)) if want_traj else None
+        census = np.zeros((B, nsteps, 5), dtype=np.int32) if want_census else None
+        w, rows = None, 1
+        if wrench is not None:
+            w = np.ascontiguousarray(wrench, dtype=np.float64)
+            rows = 1 if w.ndim == 3 else w.shape[0]
+            assert w.shape[-3:] == (B, sc.nb, 6)
+        self.lib.world_boxsphere_ref_step(ctypes.byref(sc), int(B), ctypes.c_double(dt), int(nsteps), P(state), P(aux), P(traj), P(census),
+                                          None if forces is None else ctypes.byref(forces), P(w), int(rows))
+        return traj, census
+
+    @staticmethod
+    def _v(a, n):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        assert a.shape == (n,)
+        return a
+
+    def contact(self, cb, quat, dims, cS, radius, TOL):
+        """-> dict(has, dist, point, normal, region) of a box pose (centre, quaternion xyzw, edge lengths) and a sphere"""
+        out = np.zeros(9)
+        a = [self._v(cb, 3), self._v(quat, 4), self._v(dims, 3), self._v(cS, 3)]
+        self.lib.world_boxsphere_ref_contact(*[x.ctypes.data_as(ctypes.c_void_p) for x in a], ctypes.c_double(radius), ctypes.c_double(TOL),
+                                             out.ctypes.data_as(ctypes.c_void_p))
+        return dict(has=int(out[0]), dist=out[1], point=out[2:5].copy(), normal=out[5:8].copy(), region=int(out[8]))
+
+    def dist(self, cb, quat, dims, cS, radius):
+        """-> (signed distance, box point, sphere point)"""
+        out = np.zeros(7)
+        a = [self._v(cb, 3), self._v(quat, 4), self._v(dims, 3), self._v(cS, 3)]
+        self.lib.world_boxsphere_ref_dist(*[x.ctypes.data_as(ctypes.c_void_p) for x in a], ctypes.c_double(radius), out.ctypes.data_as(ctypes.c_void_p))
+        return out[0], out[1:4].copy(), out[4:7].copy()
+
+    def pair(self, sc, state, p, TOL):
+        """pair p of a scene in one world's state, as the stepper reads it -> dict(dist, pa, pb, a, b, ncontacts, g1, g2, cdist, point, normal)"""
+        out = np.zeros(19)
+        st = np.ascontiguousarray(state, dtype=np.float64).ravel()
+        assert st.size == sc.nb * S.MH_BODY_STATE
+        self.lib.world_boxsphere_ref_pair(ctypes.byref(sc), st.ctypes.data_as(ctypes.c_void_p), int(p), ctypes.c_double(TOL), out.ctypes.data_as(ctypes.c_void_p))
+        return dict(dist=out[0], pa=out[1:4].copy(), pb=out[4:7].copy(), a=int(out[7]), b=int(out[8]), ncontacts=int(out[9]), g1=int(out[10]), g2=int(out[11]),
+                    cdist=out[12], point=out[13:16].copy(), normal=out[16:19].copy())
+
+
+@functools.lru_cache(maxsize=None)
+def reference():
+    """the box-sphere reference, built once per process with g++ and oracle/Makefile's CXXFLAGS (the oracle's floating-point contract: no FMA)"""
+    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
+    so = os.path.join(tempfile.mkdtemp(prefix="world_boxsphere_ref_"), "libworld_boxsphere_ref.so")
+    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "world_boxsphere_ref.cpp"), "-o", so])
+    return BoxSphereRef(so)
+
+
+# ---- scenes ------------------------------------------------------------------------------------------------------------------------------------
+def mixed_scene(bodies, gravity=(0.0, -9.81, 0.0), epsilon=0.2, mu_coulomb=0.4, nk=4, disable_box_sphere=False):
+    """bodies: a list of ("box", dims, mass) / ("sphere", radius, mass) in id order, over the plane y = 0.  Every pair carries the same parameters;
+    box-box pairs are disabled (not built), box-sphere pairs too if asked."""
+    nb = len(bodies)
+    sc = S.make_scene([b[1] if b[0] == "sphere" else 1.0 for b in bodies], [b[2] for b in bodies], gravity, ground_rpy=(0.0, 0.0, 0.0))
+    for k, b in enumerate(bodies):
+        if b[0] == "box":
+            S.add_box(sc, k, b[1], b[2])
+    ntot = nb + 1
+    for p in range(ntot * (ntot - 1) // 2):
+        sc.cp_epsilon[p] = epsilon
+        sc.cp_mu_coulomb[p] = mu_coulomb
+        sc.cp_nk[p] = nk
+    for i in range(nb):
+        for j in range(i + 1, nb):
+            kinds = {bodies[i][0], bodies[j][0]}
+            if kinds == {"box"} or (disable_box_sphere and kinds == {"box", "sphere"}):
+                sc.pair_enabled[S.pair_index(i, j, ntot)] = 0
+    sc.cstab_max_iterations = 10
+    sc.lcp_n_max = 64
+    return sc
+
+
+def quat_R(q):
+    """the rotation the stepper forms from a quaternion xyzw (World::rot)"""
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def face_batch(B=8, sphere_first=False, **kw):
+    """the box at rest on the plane, the sphere 1-5 mm above its top face (a few cm off the middle), moving down at 1 m/s, no spin"""
+    sc = S.ball_on_crate_scene(sphere_first=sphere_first, **kw)
+    st = S.ball_on_crate_state(B, sphere_first=sphere_first).reshape(B, 2, S.MH_BODY_STATE)
+    sp = 0 if sphere_first else 1
+    for w in range(B):
+        u = world_uniforms(w, 3)
+        st[w, sp, 1] = BOX_DIMS[1] + RADIUS + 1e-3 + 4e-3 * u[0]
+        st[w, sp, 0] = 0.1 * (u[1] - 0.5)
+        st[w, sp, 2] = 0.1 * (u[2] - 0.5)
+    return sc, st.reshape(B, -1)
+
+
+def edge_vertex_batch():
+    """the same bodies, the box floating 5 m up under a random unit quaternion; the sphere 1-3 mm off an edge (worlds 0-3) or a vertex (worlds 4-7),
+    moving at 1 m/s along the outward direction towards it: both fall freely, so the approach stays straight"""
+    sc = S.ball_on_crate_scene()
+    B = 8
+    st = np.zeros((B, 2, S.MH_BODY_STATE))
+    h = 0.5 * np.array(BOX_DIMS)
+    for w in range(B):
+        u = world_uniforms(100 + w, 6)
+        q = np.array([u[0] - 0.5, u[1] - 0.5, u[2] - 0.5, u[3] - 0.5]); q = q / np.linalg.norm(q)
+        R = quat_R(q)
+        if w < 4:
+            p = np.array([h[0], h[1], 0.5 * h[2] * (u[4] - 0.5)]); d = np.array([1.0, 1.0, 0.0]) / np.sqrt(2.0)
+        else:
+            p = h.copy(); d = np.array([1.0, 1.0, 1.0]) / np.sqrt(3.0)
+        cb = np.array([0.0, 5.0, 0.0])
+        st[w, 0, :3] = cb; st[w, 0, 3:7] = q
+        st[w, 1, :3] = cb + R @ (p + d * (RADIUS + 1e-3 + 2e-3 * u[5])); st[w, 1, 6] = 1.0
+        st[w, 1, 7:10] = -(R @ d)
+    return sc, st.reshape(B, -1)
+
+
+FULL_BODIES = [("box", BOX_DIMS, 3.0), ("sphere", RADIUS, 0.5), ("sphere", 0.2, 0.4), ("box", BOX_DIMS, 3.0),
+               ("box", (0.6, 0.6, 0.6), 2.0), ("sphere", 0.3, 0.8), ("box", (0.8, 0.4, 1.0), 2.5), ("sphere", RADIUS, 0.5)]
+
+
+def full_batch(B=4):
+    """MH_MAX_BODIES bodies over the plane: 4 boxes and 4 spheres, ids interleaved so that both id orders of the pair occur.  Box 0 rests on the plane
+    (vertex contacts), sphere 1 lands on its top face and sphere 2 on sphere 1: one island spans a box vertex contact, a box-sphere contact and a
+    sphere-sphere contact.  Sphere 5 lands on box 4, sphere 7 on the plane beside box 6, box 3 drops onto the plane."""
+    sc = mixed_scene(FULL_BODIES)
+    st = np.zeros((B, 8, S.MH_BODY_STATE)); st[:, :, 6] = 1.0
+    for w in range(B):
+        u = world_uniforms(200 + w, 8)
+        g = 1e-3 * (1.0 + u)                                      # gaps of 1-2 mm
+        st[w, 0, :3] = (0.0, 0.25, 0.0)
+        st[w, 1, :3] = (0.05 * (u[0] - 0.5), 0.5 + 0.25 + g[0], 0.0); st[w, 1, 8] = -1.0
+        st[w, 2, :3] = (st[w, 1, 0], st[w, 1, 1] + 0.25 + 0.2 + g[1], 0.0); st[w, 2, 8] = -1.0
+        st[w, 3, :3] = (3.0, 0.25 + g[2], 0.0); st[w, 3, 8] = -0.5
+        st[w, 4, :3] = (6.0, 0.3, 0.0)
+        st[w, 5, :3] = (6.0 + 0.1 * (u[3] - 0.5), 0.6 + 0.3 + g[4], 0.1 * (u[5] - 0.5)); st[w, 5, 8] = -1.0
+        st[w, 6, :3] = (9.0, 0.2, 0.0)
+        st[w, 7, :3] = (9.0 + 0.4 + 0.25 + 0.01, 0.25 + g[6], 0.0); st[w, 7, 8] = -1.0
+    return sc, st.reshape(B, -1)
+
+
+def noslip_capacity_batch(B=4):
+    """two boxes flat on the plane side by side and a ball landing on the seam between them, mu-coulomb = 100 everywhere: one no-slip island of
+    4 + 4 box vertex contacts and two box-sphere contacts"""
+    sc = mixed_scene([("box", BOX_DIMS, 3.0), ("box", BOX_DIMS, 3.0), ("sphere", RADIUS, 0.5)], mu_coulomb=100.0)
+    st = np.zeros((B, 3, S.MH_BODY_STATE)); st[:, :, 6] = 1.0
+    for w in range(B):
+        u = world_uniforms(300 + w, 1)
+        st[w, 0, :3] = (-0.5, 0.25, 0.0); st[w, 1, :3] = (0.5, 0.25, 0.0)
+        st[w, 2, :3] = (0.0, 0.5 + RADIUS + 1e-3 * (1.0 + u[0]), 0.0); st[w, 2, 8] = -1.0
+    return sc, st.reshape(B, -1)
+
+
+def stab_batch(B=4):
+    """the stabiliser's two kinds of row: sphere 1 starts 1e-4 inside the top face of the box (dist < 0: the contact function's own row), sphere 2 hovers
+    1e-3 above sphere 1 (the synthetic row of a separated pair); everything at rest"""
+    sc = mixed_scene([("box", BOX_DIMS, 3.0), ("sphere", RADIUS, 0.5), ("sphere", 0.2, 0.4)])
+    sc.cstab_max_iterations = 10
+    st = np.zeros((B, 3, S.MH_BODY_STATE)); st[:, :, 6] = 1.0
+    for w in range(B):
+        u = world_uniforms(400 + w, 2)
+        st[w, 0, :3] = (0.0, 0.25, 0.0)
+        st[w, 1, :3] = (0.1 * (u[0] - 0.5), 0.5 + RADIUS - 1e-4, 0.1 * (u[1] - 0.5))
+        st[w, 2, :3] = (st[w, 1, 0], st[w, 1, 1] + RADIUS + 0.2 + 1e-3, st[w, 1, 2])
+    return sc, st.reshape(B, -1)
+
+
+def disabled_mixed_batch(B=6):
+    """two spheres and a box over the plane with the box-sphere pairs DISABLED (what the plain large kernels step): sphere 1 lands on sphere 0, the
+    box tumbles onto the plane"""
+    sc = mixed_scene([("sphere", 0.5, 1.0), ("sphere", 0.4, 2.0), ("box", (0.8, 0.6, 1.0), 2.0)], gravity=(0.2, -9.81, 0.1), disable_box_sphere=True)
+    sts = []
+    for w in range(B):
+        u = world_uniforms(w, 12)
+        st = np.zeros((3, 13)); st[:, 6] = 1.0
+        st[0, :3] = (0.0, 0.5 + 0.05 * u[0], 0.0); st[1, :3] = (0.1 * u[1], 1.45 + 0.2 * u[2], 0.05 * u[3])
+        st[2, :3] = (2.0, 0.45 + 0.3 * u[4], 0.0)
+        q = np.array([u[5] - 0.5, u[6] - 0.5, u[7] - 0.5, 1.0]); st[2, 3:7] = q / np.linalg.norm(q)
+        st[0, 7:10] = (0.3 * u[8], 0.0, 0.0); st[2, 10:13] = (u[9], 2 * u[10], u[11])
+        sts.append(st.ravel())
+    return sc, np.array(sts)
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_cases():
+    """name -> dict(scene, state, dt, nsteps): the batches of tests/test_world_boxsphere_gpu.py, the smallest shapes that still reach each part of the
+    kernel"""
+    out = {}
+    sc, st = face_batch(8)
+    out["face"] = dict(scene=sc, state=st, dt=1e-3, nsteps=30)
+    sc, st = edge_vertex_batch()
+    out["edge_vertex"] = dict(scene=sc, state=st, dt=1e-3, nsteps=25)
+    sc, st = face_batch(4, sphere_first=True)
+    out["id_order"] = dict(scene=sc, state=st, dt=1e-3, nsteps=25)
+    wr = np.zeros((8, 2, 6)); wr[:, 0, :] = (0.5, 0.0, 0.25, 0.0, 0.1, 0.0)     # one wrench row, on the box: a push along x and z, a torque about y
+    out["face_forces"] = dict(out["face"], forces=S.make_forces(2, stokes=(0.3, 0.05)), wrench=wr)
+    sc, st = full_batch(4)
+    out["full"] = dict(scene=sc, state=st, dt=1e-3, nsteps=20)
+    sc, st = face_batch(4, mu_coulomb=100.0, epsilon=0.0)
+    out["noslip"] = dict(scene=sc, state=st, dt=1e-3, nsteps=20)
+    sc, st = noslip_capacity_batch(4)
+    out["noslip_capacity"] = dict(scene=sc, state=st, dt=1e-3, nsteps=20)
+    sc, st = stab_batch(4)
+    out["stab"] = dict(scene=sc, state=st, dt=1e-3, nsteps=5)
+    sc, st = disabled_mixed_batch(6)
+    out["disabled"] = dict(scene=sc, state=st, dt=0.01, nsteps=40)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference_run(name):
+    """(case, final state, final aux, trajectory, census) of the reference for gpu_cases()[name], computed once per process and handed out read-only.
+    The conditions on the inputs are asserted here: except in the capacity case at most 1 world in 8 ends with a fatal bit, and every batch with an
+    enabled box-sphere pair has solved LCPs and produced box-sphere contacts"""
+    c = gpu_cases()[name]
+    st, aux = c["state"].copy(), S.new_aux(c["state"].shape[0])
+    traj, census = reference().step(c["scene"], st, aux, c["dt"], c["nsteps"], want_traj=True, want_census=True, forces=c.get("forces"), wrench=c.get("wrench"))
+    if name != "noslip_capacity":
+        assert 8 * int(((aux["status"] & FATAL) != 0).sum()) <= len(aux), (name, aux["status"])
+    if name != "disabled":
+        assert (aux["lcp_solves"] > 0).all(), (name, aux["lcp_solves"])
+        assert census[:, :, :PENETRATING + 1].sum() > 0, name
+    for a in (st, aux, traj, census):
+        a.setflags(write=False)
+    return c, st, aux, traj, census
+
+
+def centre_inside_box(sc, state):
+    """True if any world of the batch starts with a sphere's centre inside a box"""
+    st = state.reshape(state.shape[0], sc.nb, S.MH_BODY_STATE)
+    for w in range(st.shape[0]):
+        for b in range(sc.nb):
+            if sc.geom_type[b] != S.MH_GEOM_BOX:
+                continue
+            R = quat_R(st[w, b, 3:7]); h = 0.5 * np.array([sc.geom_dim[b][k] for k in range(3)])
+            for s in range(sc.nb):
+                if sc.geom_type[s] == S.MH_GEOM_SPHERE and (np.abs(R.T @ (st[w, s, :3] - st[w, b, :3])) < h).all():
+                    return True
+    return False
