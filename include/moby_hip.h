@@ -171,8 +171,29 @@ int mh_lcp_solve_batch(int kind, int B, int n,
  *   broad phase      the swept-bounds overlap test like any other pair; the box's bounding radius is its half diagonal.
  * Canonical contact order is unchanged: pairs in pair-list order, a pair's contacts in generator order.  Such a scene steps through code objects of its
  * own (mh_world_large_bsp.hip, mh_world_large_bsp_forces.hip: the large variant built with MHW_BSP); every other scene launches what it did.
- * NOT built: box against box (mh_world_batch_create refuses an enabled box-box pair), static boxes among free bodies, and the pair in the
- * large-world stepper (moby_hip_stack.h), which keeps its refusal.
+ * NOT built: box against box (mh_world_batch_create refuses an enabled box-box pair) and the pair in the large-world stepper (moby_hip_stack.h), which
+ * keeps its refusal.
+ *
+ * Static bodies.  mh_scene knows one static object, its ground plane.  mh_world_batch_create_statics takes up to MH_MAX_STATICS more (mh_world_statics
+ * below): planes and boxes, each with a frame of its own, shared by all worlds of the batch.  Body indices: enabled bodies 0 .. nb-1, the scene's ground
+ * (if has_ground) nb as before, static k at nb + has_ground + k.  The scene's pair_enabled / cp_* arrays are read triangularly over
+ * ntot = nb + has_ground + n bodies -- the rule that exists, with a larger ntot; C(9, 2) = MH_MAX_PAIRS is why ntot <= MH_MAX_BODIES + 1.  A slot of two
+ * statics is ignored whatever it holds.  Per pair kind:
+ *   sphere or box body   the closed forms of the ground, over that plane's own R and o: contact CCD.inl:804-886 (sphere: one contact, geom1 = the
+ *   against plane k      sphere; box: one per vertex within TOL, geom1 = the plane, normal = -(its normal)); signed distance PlanePrimitive.cpp:338-411;
+ *                        conservative advancement CCD.cpp:121-235 (sphere) and CCD.cpp:238-468 (box) with the pair's own plane; stabiliser rows and
+ *                        broad phase as for the ground: a plane's bound is infinite.
+ *   sphere against       the box is geometry A, as in "Box-sphere pairs" (CCD.inl swaps): contact find_contacts_box_sphere (CCD.inl:1208-1259), created
+ *   static box k         as (box, sphere) with contact_geom1 = the static; signed distance BoxPrimitive::calc_signed_dist (BoxPrimitive.cpp:256-276,
+ *                        788-836) -- both over R[k] (box axes), o[k] (box centre) and dim[k] instead of a body's quaternion and COM; the sphere has the
+ *                        lower index, so the first point is the sphere's.  Conservative advancement: the sphere rule (CCD.cpp:121-235) with
+ *                        calc_max_dist = 0 for the static (CCD.cpp:585-609).  Stabiliser: one row per pair, as for box-sphere pairs.  Broad phase: the
+ *                        static box's bounding sphere (centre o[k], radius the half diagonal) does not move (CCD.cpp:735-768 rebuilds enabled bodies'
+ *                        bounds only); pairs of two disabled bodies are dropped (CCD.cpp:864-866).
+ * Canonical contact order is unchanged: pair-list order.  A static never moves, carries no velocity and is no node of an island.  Such a batch steps
+ * through code objects of its own (mh_world_large_st.hip, mh_world_large_st_forces.hip: the large variant built with MHW_STATICS); every other batch
+ * launches what it did.  NOT built: a box body against a static box (refused while the pair is enabled), static spheres, per-world or moving statics,
+ * spokes bodies in a scene with statics (the plugin knows one ground), statics in the large-world and articulated steppers.
  */
 #define MH_MAX_BODIES 8
 #define MH_MAX_PAIRS  36            /* C(MH_MAX_BODIES + 1, 2) */
@@ -283,6 +304,8 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    after it; default 0: their own kernels; include/moby_hip_artic.h, mh_artic_model.pair_kind).
                                             key 15: world batches that would take the large variant stepped by its box-sphere build, mh_world_large_bsp*.hip (1, for
                                                    batches created after it; default 0: only scenes with an enabled box-sphere pair; for A/B runs).
+                                            key 16: world batches that would take the box-sphere build stepped by the statics build, mh_world_large_st*.hip (1, for
+                                                   batches created after it; default 0: only batches created with statics; for A/B runs).
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);
@@ -377,6 +400,30 @@ int mh_world_step_batch(const mh_scene* scene, int B, double dt, int nsteps,
  * the host) and moby_amd.world.WorldBatch(forces=) go through it; a wrench needs a DEVICE array and therefore a resident batch. */
 int mh_world_step_batch_forces(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
                                double* state, mh_world_aux* aux, double* traj);
+
+
+/* Static bodies among the free ones ("Static bodies" above).  The record belongs to the SCENE: one set for all worlds of the batch. */
+#define MH_WORLD_STATICS 1
+#define MH_MAX_STATICS 8
+#define MH_STATIC_PLANE 0
+#define MH_STATIC_BOX   1
+#ifndef MH_ABI_WITHOUT_WORLD_STATICS   /* defined by the library's own world code objects that know no statics, so that they compile from the text they had */
+typedef struct mh_world_statics {
+  int    n;                               /* 0..MH_MAX_STATICS, nb + has_ground + n <= MH_MAX_BODIES + 1 */
+  int    type[MH_MAX_STATICS];            /* MH_STATIC_* */
+  double R[MH_MAX_STATICS][9];            /* row-major rotation of the static's frame (plane: +Y is the normal, as plane_R) */
+  double o[MH_MAX_STATICS][3];            /* frame origin (box: its centre) */
+  double dim[MH_MAX_STATICS][3];          /* box: xlen, ylen, zlen; plane: unused */
+} mh_world_statics;
+/* mh_world_batch_create with static bodies.  statics == NULL or n == 0: exactly mh_world_batch_create.  MH_ERR_INVALID_ARG (with a message): n outside
+ * [0, MH_MAX_STATICS] or nb + has_ground + n > MH_MAX_BODIES + 1; an unknown type; a box with a non-positive edge; an enabled pair of a box body and a
+ * static box (box-box); a spokes body in a scene with n > 0.  Every other entry point takes the batch as before; mh_world_batch_occupancy reports the object
+ * it launches, and mh_world_batch_profile launches the production object (there is no stamped build) and reports zero cycles. */
+int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics* statics, int B, mh_world_batch** out);
+/* Host convenience: mh_world_step_batch_forces with static bodies (forces and statics may each be NULL). */
+int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
+                                double* state, mh_world_aux* aux, double* traj, const mh_world_statics* statics);
+#endif
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,8 @@ SYMBOLS = {
     "mh_world_batch_device_ptrs": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "mh_world_step_batch": (_i, [_vp, _i, _d, _i, _vp, _vp, _vp]),
     "mh_world_step_batch_forces": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "mh_world_step_batch_statics": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "mh_world_batch_create_statics": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     # include/moby_hip_impact.h
     "mh_impact_batch_create": (_i, [_i, _i, _i, _i, _vp, _vp, ctypes.POINTER(_vp)]),
     "mh_impact_batch_destroy": (_i, [_vp]),

@@ -9,6 +9,8 @@
 //   sim.current_time;               // Simulator::current_time of world 0
 //   sim.set_forces(forces);         // the simulator's recurrent forces besides gravity (StokesDragForce, DampingForce): mh_world_forces
 //   sim.step_wrench(1e-3, wrench_dev);   // ... and what the bodies' controllers add_force this step: a DEVICE array B x nb x 6
+//   MobyHip::BatchedTimeSteppingSimulator* s2 = MobyHip::BatchedTimeSteppingSimulator::with_statics(scene, statics, B, state);
+//                                   // the same with static planes and boxes beside the scene's ground (mh_world_statics); delete it when done
 //   sim.get_generalized_coordinates_euler(w, b, q);   // x y z qx qy qz qw of body b of world w
 //
 // Conventions kept from the reference: step() returns the step size; bodies are addressed in id order
@@ -33,12 +35,13 @@ class BatchedTimeSteppingSimulator {
                                bool replicate = false)
       : current_time(0.0), _scene(scene), _B(B), _wb(NULL), _dirty(false)
   {
-    if (mh_world_batch_create(&_scene, B, &_wb) != MH_OK) throw std::runtime_error(mh_last_error());
-    const size_t nst = (size_t)_scene.nb * MH_BODY_STATE;
-    _state.resize((size_t)B * nst);
-    for (int w = 0; w < B; w++) for (size_t k = 0; k < nst; k++) _state[(size_t)w * nst + k] = state[replicate ? k : (size_t)w * nst + k];
-    _aux.resize((size_t)B);
-    if (mh_world_batch_upload(_wb, _state.data(), NULL) != MH_OK) throw std::runtime_error(mh_last_error());
+    init(NULL, state, replicate);
+  }
+  /// The simulator of a scene with static bodies beside its ground (include/moby_hip.h, "Static bodies"): walls, tables, steps.  A named factory, not a
+  /// constructor overload, so that no existing call can become ambiguous; the caller owns the object.
+  static BatchedTimeSteppingSimulator* with_statics(const mh_scene& scene, const mh_world_statics& statics, int B, const double* state, bool replicate = false)
+  {
+    return new BatchedTimeSteppingSimulator(scene, &statics, B, state, replicate);
   }
   ~BatchedTimeSteppingSimulator() { if (_wb) mh_world_batch_destroy(_wb); }
 
@@ -73,6 +76,20 @@ class BatchedTimeSteppingSimulator {
   const std::vector<double>& state() { sync(); return _state; }
 
  private:
+  BatchedTimeSteppingSimulator(const mh_scene& scene, const mh_world_statics* statics, int B, const double* state, bool replicate)
+      : current_time(0.0), _scene(scene), _B(B), _wb(NULL), _dirty(false)
+  {
+    init(statics, state, replicate);
+  }
+  void init(const mh_world_statics* statics, const double* state, bool replicate)
+  {
+    if (mh_world_batch_create_statics(&_scene, statics, _B, &_wb) != MH_OK) throw std::runtime_error(mh_last_error());
+    const size_t nst = (size_t)_scene.nb * MH_BODY_STATE;
+    _state.resize((size_t)_B * nst);
+    for (int w = 0; w < _B; w++) for (size_t k = 0; k < nst; k++) _state[(size_t)w * nst + k] = state[replicate ? k : (size_t)w * nst + k];
+    _aux.resize((size_t)_B);
+    if (mh_world_batch_upload(_wb, _state.data(), NULL) != MH_OK) { mh_world_batch_destroy(_wb); _wb = NULL; throw std::runtime_error(mh_last_error()); }
+  }
   BatchedTimeSteppingSimulator(const BatchedTimeSteppingSimulator&);
   BatchedTimeSteppingSimulator& operator=(const BatchedTimeSteppingSimulator&);
   void sync() {

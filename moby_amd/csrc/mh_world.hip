@@ -9,6 +9,7 @@
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
 #include "mh_world_bsp.h"
+#include "mh_world_st.h"
 
 namespace mh {
 // layouts of the constant tables of mh_world_common.h / mh_lcp_wave.h (checked by size in upload_tables)
@@ -33,13 +34,13 @@ hipError_t init_tables()
     }
   mh::Pow10TableH p10;
   for (int i = 0; i < 64; i++) p10.v[i] = std::pow(10.0, (double)(i - 32)); // LCP.cpp:285
-  const mh_world_variant* vs[7] = { mh_world_variant_small(), mh_world_variant_wheel(), mh_world_variant_large(),
+  const mh_world_variant* vs[8] = { mh_world_variant_small(), mh_world_variant_wheel(), mh_world_variant_large(),
                                     mh_world_variant_small_prof(), mh_world_variant_wheel_prof(), mh_world_variant_large_prof(),
-                                    mh_world_variant_large_bsp() };     // (one copy of the tables per code object)
-  for (int i = 0; i < 7 && g_tables_err == hipSuccess; i++) g_tables_err = vs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
-  const mh_world_forced_variant* fs[4] = { mh_world_variant_small_forces(), mh_world_variant_wheel_forces(), mh_world_variant_large_forces(),
-                                           mh_world_variant_large_bsp_forces() };
-  for (int i = 0; i < 4 && g_tables_err == hipSuccess; i++) g_tables_err = fs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+                                    mh_world_variant_large_bsp(), mh_world_variant_large_st() };     // (one copy of the tables per code object)
+  for (int i = 0; i < 8 && g_tables_err == hipSuccess; i++) g_tables_err = vs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  const mh_world_forced_variant* fs[5] = { mh_world_variant_small_forces(), mh_world_variant_wheel_forces(), mh_world_variant_large_forces(),
+                                           mh_world_variant_large_bsp_forces(), mh_world_variant_large_st_forces() };
+  for (int i = 0; i < 5 && g_tables_err == hipSuccess; i++) g_tables_err = fs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   return g_tables_err;
 }
 hipError_t tables_for_current_device()
@@ -52,11 +53,12 @@ hipError_t tables_for_current_device()
   if (!g_tables_done[dev]) { e = init_tables(); if (e == hipSuccess) g_tables_done[dev] = 1; }
   return e;
 }
-int check_scene(const mh_scene* sc)
+// nstat: the static bodies beside the scene's ground (mh_world_statics.n; 0 for the entries without statics): the pair arrays are triangular over all of them
+int check_scene(const mh_scene* sc, int nstat = 0)
 {
   if (!sc) return fail(MH_ERR_INVALID_ARG, "null scene");
   if (sc->nb < 1 || sc->nb > MH_MAX_BODIES) return fail(MH_ERR_INVALID_ARG, "nb = %d outside [1, %d]", sc->nb, MH_MAX_BODIES);
-  const int ntot = sc->nb + (sc->has_ground ? 1 : 0);
+  const int ntot = sc->nb + (sc->has_ground ? 1 : 0) + nstat;
   int spokes_body = -1;
   for (int b = 0; b < sc->nb; b++) {
     if (sc->geom_type[b] != MH_GEOM_SPHERE && sc->geom_type[b] != MH_GEOM_SPOKES && sc->geom_type[b] != MH_GEOM_BOX)
@@ -82,6 +84,30 @@ int check_scene(const mh_scene* sc)
   for (int p = 0; p < ntot * (ntot - 1) / 2; p++)
     if (sc->cp_nk[p] < 4 || sc->cp_nk[p] > 64) return fail(MH_ERR_INVALID_ARG, "pair %d: friction-cone-edges %d outside [4, 64]", p, sc->cp_nk[p]);
   if (sc->lcp_n_max < 0 || sc->lcp_n_max > MH_LCP_MAX_N_WAVE) return fail(MH_ERR_INVALID_ARG, "lcp_n_max outside [0, %d]", MH_LCP_MAX_N_WAVE);
+  return MH_OK;
+}
+// the refusals of mh_world_batch_create_statics (include/moby_hip.h); n == 0 passes
+int check_statics(const mh_scene* sc, const mh_world_statics* st)
+{
+  if (!sc) return fail(MH_ERR_INVALID_ARG, "null scene");
+  if (st->n < 0 || st->n > MH_MAX_STATICS) return fail(MH_ERR_INVALID_ARG, "statics: n = %d outside [0, %d]", st->n, MH_MAX_STATICS);
+  if (st->n == 0) return MH_OK;
+  if (sc->nb < 1 || sc->nb > MH_MAX_BODIES) return fail(MH_ERR_INVALID_ARG, "nb = %d outside [1, %d]", sc->nb, MH_MAX_BODIES);
+  const int hg = sc->has_ground ? 1 : 0, ntot = sc->nb + hg + st->n;
+  if (ntot > MH_MAX_BODIES + 1)
+    return fail(MH_ERR_INVALID_ARG, "statics: nb + has_ground + n = %d + %d + %d exceeds %d (the pair arrays hold C(%d, 2) slots)", sc->nb, hg, st->n, MH_MAX_BODIES + 1, MH_MAX_BODIES + 1);
+  for (int b = 0; b < sc->nb; b++) if (sc->geom_type[b] == MH_GEOM_SPOKES)
+    return fail(MH_ERR_INVALID_ARG, "body %d: spokes geometry in a scene with static bodies is not built (the wheel's collision plugin knows one ground)", b);
+  for (int k = 0; k < st->n; k++) {
+    if (st->type[k] != MH_STATIC_PLANE && st->type[k] != MH_STATIC_BOX) return fail(MH_ERR_INVALID_ARG, "static %d: type %d is not built (plane, box)", k, st->type[k]);
+    for (int q = 0; q < 9; q++) if (!std::isfinite(st->R[k][q])) return fail(MH_ERR_INVALID_ARG, "static %d: rotation is not finite", k);
+    for (int q = 0; q < 3; q++) if (!std::isfinite(st->o[k][q])) return fail(MH_ERR_INVALID_ARG, "static %d: origin is not finite", k);
+    if (st->type[k] != MH_STATIC_BOX) continue;
+    for (int q = 0; q < 3; q++) if (!(st->dim[k][q] > 0.0) || !std::isfinite(st->dim[k][q])) return fail(MH_ERR_INVALID_ARG, "static %d: box edge lengths must be > 0", k);
+    const int j = sc->nb + hg + k;
+    for (int b = 0; b < sc->nb; b++) if (sc->geom_type[b] == MH_GEOM_BOX && sc->pair_enabled[b * ntot - (b * (b + 1)) / 2 + (j - b - 1)])
+      return fail(MH_ERR_INVALID_ARG, "body %d, static %d: box-box contact is not built; disable the pair (box-plane and sphere-box are)", b, k);
+  }
   return MH_OK;
 }
 } // namespace
@@ -112,6 +138,7 @@ struct mh_world_batch {
   int B;
   int nmax;
   int variant;               // 0 small, 1 large, 2 wheel
+  bool st;                   // the large variant's statics build (mh_world_large_st*.hip): created with statics, or a box-sphere batch under mh_debug_set(16, 1)
   bool bsp;                  // the large variant's box-sphere build (mh_world_large_bsp*.hip): an enabled box-sphere pair, or mh_debug_set(15, 1) at create
   mh_world_kernel kernel;
   int ph_count;
@@ -156,9 +183,17 @@ int mh_world_batch_occupancy(mh_world_batch* wb)
 
 int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
 {
+  return mh_world_batch_create_statics(scene, nullptr, B, out);
+}
+
+int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics* statics, int B, mh_world_batch** out)
+{
   if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
   *out = nullptr;
-  int rc = check_scene(scene);
+  int rc = statics ? check_statics(scene, statics) : MH_OK;
+  if (rc != MH_OK) return rc;
+  const int nstat = statics ? statics->n : 0;
+  rc = check_scene(scene, nstat);
   if (rc != MH_OK) return rc;
   if (B <= 0) return fail(MH_ERR_INVALID_ARG, "batch must be > 0");
   if (mh_device_count() <= 0) return fail(MH_ERR_NO_DEVICE, "no HIP device visible");
@@ -174,7 +209,7 @@ int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
     // A world that outgrows the variant's limits at run time gets MH_WORLD_UNSUPPORTED.
     // Spokes geometry or a pair with mu-coulomb >= 100 (=> the no-slip model, ICH:127-135) needs a
     // variant built with those features: "wheel" for one or two bodies, otherwise "large".
-    const int ntot = scene->nb + (scene->has_ground ? 1 : 0), npairs = ntot * (ntot - 1) / 2;
+    const int ntot = scene->nb + (scene->has_ground ? 1 : 0) + nstat, npairs = ntot * (ntot - 1) / 2;
     bool noslip = false, box = false;
     for (int b = 0; b < scene->nb; b++) if (scene->geom_type[b] == MH_GEOM_SPOKES) noslip = true;
     for (int b = 0; b < scene->nb; b++) if (scene->geom_type[b] == MH_GEOM_BOX) box = true;
@@ -190,7 +225,10 @@ int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
     }
     wb->bsp = wb->variant == 1 && (bsp || mh_g_debug_world_bsp != 0);
     if (wb->bsp) wb->kernel = mh_world_variant_large_bsp()->kernel;
-    wb->fkernel = wb->bsp ? mh_world_variant_large_bsp_forces()->kernel : (wb->variant == 0 ? mh_world_variant_small_forces() : wb->variant == 2 ? mh_world_variant_wheel_forces() : mh_world_variant_large_forces())->kernel;
+    // static bodies need the statics build; every other batch launches what it launched (key 16: the box-sphere batches through the statics build)
+    wb->st = nstat > 0 || (wb->bsp && mh_g_debug_world_st != 0);
+    if (wb->st) { wb->variant = 1; wb->bsp = true; wb->kernel = mh_world_variant_large_st()->kernel; }
+    wb->fkernel = wb->st ? mh_world_variant_large_st_forces()->kernel : wb->bsp ? mh_world_variant_large_bsp_forces()->kernel : (wb->variant == 0 ? mh_world_variant_small_forces() : wb->variant == 2 ? mh_world_variant_wheel_forces() : mh_world_variant_large_forces())->kernel;
     wb->has_forces = false; wb->d_forces = nullptr;
   }
   wb->d_scene = nullptr; wb->d_state = nullptr; wb->d_aux = nullptr; wb->d_lu_ws = nullptr;
@@ -201,12 +239,16 @@ int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
     const double Rr = scene->geom_dim[b][0]; const int N = (int)scene->geom_dim[b][1];
     for (int i = 0; i < N; i++) { const double theta = M_PI * i * 2.0 / N; tips[2*i] = std::cos(theta) * Rr; tips[2*i+1] = std::sin(theta) * Rr; }
   }
-  hipError_t e = hipMalloc(&wb->d_scene, sizeof(mh_scene) + sizeof(tips));
+  // ... and by the statics record (n = 0 without statics), which only the statics build reads
+  mh_world_statics strec; std::memset(&strec, 0, sizeof(strec));
+  if (nstat > 0) strec = *statics;
+  hipError_t e = hipMalloc(&wb->d_scene, sizeof(mh_scene) + sizeof(tips) + sizeof(strec));
   if (e == hipSuccess) e = hipMalloc(&wb->d_lu_ws, (size_t)B * wb->nmax * wb->nmax * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&wb->d_state, (size_t)B * scene->nb * MH_BODY_STATE * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&wb->d_aux, (size_t)B * sizeof(mh_world_aux));
   if (e == hipSuccess) e = hipMemcpy(wb->d_scene, scene, sizeof(mh_scene), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<char*>(wb->d_scene) + sizeof(mh_scene), tips, sizeof(tips), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<char*>(wb->d_scene) + sizeof(mh_scene) + sizeof(tips), &strec, sizeof(strec), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(wb->d_state, 0, (size_t)B * scene->nb * MH_BODY_STATE * sizeof(double));
   if (e == hipSuccess) {
     std::vector<mh_world_aux> a((size_t)B);
@@ -420,17 +462,23 @@ int mh_world_batch_device_ptrs(mh_world_batch* wb, double** state_dev, mh_world_
 int mh_world_step_batch(const mh_scene* scene, int B, double dt, int nsteps,
                         double* state, mh_world_aux* aux, double* traj)
 {
-  return mh_world_step_batch_forces(scene, nullptr, B, dt, nsteps, state, aux, traj);
+  return mh_world_step_batch_statics(scene, nullptr, B, dt, nsteps, state, aux, traj, nullptr);
 }
 
 int mh_world_step_batch_forces(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
                                double* state, mh_world_aux* aux, double* traj)
 {
+  return mh_world_step_batch_statics(scene, forces, B, dt, nsteps, state, aux, traj, nullptr);
+}
+
+int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
+                                double* state, mh_world_aux* aux, double* traj, const mh_world_statics* statics)
+{
   if (B == 0 || nsteps == 0) return MH_OK;
   if (B < 0 || nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative batch or step count");
   if (!state || !aux) return fail(MH_ERR_INVALID_ARG, "null state/aux");
   mh_world_batch* wb = nullptr;
-  int rc = mh_world_batch_create(scene, B, &wb);
+  int rc = mh_world_batch_create_statics(scene, statics, B, &wb);
   if (rc != MH_OK) return rc;
   double* dtraj = nullptr;
   const size_t sz_tr = (size_t)B * nsteps * scene->nb * 7 * sizeof(double);

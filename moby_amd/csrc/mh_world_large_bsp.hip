@@ -2,6 +2,7 @@
 // scene enables at least one box-sphere pair, or under mh_debug_set(15, 1).  The constants are mh_world_large.hip's: <= 8 bodies, <= 36 pairs, <= 40 contacts,
 // <= 24 rows per island, every feature.  A translation unit of its own, so that the plain large kernels stay the code objects they were.
 #include <hip/hip_runtime.h>
+#define MH_ABI_WITHOUT_WORLD_STATICS 1   /* this object knows no static bodies: the public header expands to the text it had for it */
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
 #include "mh_world_bsp.h"

@@ -1,24 +1,23 @@
-// The "large" variant of the many-worlds kernel (mh_world_wave.inc): <= 8 bodies, <= 36 pairs, <= 40 contacts, <= 24 rows per island, every feature.
-// One translation unit per variant: the LDS image, occupancy and feature set differ, and the three compile in parallel.
+// The "large" variant of the many-worlds kernel (mh_world_wave.inc) with static bodies beside the free ones (MHW_STATICS, on top of MHW_BSP): what a batch
+// created with a non-empty mh_world_statics launches, or one that would take the box-sphere build under mh_debug_set(16, 1).  The constants are
+// mh_world_large.hip's: <= 8 bodies, <= 36 pairs over <= 9 bodies and statics, <= 40 contacts, <= 24 rows per island, every feature.  A translation unit of
+// its own, so that the other large kernels stay the code objects they were.
 #include <hip/hip_runtime.h>
-#define MH_ABI_WITHOUT_WORLD_STATICS 1   /* this object knows no static bodies: the public header expands to the text it had for it */
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#ifdef MH_PROFILE_BUILD      /* mh_world_large_prof.hip: the same kernel with the s_memtime stamps compiled in (mh_world_batch_profile) */
-#define MHW_NS large_prof
-#define MHW_VARIANT_GETTER mh_world_variant_large_prof
-#elif defined(MH_FORCES_BUILD) /* mh_world_large_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
-#define MHW_NS large_forces
-#define MHW_VARIANT_GETTER mh_world_variant_large_forces
+#include "mh_world_st.h"
+#if defined(MH_FORCES_BUILD)   /* mh_world_large_st_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
+#define MHW_NS large_st_forces
+#define MHW_VARIANT_GETTER mh_world_variant_large_st_forces
 #define MHW_VARIANT_T mh_world_forced_variant
 #define MHW_FORCES 1
 #else
-#define MHW_NS large
-#define MHW_VARIANT_GETTER mh_world_variant_large
-#endif
-#ifndef MHW_VARIANT_T
+#define MHW_NS large_st
+#define MHW_VARIANT_GETTER mh_world_variant_large_st
 #define MHW_VARIANT_T mh_world_variant
 #endif
+#define MHW_STATICS 1
+#define MHW_BSP 1
 #define MHW_NOSLIP 1
 #define MHW_BOX 1
 #define MHW_NB MH_MAX_BODIES

@@ -1,6 +1,7 @@
 // The "small" variant of the many-worlds kernel (mh_world_wave.inc): <= 4 bodies, <= 6 pairs, <= 6 contacts, <= 12 Jacobian rows, spheres + Drumwright-Shell model only.
 // One translation unit per variant: the LDS image, occupancy and feature set differ, and the three compile in parallel.
 #include <hip/hip_runtime.h>
+#define MH_ABI_WITHOUT_WORLD_STATICS 1   /* this object knows no static bodies: the public header expands to the text it had for it */
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
 #ifdef MH_PROFILE_BUILD      /* mh_world_small_prof.hip: the same kernel with the s_memtime stamps compiled in (mh_world_batch_profile) */

@@ -1,5 +1,5 @@
 // One Moby world per wavefront: TimeSteppingSimulator::step and everything it drives, for scenes of
-// free rigid bodies (spheres, boxes against the plane, rimless-wheel spokes) + one static plane.
+// free rigid bodies (spheres, boxes against the plane, rimless-wheel spokes) + one static plane (with MHW_STATICS: + up to 8 static planes and boxes).
 //
 // Replaces (per world; same results as the CPU oracle oracle/world.hpp, which restates these
 // reference functions statement by statement):
@@ -42,6 +42,8 @@
 // recurrent forces and the caller's wrench to the forward dynamics; every line it adds sits under #if MHW_FORCES.
 // MHW_BSP (1 in mh_world_large_bsp*.hip, undefined = 0 elsewhere; needs MHW_BOX) adds box-sphere contacts between two free bodies (include/moby_hip.h,
 // "box-sphere pairs"); every line it adds or alters sits under #if MHW_BSP, so the other code objects compile from the text they had.
+// MHW_STATICS (1 in mh_world_large_st*.hip, undefined = 0 elsewhere; needs MHW_BSP) adds several static bodies -- planes and boxes, each with a frame of its
+// own -- beside the free bodies (include/moby_hip.h, "static bodies"); every line it adds or alters sits under #if MHW_STATICS.
 #include "mh_world_common.h"
 
 #define MHW_NS_MAXC ((MHW_MAX_CONTACTS < 6) ? MHW_MAX_CONTACTS : 6)   /* contacts of a no-slip island */
@@ -151,6 +153,16 @@ __shared__ double gf[F_END];
 __shared__ int g_fterms;
 #endif
 
+#if MHW_STATICS
+// The static bodies of the scene (include/moby_hip.h: mh_world_statics), cached at launch in an image of its own beside gd, as gf is, so that gd's offsets
+// stay where they were.  Slot s serves body nb + s: the scene's own ground (if any) is slot 0, from plane_R / plane_o; static k follows at has_ground + k.
+// nb >= 1 and ntot <= MH_MAX_BODIES + 1 leave at most MH_MAX_STATICS slots.  Per slot: rotation (9, row-major), origin (3), box edge lengths (3) and the
+// box's bounding radius (half diagonal, CCD.cpp:1056-1063): 16 MH_MAX_STATICS doubles + a type word each = 1056 bytes.
+enum { S_R = 0, S_O = 9 * MH_MAX_STATICS, S_DIM = 12 * MH_MAX_STATICS, S_RAD = 15 * MH_MAX_STATICS, S_END = 16 * MH_MAX_STATICS };
+__shared__ double gs[S_END];
+__shared__ int gst[MH_MAX_STATICS];
+#endif
+
 #define MHW_FN __device__ __noinline__
 // (measured with tools/variants.sh: the impulse application / constraint-velocity update, the island search and
 //  compute_problem_data are faster inlined, +1.8 %; apply_impulses, store_contact and broad_phase are not)
@@ -183,6 +195,22 @@ MH_DEV void pair_bodies(int p, int& a, int& b) {
   while (rem >= ntot - 1 - i) { rem -= ntot - 1 - i; i++; }
   a = i; b = i + 1 + rem;
 }
+#if MHW_STATICS
+// the frame of static plane `pl` (a body index >= nb; the scene's ground is nb), from the table: the same statements over that plane's R and o
+MH_DEV V3 plane_n(int pl) { const double* R = gs + S_R + 9 * (pl - gi[I_NB]); return v3(R[1], R[4], R[7]); }
+MH_DEV V3 to_plane(V3 p, int pl) {
+  const int s = pl - gi[I_NB];
+  const double* R = gs + S_R + 9 * s; V3 d = p - v3(gs[S_O + 3*s], gs[S_O + 3*s + 1], gs[S_O + 3*s + 2]);
+  return v3((R[0]*d.x + R[3]*d.y) + R[6]*d.z, (R[1]*d.x + R[4]*d.y) + R[7]*d.z, (R[2]*d.x + R[5]*d.y) + R[8]*d.z);
+}
+MH_DEV V3 from_plane(V3 p, int pl) {
+  const int s = pl - gi[I_NB];
+  const double* R = gs + S_R + 9 * s;
+  return v3(gs[S_O + 3*s] + ((R[0]*p.x + R[1]*p.y) + R[2]*p.z),
+            gs[S_O + 3*s + 1] + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z),
+            gs[S_O + 3*s + 2] + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
+}
+#else
 MH_DEV V3 plane_n() { return v3(gd[D_PLANE_R + 1], gd[D_PLANE_R + 4], gd[D_PLANE_R + 7]); }
 MH_DEV V3 to_plane(V3 p) {
   const double* R = gd + D_PLANE_R; V3 d = p - v3(gd[D_PLANE_O], gd[D_PLANE_O + 1], gd[D_PLANE_O + 2]);
@@ -194,6 +222,7 @@ MH_DEV V3 from_plane(V3 p) {
             gd[D_PLANE_O + 1] + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z),
             gd[D_PLANE_O + 2] + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
 }
+#endif
 MH_DEV void orthonormal_basis(V3 n, V3& s, V3& t) {
   const double ax = fabs(n.x), ay = fabs(n.y), az = fabs(n.z);
   V3 e;
@@ -244,11 +273,19 @@ MH_DEV V3 box_vertex(int b, int i) {
   return v3(c.x + ((R[0]*p.x + R[1]*p.y) + R[2]*p.z), c.y + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z), c.z + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
 }
 // find_contacts_plane_generic(plane, box) (CCD.inl:848-886): bit i set <=> vertex i is within TOL (<=) of the plane
+#if MHW_STATICS
+MH_DEV unsigned box_contact_mask(int b, double TOL, int pl) {
+  unsigned m = 0;
+  for (int i = 0; i < 8; i++) { const V3 pp = to_plane(box_vertex(b, i), pl); if (pp.y <= TOL) m |= 1u << i; }
+  return m;
+}
+#else
 MH_DEV unsigned box_contact_mask(int b, double TOL) {
   unsigned m = 0;
   for (int i = 0; i < 8; i++) { const V3 pp = to_plane(box_vertex(b, i)); if (pp.y <= TOL) m |= 1u << i; }
   return m;
 }
+#endif
 MH_DEV bool rel_equal(double x, double y) {                         // CompGeom.h:110
   const double ax = fabs(x), ay = fabs(y);
   const double m1 = (ay > 1.0) ? ay : 1.0; const double m = (ax > m1) ? ax : m1;
@@ -264,21 +301,51 @@ MH_DEV bool collinear(V3 a, V3 b, V3 c) {                           // CompGeom.
 // the bodies' own (box centre = COM, box axes = rot(box)).  Operation order = tests/native/world_boxsphere_ref.cpp (= artic_boxsphere_ref.cpp):
 // three-term sums as (a + b) + c.  Each function forms the box rotation once. ----
 MH_DEV bool is_sphere(int b) { return b < gi[I_NB] && gi[I_GEOM + b] == MH_GEOM_SPHERE; }
+#if MHW_STATICS
+MH_DEV bool is_static(int b, int type) { const int s = b - gi[I_NB]; return s >= 0 && s < MH_MAX_STATICS && b < gi[I_NTOT] && gst[s] == type; }
+MH_DEV bool is_ground(int b) { return is_static(b, MH_STATIC_PLANE); }                 // "a static plane": the scene's ground or any other
+MH_DEV bool is_sbox(int b) { return is_static(b, MH_STATIC_BOX); }
+MH_DEV bool bsp_pair(int a, int b, int& bx, int& sp) {
+  if (is_box(a) && is_sphere(b)) { bx = a; sp = b; return true; }
+  if (is_sphere(a) && (is_box(b) || is_sbox(b))) { bx = b; sp = a; return true; }       // (a static has the higher index: it is never a)
+  return false;
+}
+// rotation, centre and half lengths of box bx: a body's own frame, or a static box's from the table
+MH_DEV void box_frame(int bx, double R[9], V3& cb, V3& h) {
+  if (bx < gi[I_NB]) {
+    rot(bx, R); cb = X(bx);
+    h = v3(gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5);
+  } else {
+    const int s = bx - gi[I_NB];
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = gs[S_R + 9*s + k];
+    cb = v3(gs[S_O + 3*s], gs[S_O + 3*s + 1], gs[S_O + 3*s + 2]);
+    h = v3(gs[S_DIM + 3*s] * 0.5, gs[S_DIM + 3*s + 1] * 0.5, gs[S_DIM + 3*s + 2] * 0.5);
+  }
+}
+#else
 MH_DEV bool is_ground(int b) { return b == gi[I_NB]; }
 MH_DEV bool bsp_pair(int a, int b, int& bx, int& sp) {
   if (is_box(a) && is_sphere(b)) { bx = a; sp = b; return true; }
   if (is_sphere(a) && is_box(b)) { bx = b; sp = a; return true; }
   return false;
 }
+#endif
 MH_DEV V3 mat_v(const double R[9], V3 p) { return v3((R[0]*p.x + R[1]*p.y) + R[2]*p.z, (R[3]*p.x + R[4]*p.y) + R[5]*p.z, (R[6]*p.x + R[7]*p.y) + R[8]*p.z); }
 MH_DEV V3 matT_v(const double R[9], V3 p) { return v3((R[0]*p.x + R[3]*p.y) + R[6]*p.z, (R[1]*p.x + R[4]*p.y) + R[7]*p.z, (R[2]*p.x + R[5]*p.y) + R[8]*p.z); }
 MH_DEV double clampd(double c, double h) { return (c < -h) ? -h : ((c > h) ? h : c); }
 // BoxPrimitive::calc_closest_points (BoxPrimitive.cpp:183-254; the QP's fixed point is the clamp) + find_contacts_box_sphere (CCD.inl:1208-1259)
 MH_DEV int bsp_contact(int bx, int sp, double TOL, V3& pt, V3& n, double& dist) {
+#if MHW_STATICS
+  double R[9]; V3 cb, h; box_frame(bx, R, cb, h);
+  const V3 cS = X(sp);
+  const V3 c = matT_v(R, cS - cb);
+#else
   double R[9]; rot(bx, R);
   const V3 cb = X(bx), cS = X(sp);
   const V3 c = matT_v(R, cS - cb);
   const V3 h = v3(gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5);
+#endif
   const double Rs = gd[D_RADIUS + sp];
   const V3 p = v3(clampd(c.x, h.x), clampd(c.y, h.y), clampd(c.z, h.z));
   V3 u = p - c;
@@ -309,11 +376,19 @@ MH_DEV int bsp_contact(int bx, int sp, double TOL, V3& pt, V3& n, double& dist) 
 }
 // BoxPrimitive::calc_signed_dist for a sphere (BoxPrimitive.cpp:256-276, 788-836): pA the box point, pB the sphere point
 MH_DEV double bsp_sdist(int bx, int sp, V3& pA, V3& pB) {
+#if MHW_STATICS
+  double R[9]; V3 cb, hv; box_frame(bx, R, cb, hv);
+  const V3 cS = X(sp);
+  const V3 cv = matT_v(R, cS - cb);
+  const double c[3] = { cv.x, cv.y, cv.z };
+  const double h[3] = { hv.x, hv.y, hv.z };
+#else
   double R[9]; rot(bx, R);
   const V3 cb = X(bx), cS = X(sp);
   const V3 cv = matT_v(R, cS - cb);
   const double c[3] = { cv.x, cv.y, cv.z };
   const double h[3] = { gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5 };
+#endif
   const double Rs = gd[D_RADIUS + sp];
   double cl[3] = { c[0], c[1], c[2] };
   bool inside = true; double sq = 0.0, in = -MHW_INF;
@@ -336,6 +411,13 @@ MH_DEV double bsp_sdist(int bx, int sp, V3& pA, V3& pB) {
 // ---- pair-lane geometry ---------------------------------------------------------------------
 // swept bounds of body b (BoundingSphere.cpp:71-95, SSL.cpp:550-579, DummyBV.h:53-56)
 MH_DEV void bounds(int b, double dt, V3& lo, V3& hi) {
+#if MHW_STATICS
+  if (is_sbox(b)) {                                                  // a static box: its bounding sphere, which does not move (CCD.cpp:735-768 rebuilds enabled bodies' only)
+    const int s = b - gi[I_NB];
+    const V3 c = v3(gs[S_O + 3*s], gs[S_O + 3*s + 1], gs[S_O + 3*s + 2]); const double r = gs[S_RAD + s];
+    lo = v3(c.x - r, c.y - r, c.z - r); hi = v3(c.x + r, c.y + r, c.z + r); return;
+  }
+#endif
   if (!enabled(b)) { lo = v3(-MHW_INF, -MHW_INF, -MHW_INF); hi = v3(MHW_INF, MHW_INF, MHW_INF); return; }
   const V3 c = X(b);
   const V3 vdt = Vl(b) * dt, wdt = Wa(b) * dt;
@@ -355,7 +437,10 @@ MHW_FN int broad_phase(double dt, int out_off) {
       // the wheel is removed from CCD's body list and (ground, wheel) is appended unconditionally,
       // after CCD's pairs (coldet-plugin.cpp:53-74)
       spk = true; keep = is_spokes(a) && b == gi[I_NB];
-#if MHW_BSP
+#if MHW_STATICS
+    } else if (is_box(a) && (is_box(b) || is_sbox(b))) {
+      keep = false;                                                 // box-box, a static box included: rejected at create unless disabled
+#elif MHW_BSP
     } else if (is_box(a) && is_box(b)) {
       keep = false;                                                 // box-box: rejected by check_scene unless disabled (box-sphere: swept bounds, below)
 #else
@@ -390,8 +475,13 @@ MHW_FN PairGeom pair_geom(int p) {
     const V3 cw = X(w);
     for (int i = 0; i < N; i++) {
       const V3 tip = spoke_tip_at(Rw, cw, i);
+#if MHW_STATICS
+      const V3 pp = to_plane(tip, gi[I_NB]);
+      if (pp.y < min_dist) { min_dist = pp.y; g.pb = from_plane(v3(pp.x, 0.0, pp.z), gi[I_NB]); g.pa = tip; }
+#else
       const V3 pp = to_plane(tip);
       if (pp.y < min_dist) { min_dist = pp.y; g.pb = from_plane(v3(pp.x, 0.0, pp.z)); g.pa = tip; }
+#endif
     }
     g.dist = min_dist; g.a = gi[I_NB]; g.b = w;
     return g;
@@ -413,8 +503,13 @@ MHW_FN PairGeom pair_geom(int p) {
     g.pa = v3(0.0, 0.0, 0.0); g.pb = v3(0.0, 0.0, 0.0);
     for (int i = 0; i < 8; i++) {
       const V3 vtx = box_vertex(g.a, i);
+#if MHW_STATICS
+      const V3 pp = to_plane(vtx, g.b);                             // (a box body's partner here is a static plane: box-sphere went above, box-box is never kept)
+      if (pp.y < min_dist) { min_dist = pp.y; g.pa = vtx; g.pb = from_plane(v3(pp.x, 0.0, pp.z), g.b); }
+#else
       const V3 pp = to_plane(vtx);
       if (pp.y < min_dist) { min_dist = pp.y; g.pa = vtx; g.pb = from_plane(v3(pp.x, 0.0, pp.z)); }
+#endif
     }
     g.dist = min_dist;
     return g;
@@ -432,11 +527,20 @@ MHW_FN PairGeom pair_geom(int p) {
     return g;
   }
   const int s = enabled(g.a) ? g.a : g.b;
+#if MHW_STATICS
+  const int pl = enabled(g.a) ? g.b : g.a;
+  const V3 cp = to_plane(X(s), pl);
+  const double r = gd[D_RADIUS + s];
+  const double low = cp.y + (-1.0 * r);
+  const V3 on_plane = from_plane(v3(cp.x, 0.0, cp.z), pl);
+  const V3 on_sphere = from_plane(v3(cp.x, low, cp.z), pl);
+#else
   const V3 cp = to_plane(X(s));
   const double r = gd[D_RADIUS + s];
   const double low = cp.y + (-1.0 * r);
   const V3 on_plane = from_plane(v3(cp.x, 0.0, cp.z));
   const V3 on_sphere = from_plane(v3(cp.x, low, cp.z));
+#endif
   if (s == g.a) { g.pa = on_sphere; g.pb = on_plane; } else { g.pa = on_plane; g.pb = on_sphere; }
   g.dist = low;
   return g;
@@ -481,12 +585,21 @@ MH_DEV ContactGeom contact_geom_body(int p, double TOL) {
     return c;
   }
   const int s = enabled(a) ? a : b, pl = enabled(a) ? b : a;
+#if MHW_STATICS
+  const V3 cp = to_plane(X(s), pl);
+  const double r = gd[D_RADIUS + s];
+  c.dist = cp.y - r;
+  if (c.dist > TOL) return c;
+  c.pt = from_plane(v3(cp.x, 0.5 * (cp.y - r), cp.z), pl);
+  c.n = plane_n(pl); c.g1 = s; c.g2 = pl; c.has = 1;
+#else
   const V3 cp = to_plane(X(s));
   const double r = gd[D_RADIUS + s];
   c.dist = cp.y - r;
   if (c.dist > TOL) return c;
   c.pt = from_plane(v3(cp.x, 0.5 * (cp.y - r), cp.z));
   c.n = plane_n(); c.g1 = s; c.g2 = pl; c.has = 1;
+#endif
   return c;
 }
 MH_DEV double rel_vel(int g1, int g2, V3 pt, V3 dir) { return dot(dir, point_vel(g1, pt) - point_vel(g2, pt)); }
@@ -514,10 +627,17 @@ MH_DEV double ca_step(int p) {
 #if MHW_BOX
     if (g.dist <= 0.0) {
       // calc_next_CA_Euler_step_generic (CCD.cpp:238-405) for plane (geom1) / box (geom2)
+#if MHW_STATICS
+      const unsigned m = box_contact_mask(g.a, MH_NEAR_ZERO, g.b);   // the pair's own plane
+      if (m == 0u) return MHW_INF;
+      const V3 cn = -plane_n(g.b);
+      const int gnd = g.b;
+#else
       const unsigned m = box_contact_mask(g.a, MH_NEAR_ZERO);
       if (m == 0u) return MHW_INF;
       const V3 cn = -plane_n();
       const int gnd = gi[I_NB];
+#endif
       V3 p3[3]; int np = 0; V3 first = v3(0.0, 0.0, 0.0);
       for (int i = 0; i < 8; i++) if ((m >> i) & 1u) {
         const V3 vtx = box_vertex(g.a, i);
@@ -790,15 +910,25 @@ MHW_FN int spoke_contacts(int p, int nc) {
   bool has = false; V3 pt = v3(0.0, 0.0, 0.0); double dist = 0.0;
   if (lane < gi[I_NSPOKES]) {
     const V3 tip = spoke_tip(a, lane);
+#if MHW_STATICS
+    const V3 pp = to_plane(tip, b);
+    has = pp.y < gd[D_THRESH];
+    pt = (tip + from_plane(v3(pp.x, 0.0, pp.z), b)) * 0.5;
+#else
     const V3 pp = to_plane(tip);
     has = pp.y < gd[D_THRESH];
     pt = (tip + from_plane(v3(pp.x, 0.0, pp.z))) * 0.5;
+#endif
     dist = pp.y;
   }
   const uint64_t m = ballot(has);
   wave_sync();
   if (nc + popc(m) > MHW_MAX_CONTACTS) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); return nc; }
+#if MHW_STATICS
+  if (has) store_contact(nc + popc(m & lanes_below(lane)), p, a, b, pt, plane_n(b), dist);
+#else
   if (has) store_contact(nc + popc(m & lanes_below(lane)), p, a, b, pt, plane_n(), dist);
+#endif
   wave_sync();
   return nc + popc(m);
 }
@@ -817,6 +947,9 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
   const double thresh = gd[D_THRESH];
   ContactGeom c; c.has = 0; c.g1 = 0; c.g2 = 0; c.pt = v3(0, 0, 0); c.n = v3(0, 0, 0); c.dist = 0.0;
   int p = 0, cnt = 0, bx = -1; unsigned bmask = 0u;
+#if MHW_STATICS
+  int bpl = 0;                                                      // the plane of this lane's box-plane pair
+#endif
   if (lane < count) {
     p = gi[list_off + lane];
     const PairGeom g = pair_geom(p);
@@ -826,7 +959,9 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
       c.n = nn / norm(nn); c.pt = g.pa; c.g1 = g.a; c.g2 = g.b; c.dist = g.dist; c.has = 1; cnt = 1;
     } else if (mode == 1 || g.dist < thresh) {
       const double TOL = (mode == 1) ? MH_NEAR_ZERO : thresh;
-#if MHW_BSP
+#if MHW_STATICS
+      if (is_box(g.a) && is_ground(g.b)) { bx = g.a; bpl = g.b; bmask = box_contact_mask(bx, TOL, bpl); cnt = popc((uint64_t)bmask); }
+#elif MHW_BSP
       if (is_box(g.a) && is_ground(g.b)) { bx = g.a; bmask = box_contact_mask(bx, TOL); cnt = popc((uint64_t)bmask); }
 #else
       if (is_box(g.a)) { bx = g.a; bmask = box_contact_mask(bx, TOL); cnt = popc((uint64_t)bmask); }
@@ -841,10 +976,18 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
   wave_sync();
   if (total > MHW_MAX_CONTACTS) return -1;
   if (bx >= 0) {
+#if MHW_STATICS
+    const V3 cn = -plane_n(bpl); const int gnd = bpl;
+#else
     const V3 cn = -plane_n(); const int gnd = gi[I_NB];
+#endif
     for (int i = 0; i < 8; i++) if ((bmask >> i) & 1u) {
       const V3 vtx = box_vertex(bx, i);
+#if MHW_STATICS
+      store_contact(off, p, gnd, bx, vtx, cn, to_plane(vtx, bpl).y);
+#else
       store_contact(off, p, gnd, bx, vtx, cn, to_plane(vtx).y);     // create_contact(plane, box, vertex, -n, dist)
+#endif
       off++;
     }
   } else if (c.has) store_contact(off, p, c.g1, c.g2, c.pt, c.n, c.dist);
@@ -1859,7 +2002,26 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
   if ((unsigned)w >= (unsigned)B) return;                     // B: the worlds of the BATCH (an id outside it is ignored, never dereferenced)
   const int lane = lane_id();
   const mh_scene& sc = *scp;
+#if MHW_STATICS
+  // the statics record follows the spoke-tip table behind the scene record (mh_world.hip lays all three out in one allocation)
+  const mh_world_statics& sst = *reinterpret_cast<const mh_world_statics*>(reinterpret_cast<const double*>(scp + 1) + 2 * MH_MAX_SPOKES);
+  const int hg = sc.has_ground ? 1 : 0, nst_ = sst.n;
+  const int nb = sc.nb, ntot = sc.nb + hg + nst_, npt = ntot * (ntot - 1) / 2;
+  if (nb < 1 || nst_ < 0 || ntot > MH_MAX_BODIES + 1) return;      // (refused at create; never index past the tables)
+  if (lane < hg + nst_) {
+    const int k = lane - hg;                                        // slot `lane` = body nb + lane: the scene's ground first, static k at has_ground + k
+    const bool gr = k < 0;
+    gst[lane] = gr ? MH_STATIC_PLANE : sst.type[k];
+    for (int q = 0; q < 9; q++) gs[S_R + 9*lane + q] = gr ? sc.plane_R[q] : sst.R[k][q];
+    for (int q = 0; q < 3; q++) gs[S_O + 3*lane + q] = gr ? sc.plane_o[q] : sst.o[k][q];
+    const double x = gr ? 0.0 : sst.dim[k][0], y = gr ? 0.0 : sst.dim[k][1], z = gr ? 0.0 : sst.dim[k][2];
+    gs[S_DIM + 3*lane] = x; gs[S_DIM + 3*lane + 1] = y; gs[S_DIM + 3*lane + 2] = z;
+    const double hx = x / 2.0, hy = y / 2.0, hz = z / 2.0;
+    gs[S_RAD + lane] = sqrt((hx*hx + hy*hy) + hz*hz);
+  } else if (lane < MH_MAX_STATICS) gst[lane] = -1;
+#else
   const int nb = sc.nb, ntot = sc.nb + (sc.has_ground ? 1 : 0), npt = ntot * (ntot - 1) / 2;
+#endif
   // scene cache
   if (lane < nb) {
     gi[I_GEOM + lane] = sc.geom_type[lane];

@@ -18,6 +18,7 @@
 #include <vector>
 #include "../../include/moby_hip_io.h"
 #include "../../include/moby_hip_io_forces.h"
+#include "../../include/moby_hip_io_statics.h"
 
 namespace {
 
@@ -457,10 +458,13 @@ const char* mh_io_last_error(void) { return g_err; }
 namespace {
 struct DampGains { std::string body; double kl = 0.0, ka = 0.0, klsq = 0.0, kasq = 0.0; };
 // forces == NULL: mh_io_load_xml (gravity is the one recurrent force it takes); otherwise mh_io_load_xml_forces
-int load_xml_scene(const char* path, mh_io_scene* out, mh_world_forces* forces)
+// statics != NULL: mh_io_load_xml_statics (include/moby_hip_io_statics.h): every disabled body becomes a static of that record, none the scene's ground
+int load_xml_scene(const char* path, mh_io_scene* out, mh_world_forces* forces, mh_world_statics* statics = nullptr)
 {
   if (!path || !out) return fail("null argument");
   if (forces) std::memset(forces, 0, sizeof(*forces));
+  if (statics) std::memset(statics, 0, sizeof(*statics));
+  std::vector<std::string> stat;
   xmlDoc* doc = xmlReadFile(path, nullptr, XML_PARSE_NONET | XML_PARSE_NOERROR | XML_PARSE_NOWARNING);
   if (!doc) return fail("cannot parse %s", path);
   struct Guard { xmlDoc* d; ~Guard() { xmlFreeDoc(d); } } guard{doc};
@@ -598,6 +602,7 @@ int load_xml_scene(const char* path, mh_io_scene* out, mh_world_forces* forces)
       auto it = bodies.find(ca.str("dynamic-body-id"));
       if (it == bodies.end()) return fail("simulator: unknown body %s", ca.str("dynamic-body-id").c_str());
       if (it->second.enabled) dyn.push_back(it->first);
+      else if (statics) stat.push_back(it->first);
       else { if (!ground.empty()) return fail("more than one disabled body"); ground = it->first; }
     } else if (strcmp(nm, "RecurrentForce") == 0) {
       auto it = gravs.find(ca.str("recurrent-force-id"));
@@ -664,6 +669,33 @@ int load_xml_scene(const char* path, mh_io_scene* out, mh_world_forces* forces)
     for (int i = 0; i < 9; i++) sc.plane_R[i] = R[i];
     for (int i = 0; i < 3; i++) sc.plane_o[i] = G.x[i] + it->second.o[i];
   }
+  if (statics) {
+    std::sort(stat.begin(), stat.end());
+    const int n = (int)stat.size();
+    if (n > MH_MAX_STATICS || nb + n > MH_MAX_BODIES + 1)
+      return fail("%d enabled and %d disabled bodies (supported: at most %d statics and %d bodies in all)", nb, n, MH_MAX_STATICS, MH_MAX_BODIES + 1);
+    statics->n = n;
+    for (int k = 0; k < n; k++) {
+      const Body& G = bodies[stat[k]];
+      index[G.id] = nb + k;
+      snprintf(out->body_id[nb + k], MH_IO_ID_LEN, "%s", G.id.c_str());
+      auto it = prims.find(G.geom);
+      if (it == prims.end()) return fail("disabled body %s: no collision geometry with a known primitive", G.id.c_str());
+      const Prim& P = it->second;
+      if (P.type == 100) {                                          // the pose rules of the ground
+        if (G.rotated && P.posed) return fail("static %s: pose on both the body and the plane primitive is not supported", G.id.c_str());
+        const double* R = G.rotated ? G.R : P.R;
+        statics->type[k] = MH_STATIC_PLANE;
+        for (int i = 0; i < 9; i++) statics->R[k][i] = R[i];
+        for (int i = 0; i < 3; i++) statics->o[k][i] = G.x[i] + P.o[i];
+      } else if (P.type == MH_GEOM_BOX) {
+        if (P.posed) return fail("static %s: box primitive %s has a pose of its own (not supported)", G.id.c_str(), G.geom.c_str());
+        statics->type[k] = MH_STATIC_BOX;
+        for (int i = 0; i < 9; i++) statics->R[k][i] = G.R[i];
+        for (int i = 0; i < 3; i++) { statics->o[k][i] = G.x[i]; statics->dim[k][i] = P.dim[i]; }
+      } else return fail("disabled body %s carries a %s: a static body must carry a Plane or a Box", G.id.c_str(), P.type == MH_GEOM_SPHERE ? "Sphere" : "primitive of an unknown kind");
+    }
+  }
   if (forces) {
     if (!stokes_id.empty()) {
       forces->terms |= MH_FORCE_STOKES;
@@ -679,7 +711,7 @@ int load_xml_scene(const char* path, mh_io_scene* out, mh_world_forces* forces)
       }
     }
   }
-  const int ntot = nb + sc.has_ground;
+  const int ntot = nb + sc.has_ground + (statics ? statics->n : 0);
   auto pidx = [&](int i, int j) { if (i > j) std::swap(i, j); return i * ntot - (i * (i + 1)) / 2 + (j - i - 1); };
   for (const CP& p : cps) {
     if (!index.count(p.a) || !index.count(p.b)) continue;     // parameters for bodies outside the simulator (wheel.xml:40 has one commented out)
@@ -703,6 +735,12 @@ int mh_io_load_xml_forces(const char* path, mh_io_scene* out, mh_world_forces* f
 {
   if (!forces) return fail("null argument");
   return load_xml_scene(path, out, forces);
+}
+
+int mh_io_load_xml_statics(const char* path, mh_io_scene* out, mh_world_forces* forces, mh_world_statics* statics)
+{
+  if (!statics) return fail("null argument");
+  return load_xml_scene(path, out, forces, statics);
 }
 
 int mh_io_load_xml_artic(const char* path, mh_io_artic* out, double* q0, double* qd0, double* step_size)

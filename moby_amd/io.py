@@ -32,6 +32,8 @@ def load():
         lib.mh_io_load_xml.argtypes = [ctypes.c_char_p, ctypes.POINTER(mh_io_scene)]
         lib.mh_io_load_xml_forces.restype = ctypes.c_int
         lib.mh_io_load_xml_forces.argtypes = [ctypes.c_char_p, ctypes.POINTER(mh_io_scene), ctypes.POINTER(S.mh_world_forces)]
+        lib.mh_io_load_xml_statics.restype = ctypes.c_int
+        lib.mh_io_load_xml_statics.argtypes = [ctypes.c_char_p, ctypes.POINTER(mh_io_scene), ctypes.POINTER(S.mh_world_forces), ctypes.POINTER(S.mh_world_statics)]
         lib.mh_io_last_error.restype = ctypes.c_char_p
         lib.mh_io_format_row.restype = ctypes.c_int
         lib.mh_io_format_row.argtypes = [ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
@@ -53,22 +55,32 @@ def load_xml_forces(path):
     return _load_xml(path, forces) + (forces,)
 
 
+def load_xml_statics(path):
+    """load_xml_forces for a scene with several disabled bodies (include/moby_hip_io_statics.h): every one becomes a static body, none the scene's ground.
+    -> (mh_scene, state, body ids (enabled bodies in id order, then the statics in id order), step size, mh_world_forces, mh_world_statics)."""
+    forces, statics = S.mh_world_forces(), S.mh_world_statics()
+    return _load_xml(path, forces, statics) + (forces, statics)
+
+
 def load_xml(path):
     """-> (mh_scene, state (1, nb*13), body ids (enabled bodies in id order, then the ground), step size)."""
     return _load_xml(path, None)
 
 
-def _load_xml(path, forces):
+def _load_xml(path, forces, statics=None):
     lib = load()
     io = mh_io_scene()
-    rc = lib.mh_io_load_xml(os.fsencode(path), ctypes.byref(io)) if forces is None else lib.mh_io_load_xml_forces(os.fsencode(path), ctypes.byref(io), ctypes.byref(forces))
+    if statics is not None:
+        rc = lib.mh_io_load_xml_statics(os.fsencode(path), ctypes.byref(io), ctypes.byref(forces), ctypes.byref(statics))
+    else:
+        rc = lib.mh_io_load_xml(os.fsencode(path), ctypes.byref(io)) if forces is None else lib.mh_io_load_xml_forces(os.fsencode(path), ctypes.byref(io), ctypes.byref(forces))
     if rc != 0:
         raise SceneError(lib.mh_io_last_error().decode("utf-8", "replace"))
     sc = S.mh_scene()
     ctypes.memmove(ctypes.addressof(sc), ctypes.addressof(io.scene), ctypes.sizeof(S.mh_scene))
     nb = sc.nb
     st = np.array(io.state[:nb * S.MH_BODY_STATE], dtype=np.float64).reshape(1, nb * S.MH_BODY_STATE)
-    ids = [io.body_id[b].value.decode() for b in range(nb + sc.has_ground)]
+    ids = [io.body_id[b].value.decode() for b in range(nb + sc.has_ground + (0 if statics is None else statics.n))]
     return sc, st, ids, io.step_size
 
 

@@ -102,6 +102,47 @@ def make_forces(nb, stokes=None, damping=None):
     return f
 
 
+MH_MAX_STATICS = 8
+MH_STATIC_PLANE, MH_STATIC_BOX = 0, 1
+
+
+class mh_world_statics(ctypes.Structure):
+    """Static bodies of a scene beside its free ones (include/moby_hip.h, "Static bodies"): one set for all worlds of a batch.
+    Static k is body nb + has_ground + k of the scene's triangular pair arrays."""
+    _fields_ = [("n", ctypes.c_int), ("type", ctypes.c_int * MH_MAX_STATICS),
+                ("R", (ctypes.c_double * 9) * MH_MAX_STATICS), ("o", (ctypes.c_double * 3) * MH_MAX_STATICS),
+                ("dim", (ctypes.c_double * 3) * MH_MAX_STATICS)]
+
+
+def make_statics(items):
+    """``mh_world_statics`` from a sequence of dicts: ``dict(plane=True, R=3x3 or rpy=(r, p, y), o=(x, y, z))`` -- the plane's +Y is its normal, as
+    the ground's -- or ``dict(box=(xlen, ylen, zlen), R=... or rpy=..., o=centre)``.  R defaults to the identity, o to the origin."""
+    st = mh_world_statics()
+    items = list(items)
+    if len(items) > MH_MAX_STATICS:
+        raise ValueError("at most %d statics" % MH_MAX_STATICS)
+    st.n = len(items)
+    for k, it in enumerate(items):
+        R = np.asarray(it["R"], dtype=np.float64).reshape(3, 3) if "R" in it else (rpy_to_R(*it["rpy"]) if "rpy" in it else np.eye(3))
+        o = it.get("o", (0.0, 0.0, 0.0))
+        st.type[k] = MH_STATIC_BOX if "box" in it else MH_STATIC_PLANE
+        for q in range(9):
+            st.R[k][q] = R.flat[q]
+        for q in range(3):
+            st.o[k][q] = o[q]
+            st.dim[k][q] = it["box"][q] if "box" in it else 0.0
+    return st
+
+
+def set_pair_params(sc, i, j, ntot, epsilon=0.0, mu_coulomb=0.0, mu_viscous=0.0, compliance=0.0, nk=4, enabled=1):
+    """Contact parameters of pair (i, j) of a scene whose pair arrays run over ntot = nb + has_ground + (number of statics) bodies."""
+    p = pair_index(min(i, j), max(i, j), ntot)
+    sc.cp_epsilon[p], sc.cp_mu_coulomb[p], sc.cp_mu_viscous[p], sc.cp_compliance[p] = epsilon, mu_coulomb, mu_viscous, compliance
+    sc.cp_nk[p] = max(4, nk)
+    sc.pair_enabled[p] = enabled
+    return p
+
+
 def rpy_to_quat(roll, pitch, yaw):
     """Quatd::rpy as Ravelin forms it (half-angle products, ZYX), x y z w.  The XML readers turn every ``rpy`` attribute
     into a quaternion first (XMLTree.cpp / RigidBody.cpp:201-210, Primitive.cpp:273-279)."""

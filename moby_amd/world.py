@@ -16,19 +16,25 @@ from . import scene as S
 class WorldBatch:
     """B worlds of one scene; numpy host arrays in/out (copies through the library)."""
 
-    def __init__(self, scene, state, aux=None, seed=1, forces=None):
+    def __init__(self, scene, state, aux=None, seed=1, forces=None, statics=None):
         self.scene = scene
         self.state = np.ascontiguousarray(state, dtype=np.float64)
         self.B = self.state.shape[0]
         assert self.state.shape[1] == scene.nb * S.MH_BODY_STATE
         self.aux = S.new_aux(self.B, seed) if aux is None else aux
         self.forces = forces       # S.mh_world_forces (S.make_forces) or None: the scene's recurrent forces
+        self.statics = statics     # S.mh_world_statics (S.make_statics, io.load_xml_statics) or None: static bodies beside the scene's ground
 
     def step(self, dt, nsteps=1, want_traj=False, wrench=None):
         """wrench: (B, nb, 6) or (rows >= nsteps, B, nb, 6) host array (fx fy fz tx ty tz per world and body), or None."""
         if self.forces is not None or wrench is not None:
             return self._step_forced(dt, nsteps, want_traj, wrench)
         lib = _lib.load()
+        if self.statics is not None:
+            traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
+            _lib.check(lib.mh_world_step_batch_statics(ctypes.addressof(self.scene), None, self.B, float(dt), int(nsteps), self.state.ctypes.data,
+                                                       self.aux.ctypes.data, None if traj is None else traj.ctypes.data, ctypes.addressof(self.statics)))
+            return traj
         traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
         rc = lib.mh_world_step_batch(ctypes.addressof(self.scene), self.B, float(dt), int(nsteps),
                                      self.state.ctypes.data, self.aux.ctypes.data,
@@ -41,11 +47,12 @@ class WorldBatch:
         takes one (a DEVICE array)"""
         if wrench is None:
             traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
-            _lib.check(_lib.load().mh_world_step_batch_forces(ctypes.addressof(self.scene), ctypes.addressof(self.forces), self.B, float(dt), int(nsteps),
-                                                              self.state.ctypes.data, self.aux.ctypes.data, None if traj is None else traj.ctypes.data))
+            _lib.check(_lib.load().mh_world_step_batch_statics(ctypes.addressof(self.scene), ctypes.addressof(self.forces), self.B, float(dt), int(nsteps),
+                                                               self.state.ctypes.data, self.aux.ctypes.data, None if traj is None else traj.ctypes.data,
+                                                               None if self.statics is None else ctypes.addressof(self.statics)))
             return traj
         import torch
-        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux)
+        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics)
         try:
             if self.forces is not None:
                 dev.set_forces(self.forces)
@@ -68,12 +75,15 @@ class WorldBatchDevice:
     """Same, with state/aux resident in HBM behind an ``mh_world_batch`` handle;
     ``step`` is asynchronous on the given (torch) stream."""
 
-    def __init__(self, scene, state, seed=1, aux=None):
+    def __init__(self, scene, state, seed=1, aux=None, statics=None):
         lib = _lib.load()
         self.scene = scene
         self.B = state.shape[0]
         self.handle = ctypes.c_void_p()
-        _lib.check(lib.mh_world_batch_create(ctypes.addressof(scene), self.B, ctypes.byref(self.handle)))
+        if statics is None:
+            _lib.check(lib.mh_world_batch_create(ctypes.addressof(scene), self.B, ctypes.byref(self.handle)))
+        else:
+            _lib.check(lib.mh_world_batch_create_statics(ctypes.addressof(scene), ctypes.addressof(statics), self.B, ctypes.byref(self.handle)))
         st = np.ascontiguousarray(state, dtype=np.float64)
         aux = S.new_aux(self.B, seed) if aux is None else np.ascontiguousarray(aux)      # aux given: resume from a checkpoint
         _lib.check(lib.mh_world_batch_upload(self.handle, st.ctypes.data, aux.ctypes.data))
