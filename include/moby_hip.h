@@ -407,7 +407,6 @@ int mh_world_step_batch_forces(const mh_scene* scene, const mh_world_forces* for
 #define MH_MAX_STATICS 8
 #define MH_STATIC_PLANE 0
 #define MH_STATIC_BOX   1
-#ifndef MH_ABI_WITHOUT_WORLD_STATICS   /* defined by the library's own world code objects that know no statics, so that they compile from the text they had */
 typedef struct mh_world_statics {
   int    n;                               /* 0..MH_MAX_STATICS, nb + has_ground + n <= MH_MAX_BODIES + 1 */
   int    type[MH_MAX_STATICS];            /* MH_STATIC_* */
@@ -423,7 +422,6 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
 /* Host convenience: mh_world_step_batch_forces with static bodies (forces and statics may each be NULL). */
 int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
                                 double* state, mh_world_aux* aux, double* traj, const mh_world_statics* statics);
-#endif
 
 #ifdef __cplusplus
 }

@@ -8,8 +8,6 @@
 #include <vector>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#include "mh_world_bsp.h"
-#include "mh_world_st.h"
 #include "mh_lcp_wave.h"
 // the workgroup-per-problem solver (n > 64) lives in mh_lcp_blk.hip / mh_lcp_blkw.hip: two thread geometries, 256 threads (four
 // problems per CU: throughput when the batch is larger than the chip) and 1024 threads (one problem per CU with 16 waves to hide

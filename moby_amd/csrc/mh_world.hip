@@ -1,5 +1,5 @@
 // Host side of the many-worlds stepping ABI (include/moby_hip.h: mh_world_batch_*).  The kernels live in
-// mh_world_{small,wheel,large}.hip; this file chooses the variant for a scene and owns the device buffers.
+// mh_world_{small,wheel,large,large_bsp,large_st}.hip; this file chooses the build for a scene (g_builds) and owns the device buffers.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -8,8 +8,6 @@
 #include <algorithm>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#include "mh_world_bsp.h"
-#include "mh_world_st.h"
 
 namespace mh {
 // layouts of the constant tables of mh_world_common.h / mh_lcp_wave.h (checked by size in upload_tables)
@@ -18,6 +16,21 @@ struct Pow10TableH { double v[64]; };
 }
 #include <mutex>
 namespace {
+// The builds of the world kernel (mh_world_wave.inc), one row each: the plain code object, the one with forces in its forward dynamics (MHW_FORCES) and the
+// one with the phase profiler's stamps -- null where there is none: mh_world_batch_profile then launches the production object and reports zeros.
+enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_COUNT };
+struct world_build {
+  const mh_world_variant* (*plain)();
+  const mh_world_forced_variant* (*forced)();
+  const mh_world_variant* (*prof)();
+};
+const world_build g_builds[WB_COUNT] = {
+  { mh_world_variant_small,     mh_world_variant_small_forces,     mh_world_variant_small_prof },
+  { mh_world_variant_wheel,     mh_world_variant_wheel_forces,     mh_world_variant_wheel_prof },
+  { mh_world_variant_large,     mh_world_variant_large_forces,     mh_world_variant_large_prof },
+  { mh_world_variant_large_bsp, mh_world_variant_large_bsp_forces, nullptr },     // box-sphere pairs (MHW_BSP)
+  { mh_world_variant_large_st,  mh_world_variant_large_st_forces,  nullptr },     // + static bodies (MHW_STATICS)
+};
 // The __constant__ tables are one copy per DEVICE (hipMemcpyToSymbol writes the current device's): uploaded once per device, keyed on the
 // device current at create, under a lock -- as mh_artic_batch_create does for its own table.
 std::mutex g_tables_mu;
@@ -34,13 +47,12 @@ hipError_t init_tables()
     }
   mh::Pow10TableH p10;
   for (int i = 0; i < 64; i++) p10.v[i] = std::pow(10.0, (double)(i - 32)); // LCP.cpp:285
-  const mh_world_variant* vs[8] = { mh_world_variant_small(), mh_world_variant_wheel(), mh_world_variant_large(),
-                                    mh_world_variant_small_prof(), mh_world_variant_wheel_prof(), mh_world_variant_large_prof(),
-                                    mh_world_variant_large_bsp(), mh_world_variant_large_st() };     // (one copy of the tables per code object)
-  for (int i = 0; i < 8 && g_tables_err == hipSuccess; i++) g_tables_err = vs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
-  const mh_world_forced_variant* fs[5] = { mh_world_variant_small_forces(), mh_world_variant_wheel_forces(), mh_world_variant_large_forces(),
-                                           mh_world_variant_large_bsp_forces(), mh_world_variant_large_st_forces() };
-  for (int i = 0; i < 5 && g_tables_err == hipSuccess; i++) g_tables_err = fs[i]->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  for (int i = 0; i < WB_COUNT && g_tables_err == hipSuccess; i++) {                                 // (one copy of the tables per code object)
+    const world_build& r = g_builds[i];
+    g_tables_err = r.plain()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+    if (g_tables_err == hipSuccess) g_tables_err = r.forced()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+    if (g_tables_err == hipSuccess && r.prof) g_tables_err = r.prof()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  }
   return g_tables_err;
 }
 hipError_t tables_for_current_device()
@@ -137,16 +149,13 @@ struct mh_world_batch {
   mh_scene scene;
   int B;
   int nmax;
-  int variant;               // 0 small, 1 large, 2 wheel
-  bool st;                   // the large variant's statics build (mh_world_large_st*.hip): created with statics, or a box-sphere batch under mh_debug_set(16, 1)
-  bool bsp;                  // the large variant's box-sphere build (mh_world_large_bsp*.hip): an enabled box-sphere pair, or mh_debug_set(15, 1) at create
-  mh_world_kernel kernel;
-  int ph_count;
+  int build;                 // row of g_builds (WB_*)
+  mh_world_kernel kernel;    // that row's plain object
   mh_scene* d_scene;
   double* d_lu_ws;
   double* d_state;
   mh_world_aux* d_aux;
-  mh_world_forced_kernel fkernel;   // the same variant built with MHW_FORCES: launched while forces are stored or when a wrench is passed
+  mh_world_forced_kernel fkernel;   // that row's forced object: launched while forces are stored or when a wrench is passed
   bool has_forces;                  // mh_world_batch_set_forces stored terms != 0
   mh_world_forces* d_forces;        // their device copy (allocated by the first set_forces)
 };
@@ -214,21 +223,20 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
     for (int b = 0; b < scene->nb; b++) if (scene->geom_type[b] == MH_GEOM_SPOKES) noslip = true;
     for (int b = 0; b < scene->nb; b++) if (scene->geom_type[b] == MH_GEOM_BOX) box = true;
     for (int p = 0; p < npairs; p++) if (scene->pair_enabled[p] && scene->cp_mu_coulomb[p] >= 1e2) noslip = true;
-    if (!noslip && !box && scene->nb <= 4 && npairs <= 6 && scene->lcp_n_max > 0 && scene->lcp_n_max <= 56) { wb->variant = 0; wb->kernel = mh_world_variant_small()->kernel; }
-    else if (noslip && !box && scene->nb <= 2 && npairs <= 3) { wb->variant = 2; wb->kernel = mh_world_variant_wheel()->kernel; }
-    else { wb->variant = 1; wb->kernel = mh_world_variant_large()->kernel; }
+    if (!noslip && !box && scene->nb <= 4 && npairs <= 6 && scene->lcp_n_max > 0 && scene->lcp_n_max <= 56) wb->build = WB_SMALL;
+    else if (noslip && !box && scene->nb <= 2 && npairs <= 3) wb->build = WB_WHEEL;
+    else wb->build = WB_LARGE;
     // an enabled pair of a box and a sphere (two free bodies) needs the large variant's box-sphere build; every other scene takes what it took
     bool bsp = false;
     for (int i = 0; i < scene->nb; i++) for (int j = i + 1; j < scene->nb; j++) {
       const int gi_ = scene->geom_type[i], gj_ = scene->geom_type[j];
       if (((gi_ == MH_GEOM_BOX && gj_ == MH_GEOM_SPHERE) || (gi_ == MH_GEOM_SPHERE && gj_ == MH_GEOM_BOX)) && scene->pair_enabled[i * ntot - (i * (i + 1)) / 2 + (j - i - 1)]) bsp = true;
     }
-    wb->bsp = wb->variant == 1 && (bsp || mh_g_debug_world_bsp != 0);
-    if (wb->bsp) wb->kernel = mh_world_variant_large_bsp()->kernel;
+    if (wb->build == WB_LARGE && (bsp || mh_g_debug_world_bsp != 0)) wb->build = WB_LARGE_BSP;       // (key 15: every large batch through the box-sphere build)
     // static bodies need the statics build; every other batch launches what it launched (key 16: the box-sphere batches through the statics build)
-    wb->st = nstat > 0 || (wb->bsp && mh_g_debug_world_st != 0);
-    if (wb->st) { wb->variant = 1; wb->bsp = true; wb->kernel = mh_world_variant_large_st()->kernel; }
-    wb->fkernel = wb->st ? mh_world_variant_large_st_forces()->kernel : wb->bsp ? mh_world_variant_large_bsp_forces()->kernel : (wb->variant == 0 ? mh_world_variant_small_forces() : wb->variant == 2 ? mh_world_variant_wheel_forces() : mh_world_variant_large_forces())->kernel;
+    if (nstat > 0 || (wb->build == WB_LARGE_BSP && mh_g_debug_world_st != 0)) wb->build = WB_LARGE_ST;
+    wb->kernel = g_builds[wb->build].plain()->kernel;
+    wb->fkernel = g_builds[wb->build].forced()->kernel;
     wb->has_forces = false; wb->d_forces = nullptr;
   }
   wb->d_scene = nullptr; wb->d_state = nullptr; wb->d_aux = nullptr; wb->d_lu_ws = nullptr;
@@ -344,7 +352,7 @@ int mh_world_batch_step_wrench(mh_world_batch* wb, void* stream, double dt, int 
   return launch_step(wb, (hipStream_t)stream, ids_dev ? count : wb->B, dt, nsteps, traj_dev, nullptr, ids_dev, wrench_dev, rows);
 }
 
-int mh_world_profile_phase_count(void) { return mh_world_variant_large()->ph_count; }
+int mh_world_profile_phase_count(void) { return g_builds[WB_LARGE].plain()->ph_count; }
 
 // diagnostic: one launch with per-phase cycle accumulators (mh::PH_*), averaged over worlds on the host
 int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* phase_cycles, int nphase)
@@ -352,17 +360,17 @@ int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* ph
   if (!wb || !phase_cycles) return fail(MH_ERR_INVALID_ARG, "null argument");
   MH_ON_DEVICE(wb);
   unsigned long long* dprof = nullptr;
-  const int PHC = mh_world_variant_large()->ph_count;   // the same enum in every variant
+  const int PHC = mh_world_profile_phase_count();       // the same enum in every build
   const size_t sz = (size_t)wb->B * PHC * sizeof(unsigned long long);
   MH_HIP(hipMalloc(&dprof, sz));
   MH_HIP(hipMemset(dprof, 0, sz));
-  // the PROFILE build of the batch's variant: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
-  const mh_world_kernel kprof = (wb->variant == 0 ? mh_world_variant_small_prof() : wb->variant == 2 ? mh_world_variant_wheel_prof() : mh_world_variant_large_prof())->kernel;
+  // the PROFILE object of the batch's build: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
+  const world_build& row = g_builds[wb->build];
   // (a batch with stored forces: the forced production kernel -- it steps the worlds under their forces and has no stamps, so every cycle count is 0)
-  // (a batch on the box-sphere build: likewise, there is no stamped build of it -- the production kernel steps the worlds, every cycle count is 0)
-  if (wb->has_forces || wb->bsp) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
+  // (a batch on the box-sphere or the statics build: likewise, there is no stamped object of it -- the production kernel steps the worlds, every cycle count is 0)
+  if (wb->has_forces || !row.prof) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
   else
-  hipLaunchKernelGGL(kprof, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
+  hipLaunchKernelGGL(row.prof()->kernel, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
                      (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, (double*)nullptr, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, dprof, (const int*)nullptr);
   hipError_t e = hipDeviceSynchronize();
   std::vector<unsigned long long> h((size_t)wb->B * PHC);

@@ -2,10 +2,8 @@
 // scene enables at least one box-sphere pair, or under mh_debug_set(15, 1).  The constants are mh_world_large.hip's: <= 8 bodies, <= 36 pairs, <= 40 contacts,
 // <= 24 rows per island, every feature.  A translation unit of its own, so that the plain large kernels stay the code objects they were.
 #include <hip/hip_runtime.h>
-#define MH_ABI_WITHOUT_WORLD_STATICS 1   /* this object knows no static bodies: the public header expands to the text it had for it */
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#include "mh_world_bsp.h"
 #if defined(MH_FORCES_BUILD)   /* mh_world_large_bsp_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
 #define MHW_NS large_bsp_forces
 #define MHW_VARIANT_GETTER mh_world_variant_large_bsp_forces
@@ -14,7 +12,6 @@
 #else
 #define MHW_NS large_bsp
 #define MHW_VARIANT_GETTER mh_world_variant_large_bsp
-#define MHW_VARIANT_T mh_world_variant
 #endif
 #define MHW_BSP 1
 #define MHW_NOSLIP 1
@@ -26,17 +23,3 @@
 #define MHW_MAX_GROWS 24
 #define MHW_WAVES_PER_SIMD 2
 #include "mh_world_wave.inc"
-
-static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes)
-{
-  if (fric_bytes != sizeof(mh::FricTable) || pow10_bytes != sizeof(mh::Pow10Table)) return hipErrorInvalidValue;
-  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_fric), fric, fric_bytes);
-  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_pow10), pow10, pow10_bytes);
-  return e;
-}
-
-const MHW_VARIANT_T* MHW_VARIANT_GETTER()
-{
-  static const MHW_VARIANT_T v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
-  return &v;
-}

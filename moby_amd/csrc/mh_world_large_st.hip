@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#include "mh_world_st.h"
 #if defined(MH_FORCES_BUILD)   /* mh_world_large_st_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
 #define MHW_NS large_st_forces
 #define MHW_VARIANT_GETTER mh_world_variant_large_st_forces
@@ -14,7 +13,6 @@
 #else
 #define MHW_NS large_st
 #define MHW_VARIANT_GETTER mh_world_variant_large_st
-#define MHW_VARIANT_T mh_world_variant
 #endif
 #define MHW_STATICS 1
 #define MHW_BSP 1
@@ -27,17 +25,3 @@
 #define MHW_MAX_GROWS 24
 #define MHW_WAVES_PER_SIMD 2
 #include "mh_world_wave.inc"
-
-static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes)
-{
-  if (fric_bytes != sizeof(mh::FricTable) || pow10_bytes != sizeof(mh::Pow10Table)) return hipErrorInvalidValue;
-  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_fric), fric, fric_bytes);
-  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_pow10), pow10, pow10_bytes);
-  return e;
-}
-
-const MHW_VARIANT_T* MHW_VARIANT_GETTER()
-{
-  static const MHW_VARIANT_T v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
-  return &v;
-}

@@ -37,13 +37,23 @@
 //     workspace of the rare factorisations that do not fit LDS: all `nsteps` steps run inside one launch.
 //
 // This file is compiled once per variant: the includer defines MHW_NS (namespace), MHW_NB, MHW_MAX_PAIRS,
-// MHW_MAX_CONTACTS, MHW_MAX_ROWS, MHW_MAX_GROWS, MHW_WAVES_PER_SIMD and the feature switches MHW_NOSLIP
-// (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).  MHW_FORCES (1 in mh_world_*_forces.hip, undefined = 0 elsewhere) adds the scene's
-// recurrent forces and the caller's wrench to the forward dynamics; every line it adds sits under #if MHW_FORCES.
-// MHW_BSP (1 in mh_world_large_bsp*.hip, undefined = 0 elsewhere; needs MHW_BOX) adds box-sphere contacts between two free bodies (include/moby_hip.h,
-// "box-sphere pairs"); every line it adds or alters sits under #if MHW_BSP, so the other code objects compile from the text they had.
-// MHW_STATICS (1 in mh_world_large_st*.hip, undefined = 0 elsewhere; needs MHW_BSP) adds several static bodies -- planes and boxes, each with a frame of its
-// own -- beside the free bodies (include/moby_hip.h, "static bodies"); every line it adds or alters sits under #if MHW_STATICS.
+// MHW_MAX_CONTACTS, MHW_MAX_ROWS, MHW_MAX_GROWS, MHW_WAVES_PER_SIMD, MHW_VARIANT_GETTER (the host-side getter at the end of this file) and the feature
+// switches MHW_NOSLIP (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).  Three more switches are 1 in the units named and undefined = 0
+// elsewhere:
+//   MHW_FORCES  (mh_world_*_forces.hip) adds the scene's recurrent forces and the caller's wrench to the forward dynamics; every line it adds sits under
+//               #if MHW_FORCES.
+//   MHW_BSP     (mh_world_large_bsp*.hip, mh_world_large_st*.hip; needs MHW_BOX) adds box-sphere contacts between two free bodies (include/moby_hip.h,
+//               "box-sphere pairs").
+//   MHW_STATICS (mh_world_large_st*.hip; needs MHW_BSP) adds several static bodies -- planes and boxes, each with a frame of its own -- beside the free
+//               bodies (include/moby_hip.h, "static bodies").
+// The geometry that mirrors the reference is written ONCE for all builds.  A plane is always named by its body index; the builds differ in a few small
+// accessors only, and these are all the MHW_BSP / MHW_STATICS conditionals of the file:
+//   MHW_STATICS  the gs / gst tables (declaration; filled in the kernel entry, with ntot); plane_R / plane_o / plane_body; is_ground / is_sbox (is_sbox is
+//                `false` without); the table arm of box_frame; the static-box arm of bounds()
+//   MHW_BSP      the box-sphere section itself (is_sphere ... bsp_sdist) and its two call sites in pair_geom and contact_geom_body; box_plane_pair; the
+//                box-box arm of broad_phase (without MHW_BSP a box-sphere pair is not kept either)
+// A feature that changes this file keeps the INSTRUCTIONS of the builds it does not concern, not their text: tools/world_asm_diff.py compares every world
+// code object of two source trees function by function (DESIGN.md 4.1).
 #include "mh_world_common.h"
 
 #define MHW_NS_MAXC ((MHW_MAX_CONTACTS < 6) ? MHW_MAX_CONTACTS : 6)   /* contacts of a no-slip island */
@@ -195,34 +205,30 @@ MH_DEV void pair_bodies(int p, int& a, int& b) {
   while (rem >= ntot - 1 - i) { rem -= ntot - 1 - i; i++; }
   a = i; b = i + 1 + rem;
 }
+// ---- the plane of a body-plane pair.  `pl` is the plane's body index (>= nb; the scene's ground is nb).  These three accessors hold the build switch; the
+// geometry below them is written once.  With MHW_STATICS every static plane has a frame of its own in the gs table; without, there is one plane, the
+// scene's ground, and `pl` is not looked at: plane_body is then gi[I_NB], not `pl`, so that enabled(plane_body(pl)) folds to false at compile time.
+// (plane_body is a macro: as an inline function returning gi[I_NB] it moved the exec-mask code of ca_step in the large kernels, tools/world_asm_diff.py.) ----
 #if MHW_STATICS
-// the frame of static plane `pl` (a body index >= nb; the scene's ground is nb), from the table: the same statements over that plane's R and o
-MH_DEV V3 plane_n(int pl) { const double* R = gs + S_R + 9 * (pl - gi[I_NB]); return v3(R[1], R[4], R[7]); }
+MH_DEV const double* plane_R(int pl) { return gs + S_R + 9 * (pl - gi[I_NB]); }
+MH_DEV const double* plane_o(int pl) { return gs + S_O + 3 * (pl - gi[I_NB]); }
+#define plane_body(pl) (pl)
+#else
+MH_DEV const double* plane_R(int) { return gd + D_PLANE_R; }
+MH_DEV const double* plane_o(int) { return gd + D_PLANE_O; }
+#define plane_body(pl) gi[I_NB]
+#endif
+MH_DEV V3 plane_n(int pl) { const double* R = plane_R(pl); return v3(R[1], R[4], R[7]); }
 MH_DEV V3 to_plane(V3 p, int pl) {
-  const int s = pl - gi[I_NB];
-  const double* R = gs + S_R + 9 * s; V3 d = p - v3(gs[S_O + 3*s], gs[S_O + 3*s + 1], gs[S_O + 3*s + 2]);
+  const double* R = plane_R(pl); const double* o = plane_o(pl); V3 d = p - v3(o[0], o[1], o[2]);
   return v3((R[0]*d.x + R[3]*d.y) + R[6]*d.z, (R[1]*d.x + R[4]*d.y) + R[7]*d.z, (R[2]*d.x + R[5]*d.y) + R[8]*d.z);
 }
 MH_DEV V3 from_plane(V3 p, int pl) {
-  const int s = pl - gi[I_NB];
-  const double* R = gs + S_R + 9 * s;
-  return v3(gs[S_O + 3*s] + ((R[0]*p.x + R[1]*p.y) + R[2]*p.z),
-            gs[S_O + 3*s + 1] + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z),
-            gs[S_O + 3*s + 2] + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
+  const double* R = plane_R(pl); const double* o = plane_o(pl);
+  return v3(o[0] + ((R[0]*p.x + R[1]*p.y) + R[2]*p.z),
+            o[1] + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z),
+            o[2] + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
 }
-#else
-MH_DEV V3 plane_n() { return v3(gd[D_PLANE_R + 1], gd[D_PLANE_R + 4], gd[D_PLANE_R + 7]); }
-MH_DEV V3 to_plane(V3 p) {
-  const double* R = gd + D_PLANE_R; V3 d = p - v3(gd[D_PLANE_O], gd[D_PLANE_O + 1], gd[D_PLANE_O + 2]);
-  return v3((R[0]*d.x + R[3]*d.y) + R[6]*d.z, (R[1]*d.x + R[4]*d.y) + R[7]*d.z, (R[2]*d.x + R[5]*d.y) + R[8]*d.z);
-}
-MH_DEV V3 from_plane(V3 p) {
-  const double* R = gd + D_PLANE_R;
-  return v3(gd[D_PLANE_O] + ((R[0]*p.x + R[1]*p.y) + R[2]*p.z),
-            gd[D_PLANE_O + 1] + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z),
-            gd[D_PLANE_O + 2] + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
-}
-#endif
 MH_DEV void orthonormal_basis(V3 n, V3& s, V3& t) {
   const double ax = fabs(n.x), ay = fabs(n.y), az = fabs(n.z);
   V3 e;
@@ -273,19 +279,11 @@ MH_DEV V3 box_vertex(int b, int i) {
   return v3(c.x + ((R[0]*p.x + R[1]*p.y) + R[2]*p.z), c.y + ((R[3]*p.x + R[4]*p.y) + R[5]*p.z), c.z + ((R[6]*p.x + R[7]*p.y) + R[8]*p.z));
 }
 // find_contacts_plane_generic(plane, box) (CCD.inl:848-886): bit i set <=> vertex i is within TOL (<=) of the plane
-#if MHW_STATICS
 MH_DEV unsigned box_contact_mask(int b, double TOL, int pl) {
   unsigned m = 0;
   for (int i = 0; i < 8; i++) { const V3 pp = to_plane(box_vertex(b, i), pl); if (pp.y <= TOL) m |= 1u << i; }
   return m;
 }
-#else
-MH_DEV unsigned box_contact_mask(int b, double TOL) {
-  unsigned m = 0;
-  for (int i = 0; i < 8; i++) { const V3 pp = to_plane(box_vertex(b, i)); if (pp.y <= TOL) m |= 1u << i; }
-  return m;
-}
-#endif
 MH_DEV bool rel_equal(double x, double y) {                         // CompGeom.h:110
   const double ax = fabs(x), ay = fabs(y);
   const double m1 = (ay > 1.0) ? ay : 1.0; const double m = (ax > m1) ? ax : m1;
@@ -298,13 +296,17 @@ MH_DEV bool collinear(V3 a, V3 b, V3 c) {                           // CompGeom.
 #endif
 #if MHW_BSP
 // ---- box-sphere pairs of two free bodies (include/moby_hip.h).  The box is the reference's geometry A whichever body has the lower id; the frames are
-// the bodies' own (box centre = COM, box axes = rot(box)).  Operation order = tests/native/world_boxsphere_ref.cpp (= artic_boxsphere_ref.cpp):
+// the bodies' own (box centre = COM, box axes = rot(box)), a static box's its table row (box_frame).  Operation order = tests/native/world_boxsphere_ref.cpp (= artic_boxsphere_ref.cpp):
 // three-term sums as (a + b) + c.  Each function forms the box rotation once. ----
 MH_DEV bool is_sphere(int b) { return b < gi[I_NB] && gi[I_GEOM + b] == MH_GEOM_SPHERE; }
 #if MHW_STATICS
 MH_DEV bool is_static(int b, int type) { const int s = b - gi[I_NB]; return s >= 0 && s < MH_MAX_STATICS && b < gi[I_NTOT] && gst[s] == type; }
 MH_DEV bool is_ground(int b) { return is_static(b, MH_STATIC_PLANE); }                 // "a static plane": the scene's ground or any other
 MH_DEV bool is_sbox(int b) { return is_static(b, MH_STATIC_BOX); }
+#else
+MH_DEV bool is_ground(int b) { return b == gi[I_NB]; }
+MH_DEV bool is_sbox(int) { return false; }
+#endif
 MH_DEV bool bsp_pair(int a, int b, int& bx, int& sp) {
   if (is_box(a) && is_sphere(b)) { bx = a; sp = b; return true; }
   if (is_sphere(a) && (is_box(b) || is_sbox(b))) { bx = b; sp = a; return true; }       // (a static has the higher index: it is never a)
@@ -312,40 +314,27 @@ MH_DEV bool bsp_pair(int a, int b, int& bx, int& sp) {
 }
 // rotation, centre and half lengths of box bx: a body's own frame, or a static box's from the table
 MH_DEV void box_frame(int bx, double R[9], V3& cb, V3& h) {
-  if (bx < gi[I_NB]) {
-    rot(bx, R); cb = X(bx);
-    h = v3(gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5);
-  } else {
+#if MHW_STATICS
+  if (bx >= gi[I_NB]) {
     const int s = bx - gi[I_NB];
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = gs[S_R + 9*s + k];
     cb = v3(gs[S_O + 3*s], gs[S_O + 3*s + 1], gs[S_O + 3*s + 2]);
     h = v3(gs[S_DIM + 3*s] * 0.5, gs[S_DIM + 3*s + 1] * 0.5, gs[S_DIM + 3*s + 2] * 0.5);
+    return;
   }
-}
-#else
-MH_DEV bool is_ground(int b) { return b == gi[I_NB]; }
-MH_DEV bool bsp_pair(int a, int b, int& bx, int& sp) {
-  if (is_box(a) && is_sphere(b)) { bx = a; sp = b; return true; }
-  if (is_sphere(a) && is_box(b)) { bx = b; sp = a; return true; }
-  return false;
-}
 #endif
+  rot(bx, R); cb = X(bx);
+  h = v3(gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5);
+}
 MH_DEV V3 mat_v(const double R[9], V3 p) { return v3((R[0]*p.x + R[1]*p.y) + R[2]*p.z, (R[3]*p.x + R[4]*p.y) + R[5]*p.z, (R[6]*p.x + R[7]*p.y) + R[8]*p.z); }
 MH_DEV V3 matT_v(const double R[9], V3 p) { return v3((R[0]*p.x + R[3]*p.y) + R[6]*p.z, (R[1]*p.x + R[4]*p.y) + R[7]*p.z, (R[2]*p.x + R[5]*p.y) + R[8]*p.z); }
 MH_DEV double clampd(double c, double h) { return (c < -h) ? -h : ((c > h) ? h : c); }
 // BoxPrimitive::calc_closest_points (BoxPrimitive.cpp:183-254; the QP's fixed point is the clamp) + find_contacts_box_sphere (CCD.inl:1208-1259)
 MH_DEV int bsp_contact(int bx, int sp, double TOL, V3& pt, V3& n, double& dist) {
-#if MHW_STATICS
   double R[9]; V3 cb, h; box_frame(bx, R, cb, h);
   const V3 cS = X(sp);
   const V3 c = matT_v(R, cS - cb);
-#else
-  double R[9]; rot(bx, R);
-  const V3 cb = X(bx), cS = X(sp);
-  const V3 c = matT_v(R, cS - cb);
-  const V3 h = v3(gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5);
-#endif
   const double Rs = gd[D_RADIUS + sp];
   const V3 p = v3(clampd(c.x, h.x), clampd(c.y, h.y), clampd(c.z, h.z));
   V3 u = p - c;
@@ -376,19 +365,11 @@ MH_DEV int bsp_contact(int bx, int sp, double TOL, V3& pt, V3& n, double& dist) 
 }
 // BoxPrimitive::calc_signed_dist for a sphere (BoxPrimitive.cpp:256-276, 788-836): pA the box point, pB the sphere point
 MH_DEV double bsp_sdist(int bx, int sp, V3& pA, V3& pB) {
-#if MHW_STATICS
   double R[9]; V3 cb, hv; box_frame(bx, R, cb, hv);
   const V3 cS = X(sp);
   const V3 cv = matT_v(R, cS - cb);
   const double c[3] = { cv.x, cv.y, cv.z };
   const double h[3] = { hv.x, hv.y, hv.z };
-#else
-  double R[9]; rot(bx, R);
-  const V3 cb = X(bx), cS = X(sp);
-  const V3 cv = matT_v(R, cS - cb);
-  const double c[3] = { cv.x, cv.y, cv.z };
-  const double h[3] = { gd[D_GDIM + 3*bx] * 0.5, gd[D_GDIM + 3*bx + 1] * 0.5, gd[D_GDIM + 3*bx + 2] * 0.5 };
-#endif
   const double Rs = gd[D_RADIUS + sp];
   double cl[3] = { c[0], c[1], c[2] };
   bool inside = true; double sq = 0.0, in = -MHW_INF;
@@ -406,6 +387,14 @@ MH_DEV double bsp_sdist(int bx, int sp, V3& pA, V3& pB) {
   else pB = cS + mat_v(R, v) * ((Rs + ((0.0 < dist) ? 0.0 : dist)) / vn);
   return dist;
 }
+#endif
+// "box against a plane" (PlanePrimitive's and CCD's polyhedron-plane paths); with MHW_BSP a box-sphere pair follows the sphere rules instead.  Without it a
+// box body's only kept partner is the ground (broad_phase).  (A macro: as an inline function its && reached gen_contacts as a value and the statics
+// build's gen_contacts came out 8 bytes longer, tools/world_asm_diff.py.)
+#if MHW_BSP
+#define box_plane_pair(a, b) (is_box(a) && is_ground(b))
+#else
+#define box_plane_pair(a, b) is_box(a)
 #endif
 
 // ---- pair-lane geometry ---------------------------------------------------------------------
@@ -437,12 +426,9 @@ MHW_FN int broad_phase(double dt, int out_off) {
       // the wheel is removed from CCD's body list and (ground, wheel) is appended unconditionally,
       // after CCD's pairs (coldet-plugin.cpp:53-74)
       spk = true; keep = is_spokes(a) && b == gi[I_NB];
-#if MHW_STATICS
+#if MHW_BSP
     } else if (is_box(a) && (is_box(b) || is_sbox(b))) {
-      keep = false;                                                 // box-box, a static box included: rejected at create unless disabled
-#elif MHW_BSP
-    } else if (is_box(a) && is_box(b)) {
-      keep = false;                                                 // box-box: rejected by check_scene unless disabled (box-sphere: swept bounds, below)
+      keep = false;                                                 // box-box, a static box included: rejected at create unless disabled (box-sphere: swept bounds, below)
 #else
     } else if ((is_box(a) || is_box(b)) && b != gi[I_NB]) {
       keep = false;                                                 // box-box / box-sphere: rejected by check_scene unless disabled
@@ -475,13 +461,8 @@ MHW_FN PairGeom pair_geom(int p) {
     const V3 cw = X(w);
     for (int i = 0; i < N; i++) {
       const V3 tip = spoke_tip_at(Rw, cw, i);
-#if MHW_STATICS
       const V3 pp = to_plane(tip, gi[I_NB]);
       if (pp.y < min_dist) { min_dist = pp.y; g.pb = from_plane(v3(pp.x, 0.0, pp.z), gi[I_NB]); g.pa = tip; }
-#else
-      const V3 pp = to_plane(tip);
-      if (pp.y < min_dist) { min_dist = pp.y; g.pb = from_plane(v3(pp.x, 0.0, pp.z)); g.pa = tip; }
-#endif
     }
     g.dist = min_dist; g.a = gi[I_NB]; g.b = w;
     return g;
@@ -503,13 +484,8 @@ MHW_FN PairGeom pair_geom(int p) {
     g.pa = v3(0.0, 0.0, 0.0); g.pb = v3(0.0, 0.0, 0.0);
     for (int i = 0; i < 8; i++) {
       const V3 vtx = box_vertex(g.a, i);
-#if MHW_STATICS
-      const V3 pp = to_plane(vtx, g.b);                             // (a box body's partner here is a static plane: box-sphere went above, box-box is never kept)
+      const V3 pp = to_plane(vtx, g.b);                             // (a box body's partner here is a plane: box-sphere went above, box-box is never kept)
       if (pp.y < min_dist) { min_dist = pp.y; g.pa = vtx; g.pb = from_plane(v3(pp.x, 0.0, pp.z), g.b); }
-#else
-      const V3 pp = to_plane(vtx);
-      if (pp.y < min_dist) { min_dist = pp.y; g.pa = vtx; g.pb = from_plane(v3(pp.x, 0.0, pp.z)); }
-#endif
     }
     g.dist = min_dist;
     return g;
@@ -526,21 +502,12 @@ MHW_FN PairGeom pair_geom(int p) {
     g.pa = ca + u * sa; g.pb = cb - u * sb; g.dist = d;
     return g;
   }
-  const int s = enabled(g.a) ? g.a : g.b;
-#if MHW_STATICS
-  const int pl = enabled(g.a) ? g.b : g.a;
+  const int s = enabled(g.a) ? g.a : g.b, pl = enabled(g.a) ? g.b : g.a;
   const V3 cp = to_plane(X(s), pl);
   const double r = gd[D_RADIUS + s];
   const double low = cp.y + (-1.0 * r);
   const V3 on_plane = from_plane(v3(cp.x, 0.0, cp.z), pl);
   const V3 on_sphere = from_plane(v3(cp.x, low, cp.z), pl);
-#else
-  const V3 cp = to_plane(X(s));
-  const double r = gd[D_RADIUS + s];
-  const double low = cp.y + (-1.0 * r);
-  const V3 on_plane = from_plane(v3(cp.x, 0.0, cp.z));
-  const V3 on_sphere = from_plane(v3(cp.x, low, cp.z));
-#endif
   if (s == g.a) { g.pa = on_sphere; g.pb = on_plane; } else { g.pa = on_plane; g.pb = on_sphere; }
   g.dist = low;
   return g;
@@ -585,21 +552,12 @@ MH_DEV ContactGeom contact_geom_body(int p, double TOL) {
     return c;
   }
   const int s = enabled(a) ? a : b, pl = enabled(a) ? b : a;
-#if MHW_STATICS
   const V3 cp = to_plane(X(s), pl);
   const double r = gd[D_RADIUS + s];
   c.dist = cp.y - r;
   if (c.dist > TOL) return c;
   c.pt = from_plane(v3(cp.x, 0.5 * (cp.y - r), cp.z), pl);
   c.n = plane_n(pl); c.g1 = s; c.g2 = pl; c.has = 1;
-#else
-  const V3 cp = to_plane(X(s));
-  const double r = gd[D_RADIUS + s];
-  c.dist = cp.y - r;
-  if (c.dist > TOL) return c;
-  c.pt = from_plane(v3(cp.x, 0.5 * (cp.y - r), cp.z));
-  c.n = plane_n(); c.g1 = s; c.g2 = pl; c.has = 1;
-#endif
   return c;
 }
 MH_DEV double rel_vel(int g1, int g2, V3 pt, V3 dir) { return dot(dir, point_vel(g1, pt) - point_vel(g2, pt)); }
@@ -619,25 +577,14 @@ MH_DEV double ca_step(int p) {
     // calc_next_CA_Euler_step reports "never" (coldet-plugin.cpp:205-208); _rmax of the wheel is 0
     if (g.dist <= 0.0) return MHW_INF;
   } else
-#if MHW_BSP
-  if (is_box(g.a) && is_ground(g.b)) {                              // box against the plane; a box-sphere pair follows the sphere rule below
-#elif MHW_BOX
-  if (is_box(g.a)) {
-#endif
 #if MHW_BOX
+  if (box_plane_pair(g.a, g.b)) {                                   // a box-sphere pair follows the sphere rule below
     if (g.dist <= 0.0) {
       // calc_next_CA_Euler_step_generic (CCD.cpp:238-405) for plane (geom1) / box (geom2)
-#if MHW_STATICS
       const unsigned m = box_contact_mask(g.a, MH_NEAR_ZERO, g.b);   // the pair's own plane
       if (m == 0u) return MHW_INF;
       const V3 cn = -plane_n(g.b);
-      const int gnd = g.b;
-#else
-      const unsigned m = box_contact_mask(g.a, MH_NEAR_ZERO);
-      if (m == 0u) return MHW_INF;
-      const V3 cn = -plane_n();
-      const int gnd = gi[I_NB];
-#endif
+      const int gnd = plane_body(g.b);
       V3 p3[3]; int np = 0; V3 first = v3(0.0, 0.0, 0.0);
       for (int i = 0; i < 8; i++) if ((m >> i) & 1u) {
         const V3 vtx = box_vertex(g.a, i);
@@ -679,11 +626,7 @@ MH_DEV double ca_step(int p) {
     if (c.has && fabs(rel_vel(c.g1, c.g2, c.pt, c.n)) < MH_NEAR_ZERO * 10) return MHW_INF;
   }
   // CA_generic
-#if MHW_BSP
-  if (g.dist <= 0.0 && !is_spokes(g.b) && !(is_box(g.a) && is_ground(g.b))) {
-#else
-  if (g.dist <= 0.0 && !is_spokes(g.b) && !is_box(g.a)) {
-#endif
+  if (g.dist <= 0.0 && !is_spokes(g.b) && !box_plane_pair(g.a, g.b)) {
     if (!have_c) c = contact_geom(p, MH_NEAR_ZERO);
     if (!c.has) return MHW_INF;
     if (rel_vel(c.g1, c.g2, c.pt, c.n) < -MH_NEAR_ZERO) return 0.0;
@@ -910,25 +853,15 @@ MHW_FN int spoke_contacts(int p, int nc) {
   bool has = false; V3 pt = v3(0.0, 0.0, 0.0); double dist = 0.0;
   if (lane < gi[I_NSPOKES]) {
     const V3 tip = spoke_tip(a, lane);
-#if MHW_STATICS
     const V3 pp = to_plane(tip, b);
     has = pp.y < gd[D_THRESH];
     pt = (tip + from_plane(v3(pp.x, 0.0, pp.z), b)) * 0.5;
-#else
-    const V3 pp = to_plane(tip);
-    has = pp.y < gd[D_THRESH];
-    pt = (tip + from_plane(v3(pp.x, 0.0, pp.z))) * 0.5;
-#endif
     dist = pp.y;
   }
   const uint64_t m = ballot(has);
   wave_sync();
   if (nc + popc(m) > MHW_MAX_CONTACTS) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); return nc; }
-#if MHW_STATICS
   if (has) store_contact(nc + popc(m & lanes_below(lane)), p, a, b, pt, plane_n(b), dist);
-#else
-  if (has) store_contact(nc + popc(m & lanes_below(lane)), p, a, b, pt, plane_n(), dist);
-#endif
   wave_sync();
   return nc + popc(m);
 }
@@ -947,9 +880,7 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
   const double thresh = gd[D_THRESH];
   ContactGeom c; c.has = 0; c.g1 = 0; c.g2 = 0; c.pt = v3(0, 0, 0); c.n = v3(0, 0, 0); c.dist = 0.0;
   int p = 0, cnt = 0, bx = -1; unsigned bmask = 0u;
-#if MHW_STATICS
   int bpl = 0;                                                      // the plane of this lane's box-plane pair
-#endif
   if (lane < count) {
     p = gi[list_off + lane];
     const PairGeom g = pair_geom(p);
@@ -959,13 +890,7 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
       c.n = nn / norm(nn); c.pt = g.pa; c.g1 = g.a; c.g2 = g.b; c.dist = g.dist; c.has = 1; cnt = 1;
     } else if (mode == 1 || g.dist < thresh) {
       const double TOL = (mode == 1) ? MH_NEAR_ZERO : thresh;
-#if MHW_STATICS
-      if (is_box(g.a) && is_ground(g.b)) { bx = g.a; bpl = g.b; bmask = box_contact_mask(bx, TOL, bpl); cnt = popc((uint64_t)bmask); }
-#elif MHW_BSP
-      if (is_box(g.a) && is_ground(g.b)) { bx = g.a; bmask = box_contact_mask(bx, TOL); cnt = popc((uint64_t)bmask); }
-#else
-      if (is_box(g.a)) { bx = g.a; bmask = box_contact_mask(bx, TOL); cnt = popc((uint64_t)bmask); }
-#endif
+      if (box_plane_pair(g.a, g.b)) { bx = g.a; bpl = g.b; bmask = box_contact_mask(bx, TOL, bpl); cnt = popc((uint64_t)bmask); }
       else { c = contact_geom(p, TOL); cnt = c.has; }
     }
   }
@@ -976,18 +901,10 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
   wave_sync();
   if (total > MHW_MAX_CONTACTS) return -1;
   if (bx >= 0) {
-#if MHW_STATICS
-    const V3 cn = -plane_n(bpl); const int gnd = bpl;
-#else
-    const V3 cn = -plane_n(); const int gnd = gi[I_NB];
-#endif
+    const V3 cn = -plane_n(bpl); const int gnd = plane_body(bpl);
     for (int i = 0; i < 8; i++) if ((bmask >> i) & 1u) {
       const V3 vtx = box_vertex(bx, i);
-#if MHW_STATICS
-      store_contact(off, p, gnd, bx, vtx, cn, to_plane(vtx, bpl).y);
-#else
-      store_contact(off, p, gnd, bx, vtx, cn, to_plane(vtx).y);     // create_contact(plane, box, vertex, -n, dist)
-#endif
+      store_contact(off, p, gnd, bx, vtx, cn, to_plane(vtx, bpl).y);   // create_contact(plane, box, vertex, -n, dist)
       off++;
     }
   } else if (c.has) store_contact(off, p, c.g1, c.g2, c.pt, c.n, c.dist);
@@ -2116,4 +2033,25 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
 }
 
 #undef MHW_FN
+#undef plane_body
+#undef box_plane_pair
 } } // namespace mh::MHW_NS
+
+// ---- what the host side (mh_world.hip) sees of this code object: its kernel, and the upload of the __constant__ tables, of which every code object has a
+// copy of its own.  MHW_VARIANT_GETTER names the getter (declared in mh_host.h); MHW_VARIANT_T is mh_world_forced_variant in the MHW_FORCES units. ----
+#ifndef MHW_VARIANT_T
+#define MHW_VARIANT_T mh_world_variant
+#endif
+static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes)
+{
+  if (fric_bytes != sizeof(mh::FricTable) || pow10_bytes != sizeof(mh::Pow10Table)) return hipErrorInvalidValue;
+  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_fric), fric, fric_bytes);
+  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mh::c_pow10), pow10, pow10_bytes);
+  return e;
+}
+
+const MHW_VARIANT_T* MHW_VARIANT_GETTER()
+{
+  static const MHW_VARIANT_T v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
+  return &v;
+}
