@@ -209,6 +209,22 @@ def test_ball_rests_on_a_crate_on_the_plane(ref):
 
 
 # ---- 5. loader and scene check ---------------------------------------------------------------------------------------------------------------------
+def test_full_image_with_parameters_per_pair_meets_its_conditions(ref):
+    """the "full_params" batch of the GPU tests as an input: 36 slots over ntot = 9 with pairwise different (epsilon, mu-coulomb, NK), NK in {4, 8}; beside
+    the six box-box pairs two sphere-sphere pairs and one sphere-ground pair are disabled.  reference_run asserts the rest (check_full_params_conditions):
+    no fatal bit, LCPs solved, the mini-step cap, contacts on box-sphere, sphere-sphere and box-ground slots, the ball sinking into the disabled plane"""
+    from tests import world_boxsphere_ref as W
+    c, st, aux, _, _ = W.reference_run("full_params")
+    sc = c["scene"]
+    assert (sc.nb, sc.has_ground) == (8, 1)
+    triples = [(sc.cp_epsilon[p], sc.cp_mu_coulomb[p], sc.cp_nk[p]) for p in range(36)]
+    en = {(i, j): sc.pair_enabled[S.pair_index(i, j, 9)] for i in range(9) for j in range(i + 1, 9)}
+    assert len(set(triples[p] for p in range(36) if sc.pair_enabled[p])) == sum(en.values()) == 36 - 6 - 3 and {t[2] for t in triples} == {4, 8}
+    assert [k for k in sorted(en) if not en[k] and k in W.FULL_PARAMS_DISABLED] == W.FULL_PARAMS_DISABLED
+    assert (aux["mini_steps"] <= 50 * c["nsteps"]).all()
+    assert not np.array_equal(st, W.reference_run("full")[1])
+
+
 def test_scene_file_loads_with_its_three_pairs(ref):
     sc, st, ids, dt = mio.load_xml(SCENE_XML)
     assert ids == ["ball", "crate", "ground"] and sc.nb == 2 and sc.has_ground == 1 and dt == 1e-3

@@ -66,6 +66,23 @@ def test_full_image():
     check_case("full")
 
 
+def test_full_image_with_parameters_per_pair():
+    """(d, parameters) the same eight bodies with (epsilon, mu-coulomb, NK in {4, 8}) of its own in every pair slot, two sphere-sphere pairs and a
+    sphere-ground pair disabled: a cp_* or pair_enabled read at another triangular index gives another result (the conditions on this input:
+    tests/world_boxsphere_ref.py check_full_params_conditions, asserted by reference_run)"""
+    check_case("full_params")
+
+
+def test_full_image_with_parameters_per_pair_through_the_statics_build():
+    """(d, parameters, key 16) the same batch through mh_world_large_st: its triangular indices run over nb + has_ground + n with n = 0"""
+    lib = _lib.load()
+    try:
+        _lib.check(lib.mh_debug_set(16, 1))
+        check_case("full_params")
+    finally:
+        _lib.check(lib.mh_debug_set(16, 0))
+
+
 def test_noslip_model():
     """(e) mu-coulomb = 100 on every pair: the no-slip model over an island of box vertex contacts and a box-sphere contact"""
     check_case("noslip")

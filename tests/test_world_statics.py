@@ -191,6 +191,44 @@ def test_two_opposed_walls_mirror(ref):
     np.testing.assert_array_equal(s.reshape(2, 13)[:, 8:13], 0.0)
 
 
+# ---- 3b. the mixed scene as an input: a ground AND statics, parameters per pair slot ------------------------------------------------------------
+def test_mixed_scene_is_built_as_stated():
+    sc, stt, st = (W.gpu_cases()["mixed"][k] for k in ("scene", "statics", "state"))
+    assert (sc.nb, sc.has_ground, stt.n, st.shape) == (3, 1, 2, (8, 39)) and list(stt.type[:2]) == [S.MH_STATIC_PLANE, S.MH_STATIC_BOX]
+    assert [sc.geom_type[b] for b in range(3)] == [S.MH_GEOM_SPHERE, S.MH_GEOM_BOX, S.MH_GEOM_SPHERE]
+    # every frame is a general rotation (at most one entry in {0, +-1}); every origin is off the world's
+    for R in (np.array(sc.plane_R[:]), np.array(stt.R[0][:]), np.array(stt.R[1][:])):
+        assert (~np.isin(np.abs(R), (0.0, 1.0))).sum() >= 8 and np.allclose(R.reshape(3, 3) @ R.reshape(3, 3).T, np.eye(3), atol=1e-15)
+    assert any(sc.plane_o[:]) and all(stt.o[0][:]) and any(stt.o[1][:])
+    # 15 slots over ntot = 6; the box body / static box pair and sphere 0 / wall are disabled, nothing else; the parameters of no two slots agree
+    en = {(i, j): sc.pair_enabled[S.pair_index(i, j, 6)] for i in range(6) for j in range(i + 1, 6)}
+    assert len(en) == 15 and sorted(k for k, v in en.items() if not v) == sorted(W.MIXED_DISABLED) == [(0, W.MIXED_WALL), (1, W.MIXED_SBOX)]
+    triples = [(sc.cp_epsilon[p], sc.cp_mu_coulomb[p], sc.cp_nk[p]) for p in range(15)]
+    assert len(set(triples)) == 15 and {t[2] for t in triples} == {4, 8} and sum(sc.cp_mu_viscous[p] > 0 for p in range(15)) >= 4
+    assert len({t[0] for t in triples}) == 15 and len({t[1] for t in triples}) == 15
+
+
+def test_mixed_scene_conditions_hold_on_the_reference(ref):
+    """reference_run asserts them (check_mixed_conditions): no fatal bit, LCPs solved and the stabiliser run, the mini-step cap, kept contacts of the five
+    pair kinds in two worlds each under parameters of their own, the ball through the wall it does not collide with"""
+    c, st, aux, _, _ = W.reference_run("mixed")
+    assert (aux["mini_steps"] <= 50 * c["nsteps"]).all() and (aux["status"] & W.FATAL == 0).all()
+    c, st_f, aux_f, _, _ = W.reference_run("mixed_forces")
+    assert not np.array_equal(st_f, st)
+
+
+@pytest.mark.parametrize("name", ["mixed", "mixed_forces"])
+def test_mixed_scene_equals_its_ground_as_static_twin_on_the_reference(ref, name):
+    """has_ground = 0, the ground static 0, the statics one slot up: bit-equal state, records and trajectory"""
+    c, st, aux, traj, _ = W.reference_run(name)
+    sc2, stt2 = W.ground_to_static(c["scene"], c["statics"])
+    assert (sc2.has_ground, stt2.n) == (0, 3) and bytes(sc2)[8:] == bytes(c["scene"])[8:]
+    st2, aux2, traj2, _ = W.run_ref(sc2, stt2, c["state"], c["dt"], c["nsteps"], want_traj=True, forces=c.get("forces"), wrench=c.get("wrench"))
+    np.testing.assert_array_equal(traj2, traj)
+    np.testing.assert_array_equal(st2, st)
+    assert aux2.tobytes() == aux.tobytes()
+
+
 # ---- 4. argument validation (no GPU: every refusal comes before the device is asked for) ------------------------------------------------------
 def _create(sc, stt, B=2):
     h = ctypes.c_void_p()

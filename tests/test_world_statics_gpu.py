@@ -145,6 +145,71 @@ def test_launch_variants():
     assert_aux_equal(aux, aux_r)
 
 
+def test_mixed_scene_with_ground_and_statics():
+    """(12) has_ground = 1 AND n = 2: the statics sit one slot up in the kernel's cache (the ground in slot 0).  A tilted ground off the origin, a plane
+    turned about two axes off the origin, a static box turned about two axes, a sphere, a box body and a second sphere; 15 pair slots with parameters
+    of their own, two of them disabled (the conditions on this input: tests/world_statics_ref.py check_mixed_conditions, asserted by reference_run)"""
+    case = gpu_cases()["mixed"]
+    sc = case["scene"]
+    assert (sc.nb, sc.has_ground, case["statics"].n) == (3, 1, 2)
+    _, aux, _ = check_case("mixed")
+    assert (aux["stab_iters"] > 0).any()
+
+
+def test_mixed_scene_equals_its_ground_as_static_twin():
+    """(13) the same scene with has_ground = 0, its ground handed over as static 0 and the two statics one slot up: bodies and pair slots are where they
+    were, so state, aux and trajectory are bit-equal -- a comparison of the device with itself, no reference in it"""
+    case = gpu_cases()["mixed"]
+    sc2, stt2 = W.ground_to_static(case["scene"], case["statics"])
+    assert (sc2.has_ground, stt2.n) == (0, 3) and list(stt2.type[:3]) == [S.MH_STATIC_PLANE, S.MH_STATIC_PLANE, S.MH_STATIC_BOX]
+    st, aux, traj = run_host(case)
+    st2, aux2, traj2 = run_host(dict(case, scene=sc2, statics=stt2))
+    np.testing.assert_array_equal(traj2, traj)
+    np.testing.assert_array_equal(st2, st)
+    assert_aux_equal(aux2, aux)
+    assert aux2.tobytes() == aux.tobytes()
+    # the ball shot at the wall its pair with is disabled has left through it
+    r = W.MIXED_BODIES[0][1]
+    for w in W.MIXED_THROUGH:
+        assert W.plane_height(W.MIXED_WALL_R, W.MIXED_WALL_O, st[w, 0:3]) < -r < r < W.plane_height(W.MIXED_WALL_R, W.MIXED_WALL_O, case["state"][w, 0:3])
+
+
+def test_mixed_scene_with_forces():
+    """(14) the mixed scene through the forced statics object: Stokes drag and damping on all three bodies, a wrench row per step"""
+    case = gpu_cases()["mixed_forces"]
+    assert case["forces"].terms == 3 and case["wrench"].shape == (case["nsteps"], 8, 3, 6)
+    assert all(case["forces"].stokes_b[b] > 0 and case["forces"].damp_kl[b] > 0 for b in range(3))
+    st, _, _ = check_case("mixed_forces")
+    assert not np.array_equal(st, reference_run("mixed")[1])
+
+
+def test_mixed_scene_launch_variants():
+    """(15) the mixed scene in three launches == in one launch == through step_ids on a shuffled id list"""
+    import torch
+    case, st_r, aux_r, _, _ = reference_run("mixed")
+    st1, aux1, _ = run_host(case, want_traj=False)
+    dev = WorldBatchDevice(case["scene"], case["state"], statics=case["statics"])
+    try:
+        for _ in range(3):
+            dev.step(case["dt"], case["nsteps"] // 3)
+        st, aux = dev.download()
+    finally:
+        dev.close()
+    np.testing.assert_array_equal(st, st1)
+    assert_aux_equal(aux, aux1)
+    dev = WorldBatchDevice(case["scene"], case["state"], statics=case["statics"])
+    try:
+        ids = torch.tensor([6, 1, 4, 7, 0, 3, 5, 2], dtype=torch.int32, device="cuda")
+        dev.step_ids(case["dt"], case["nsteps"], ids.data_ptr(), 8)
+        st, aux = dev.download()
+    finally:
+        dev.close()
+    np.testing.assert_array_equal(st, st1)
+    assert_aux_equal(aux, aux1)
+    np.testing.assert_array_equal(st, st_r)
+    assert_aux_equal(aux, aux_r)
+
+
 def test_key_16_changes_no_result():
     """(9) a ground-only scene with an enabled box-sphere pair through mh_world_large_bsp (key 16 = 0) and through mh_world_large_st (key 16 = 1):
     bit-equal, and equal to the reference"""

@@ -175,6 +175,55 @@ def full_batch(B=4):
     return sc, st.reshape(B, -1)
 
 
+FULL_PARAMS_DISABLED = [(1, 5), (5, 7), (7, 8)]      # two sphere-sphere pairs that never meet, and sphere 7 / ground: that ball must sink into the plane
+
+
+def full_params_batch(B=4):
+    """full_batch with parameters of its own in every pair slot (36 over ntot = 9): epsilon and mu-coulomb rise with the slot, NK alternates between 4
+    and 8 -- except the four box / ground slots, which stay at NK = 4 (box 0's island holds 4 vertex contacts, a box-sphere and a sphere-sphere contact:
+    4 x 8 + 2 x 10 = 52 of the 64 LCP rows; NK = 8 under the box would make it 60 and leave nothing for a fifth vertex)."""
+    sc, st = full_batch(B)
+    kinds = [b[0] for b in FULL_BODIES] + ["ground"]
+    for i in range(9):
+        for j in range(i + 1, 9):
+            p = S.pair_index(i, j, 9)
+            nk = 4 if (kinds[i] == "box" and j == 8) else (8 if p % 2 else 4)
+            S.set_pair_params(sc, i, j, 9, epsilon=0.02 + 0.0125 * p, mu_coulomb=0.2 + 0.01 * p, mu_viscous=0.02 if p % 5 == 0 else 0.0, nk=nk,
+                              enabled=0 if (kinds[i] == kinds[j] == "box" or (i, j) in FULL_PARAMS_DISABLED) else 1)
+    return sc, st
+
+
+def check_full_params_conditions(case, st, aux):
+    """the conditions on "full_params" as an input, on the reference alone: no fatal bit, LCPs solved, the mini-step cap; stepping one step at a time,
+    contacts on a box-sphere, a sphere-sphere and a box-ground slot, their parameters pairwise different; the ball over the disabled ground pair sinks"""
+    sc = case["scene"]
+    B, nsteps = case["state"].shape[0], case["nsteps"]
+    assert ((aux["status"] & FATAL) == 0).all() and (aux["lcp_solves"] > 0).all(), (aux["status"], aux["lcp_solves"])
+    assert (aux["mini_steps"] <= 50 * nsteps).all(), aux["mini_steps"]
+    kinds = [b[0] for b in FULL_BODIES] + ["ground"]
+    s1, a1 = case["state"].copy(), S.new_aux(B)
+    seen = set()
+    for _ in range(nsteps):
+        reference().step(sc, s1, a1, case["dt"], 1)
+        for w in range(B):
+            for i in range(8):
+                for j in range(i + 1, 9):
+                    p = S.pair_index(i, j, 9)
+                    if sc.pair_enabled[p] and (i, j) not in seen and reference().pair(sc, s1[w], p, sc.contact_dist_thresh)["ncontacts"] > 0:
+                        seen.add((i, j))
+    np.testing.assert_array_equal(s1, st)
+    assert a1.tobytes() == aux.tobytes()
+    by_kind = {}
+    for i, j in seen:
+        by_kind.setdefault(tuple(sorted((kinds[i], kinds[j]))), []).append((i, j))
+    assert all(k in by_kind for k in (("box", "sphere"), ("sphere", "sphere"), ("box", "ground"))), by_kind
+    used = [(sc.cp_epsilon[S.pair_index(i, j, 9)], sc.cp_mu_coulomb[S.pair_index(i, j, 9)], sc.cp_nk[S.pair_index(i, j, 9)]) for i, j in seen]
+    assert len(set(used)) == len(used) and len(set(u[0] for u in used)) == len(used), used
+    y7 = st.reshape(B, 8, S.MH_BODY_STATE)[:, 7, 1]
+    assert (y7 < RADIUS - 5e-3).all(), y7            # 5 mm into the plane it does not collide with
+    return seen
+
+
 def noslip_capacity_batch(B=4):
     """two boxes flat on the plane side by side and a ball landing on the seam between them, mu-coulomb = 100 everywhere: one no-slip island of
     4 + 4 box vertex contacts and two box-sphere contacts"""
@@ -232,6 +281,8 @@ def gpu_cases():
     out["face_forces"] = dict(out["face"], forces=S.make_forces(2, stokes=(0.3, 0.05)), wrench=wr)
     sc, st = full_batch(4)
     out["full"] = dict(scene=sc, state=st, dt=1e-3, nsteps=20)
+    sc, st = full_params_batch(4)
+    out["full_params"] = dict(scene=sc, state=st, dt=1e-3, nsteps=20)
     sc, st = face_batch(4, mu_coulomb=100.0, epsilon=0.0)
     out["noslip"] = dict(scene=sc, state=st, dt=1e-3, nsteps=20)
     sc, st = noslip_capacity_batch(4)
@@ -256,6 +307,8 @@ def reference_run(name):
     if name != "disabled":
         assert (aux["lcp_solves"] > 0).all(), (name, aux["lcp_solves"])
         assert census[:, :, :PENETRATING + 1].sum() > 0, name
+    if name == "full_params":
+        check_full_params_conditions(c, st, aux)
     for a in (st, aux, traj, census):
         a.setflags(write=False)
     return c, st, aux, traj, census

@@ -261,6 +261,164 @@ def corner9_batch(B):
     return sc, stt, st.reshape(B, -1)
 
 
+# ---- the mixed scene: a scene ground AND statics, a free box-sphere pair among them, every pair slot with parameters of its own ---------------------
+MIXED_BODIES = [("sphere", 0.25, 1.0), ("box", (0.6, 0.4, 0.5), 2.0), ("sphere", 0.2, 0.5)]
+MIXED_GROUND_RPY, MIXED_GROUND_O = (0.1, 0.0, 0.07), (0.0, -0.05, 0.0)
+MIXED_WALL_R, MIXED_WALL_O = rot_y(0.8, 0.6) @ rot_z(0.96, 0.28) @ R_POS_X, (-0.9, 0.2, 0.1)
+MIXED_SBOX_DIMS, MIXED_SBOX_R, MIXED_SBOX_O = (1.0, 0.5, 0.8), rot_y(0.6, 0.8) @ rot_z(0.96, -0.28), (1.2, 0.2, 0.0)
+MIXED_GROUND, MIXED_WALL, MIXED_SBOX = 3, 4, 5                       # body indices over ntot = 6: the ground is body nb, static k is nb + 1 + k
+MIXED_DISABLED = [(1, MIXED_SBOX), (0, MIXED_WALL)]                  # box body / static box (box-box: it must be), and sphere 0 / the wall
+MIXED_THROUGH = (5, 6, 7)                                            # the worlds whose sphere 0 is shot at the wall it does not collide with
+# (epsilon, mu_coulomb, mu_viscous, NK) of each slot a body is part of; the box body's plane pairs stay at NK = 4 (4 + 4 vertex contacts of NK = 8
+# would be 80 LCP rows, beyond the 64 the wave solver holds)
+MIXED_PARAMS = {
+    (0, 1): (0.15, 0.35, 0.0, 8), (0, 2): (0.25, 0.45, 0.02, 4), (0, MIXED_GROUND): (0.2, 0.3, 0.05, 8), (0, MIXED_WALL): (0.9, 0.08, 0.0, 4),
+    (0, MIXED_SBOX): (0.3, 0.5, 0.04, 8), (1, 2): (0.1, 0.25, 0.03, 8), (1, MIXED_GROUND): (0.02, 0.05, 0.0, 4), (1, MIXED_WALL): (0.04, 0.2, 0.06, 4),
+    (1, MIXED_SBOX): (0.95, 0.9, 0.0, 4), (2, MIXED_GROUND): (0.12, 0.55, 0.0, 4), (2, MIXED_WALL): (0.22, 0.15, 0.07, 8), (2, MIXED_SBOX): (0.05, 0.6, 0.0, 8),
+    (MIXED_GROUND, MIXED_WALL): (0.6, 0.7, 0.0, 4), (MIXED_GROUND, MIXED_SBOX): (0.65, 0.75, 0.0, 8), (MIXED_WALL, MIXED_SBOX): (0.7, 0.8, 0.0, 4)}
+
+
+def mixed_scene_and_statics():
+    """nb = 3 (sphere, box, sphere), a tilted scene ground off the origin, n = 2 statics (a plane turned about two axes off the origin, a box turned
+    about two axes): ntot = 6, 15 pair slots, each with parameters of its own"""
+    sc = scene(MIXED_BODIES, 2, ground=True)
+    Rg = S.rpy_to_R(*MIXED_GROUND_RPY)
+    for k in range(9):
+        sc.plane_R[k] = Rg.flat[k]
+    for k in range(3):
+        sc.plane_o[k] = MIXED_GROUND_O[k]
+    assert len(MIXED_PARAMS) == 15 and len(set((e, m, nk) for e, m, _, nk in MIXED_PARAMS.values())) == 15
+    for (i, j), (eps, mu, muv, nk) in MIXED_PARAMS.items():
+        S.set_pair_params(sc, i, j, 6, epsilon=eps, mu_coulomb=mu, mu_viscous=muv, nk=nk, enabled=0 if (i, j) in MIXED_DISABLED else 1)
+    stt = S.make_statics([dict(plane=True, R=MIXED_WALL_R, o=MIXED_WALL_O), dict(box=MIXED_SBOX_DIMS, R=MIXED_SBOX_R, o=MIXED_SBOX_O)])
+    return sc, stt
+
+
+def plane_height(R, o, x):
+    """signed distance of point(s) x from the plane with frame R (its +Y the normal) and origin o"""
+    return (np.asarray(x) - np.asarray(o)) @ np.asarray(R)[:, 1]
+
+
+def _quat_R(q):
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def R_to_quat(R):
+    """a rotation matrix (trace > 0) as a unit quaternion xyzw"""
+    w = 0.5 * np.sqrt(1.0 + R[0, 0] + R[1, 1] + R[2, 2])
+    q = np.array([(R[2, 1] - R[1, 2]) / (4.0 * w), (R[0, 2] - R[2, 0]) / (4.0 * w), (R[1, 0] - R[0, 1]) / (4.0 * w), w])
+    return q / np.linalg.norm(q)
+
+
+def mixed_batch(B=8):
+    """The box body drops flat onto the tilted ground (four vertex contacts) 1-2 mm from the tilted wall and slides down the slope into it (a vertex
+    contact, kept by gravity; the box starts flat because a tumbled one crawls through conservative advancement once it rests on one or two vertices).
+    Sphere 2 lands on the box body in the even worlds and on the ground beside it in the odd ones; sphere 0 lands on the top face of the static box --
+    except in the worlds MIXED_THROUGH, where it skims the ground at 7 m/s towards the wall its pair with is disabled and must leave through it."""
+    sc, stt = mixed_scene_and_statics()
+    Rg, og = S.rpy_to_R(*MIXED_GROUND_RPY), np.array(MIXED_GROUND_O)
+    Rw, ow = MIXED_WALL_R, np.array(MIXED_WALL_O)
+    ng, nw = Rg[:, 1], Rw[:, 1]
+    along = np.cross(nw, ng); along = along / np.linalg.norm(along)          # the direction of the line in which wall and ground meet
+    into = -(nw - (nw @ ng) * ng); into = into / np.linalg.norm(into)        # along the ground, into the wall
+    Rb, ob = MIXED_SBOX_R, np.array(MIXED_SBOX_O)
+    hb = 0.5 * np.array(MIXED_BODIES[1][1])
+    corners = np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)]) * hb
+    st = sphere_state(B, 3)
+    for w in range(B):
+        u = world_uniforms(1300 + w, 12)
+        # the box body: flat over the ground (its y axis the ground's normal), turned about that normal; 2-4 mm over the ground, its vertex nearest the
+        # wall 4-8 mm off it; it drops onto the ground and slides into the wall
+        a = 0.35 + 0.3 * u[0]
+        Rbox = Rg @ rot_y(np.cos(a), np.sin(a))
+        q = R_to_quat(Rbox)
+        cw = corners @ _quat_R(q).T
+        rhs = [2e-3 * (1.0 + u[3]) - (cw @ ng).min() + og @ ng, 1e-3 * (1.0 + u[4]) - (cw @ nw).min() + ow @ nw, 0.1 * (u[5] - 0.5) + ow @ along]
+        cbox = np.linalg.solve(np.array([ng, nw, along]), rhs)
+        vbox = 0.3 * into - 1.0 * ng
+        set_body(st, w, 1, cbox, v=tuple(vbox), q=tuple(q))
+        # sphere 2: 4-6 mm above the box body's top face, 1 m/s faster towards it
+        top = _quat_R(q)[:, 1]
+        if w % 2 == 0:
+            set_body(st, w, 2, cbox + top * (hb[1] + 0.2 + 4e-3 + 2e-3 * u[6]) + _quat_R(q) @ np.array([0.1 * (u[7] - 0.5), 0.0, 0.1 * (u[8] - 0.5)]),
+                     v=tuple(vbox - 1.0 * top))
+        else:
+            # ... or, in the odd worlds, drops onto the ground 1 m along the wall from the box body
+            c2 = np.linalg.solve(np.array([ng, nw, along]), [0.2 + 1e-3 * (1.0 + u[6]) + og @ ng, 0.5 + 0.1 * u[7] + ow @ nw, 1.0 + 0.1 * u[8] + ow @ along])
+            set_body(st, w, 2, c2, v=tuple(-0.5 * ng))
+        if w in MIXED_THROUGH:
+            # sphere 0: 1-2 mm over the ground, 1 cm in front of the wall, 2 m along it from the box body; 5 m/s along the ground into the wall
+            c0 = np.linalg.solve(np.array([ng, nw, along]), [0.25 + 1e-3 * (1.0 + u[9]) + og @ ng, 0.25 + 0.01 + ow @ nw, -2.0 + ow @ along])
+            set_body(st, w, 0, c0, v=tuple(7.0 * into - 0.2 * ng))
+        else:
+            # sphere 0: 1-2 mm above the static box's top face, moving along and into it
+            c0 = ob + Rb @ np.array([0.2 * (u[10] - 0.5), 0.25 + 0.25 + 1e-3 * (1.0 + u[9]), 0.2 * (u[11] - 0.5)])
+            set_body(st, w, 0, c0, v=tuple(Rb @ np.array([0.3, -0.8, 0.0])))
+    return sc, stt, st.reshape(B, -1)
+
+
+def ground_to_static(sc, stt):
+    """the twin of a scene with a ground and statics: has_ground = 0, the ground static 0 and the statics one slot up.  Body indices and pair slots do not
+    move (the ground is body nb either way)"""
+    s2 = S.mh_scene.from_buffer_copy(bytes(sc))
+    assert sc.has_ground == 1 and stt.n < S.MH_MAX_STATICS
+    s2.has_ground = 0
+    items = [dict(plane=True, R=np.array(sc.plane_R[:]).reshape(3, 3), o=tuple(sc.plane_o[:]))]
+    for k in range(stt.n):
+        it = dict(R=np.array(stt.R[k][:]).reshape(3, 3), o=tuple(stt.o[k][:]))
+        it.update(dict(box=tuple(stt.dim[k][:])) if stt.type[k] == S.MH_STATIC_BOX else dict(plane=True))
+        items.append(it)
+    return s2, S.make_statics(items)
+
+
+def contact_worlds(case):
+    """the reference, one step at a time: pair slot -> the set of worlds in which the pair probe showed a kept contact after some step; and the final
+    (state, aux)"""
+    sc, stt = case["scene"], case["statics"]
+    B = case["state"].shape[0]
+    ntot = sc.nb + sc.has_ground + (stt.n if stt is not None else 0)
+    slots = [S.pair_index(i, j, ntot) for i in range(sc.nb) for j in range(i + 1, ntot) if sc.pair_enabled[S.pair_index(i, j, ntot)]]
+    st, aux = case["state"].copy(), S.new_aux(B)
+    seen = {p: set() for p in slots}
+    for _ in range(case["nsteps"]):
+        reference().step(sc, stt, st, aux, case["dt"], 1)
+        for w in range(B):
+            for p in slots:
+                g = reference().pair(sc, stt, st[w], p, sc.contact_dist_thresh)
+                if g["kept"] and g["ncontacts"] > 0:
+                    seen[p].add(w)
+    return seen, st, aux
+
+
+def check_mixed_conditions(case, st, aux):
+    """the conditions on the mixed scene as an input, asserted on the reference alone (st, aux: its final state and records)"""
+    sc = case["scene"]
+    B, nsteps = case["state"].shape[0], case["nsteps"]
+    assert ((aux["status"] & FATAL) == 0).all() and (aux["lcp_solves"] > 0).all(), (aux["status"], aux["lcp_solves"])
+    assert (aux["mini_steps"] <= 50 * nsteps).all(), aux["mini_steps"]            # bounds the GPU test's run time
+    assert (aux["stab_iters"] > 0).any()
+    seen, st1, aux1 = contact_worlds(case)
+    np.testing.assert_array_equal(st1, st)                                        # step by step is the one call
+    assert aux1.tobytes() == aux.tobytes()
+    P = lambda i, j: S.pair_index(i, j, 6)
+    n = {p: len(ws) for p, ws in seen.items()}
+    assert n[P(0, MIXED_SBOX)] >= 2, n                                            # sphere / static box
+    assert n[P(1, 2)] >= 2, n                                                     # free box / free sphere
+    assert n[P(1, MIXED_GROUND)] >= 2, n                                          # box body / scene ground
+    assert n[P(1, MIXED_WALL)] >= 2, n                                            # box body / tilted static plane
+    assert len(seen[P(0, MIXED_GROUND)] | seen[P(2, MIXED_GROUND)] | seen[P(2, MIXED_WALL)]) >= 2, n    # sphere / tilted plane or ground
+    used = [(sc.cp_epsilon[p], sc.cp_mu_coulomb[p], sc.cp_nk[p]) for p, ws in seen.items() if ws]
+    assert len(set(used)) == len(used) >= 5, used
+    # the ball shot at the wall it does not collide with: in front of it at the start, wholly behind it at the end
+    r = MIXED_BODIES[0][1]
+    for w in MIXED_THROUGH:
+        assert plane_height(MIXED_WALL_R, MIXED_WALL_O, case["state"][w, 0:3]) > r and plane_height(MIXED_WALL_R, MIXED_WALL_O, st[w, 0:3]) < -r, w
+    return seen
+
+
 @functools.lru_cache(maxsize=None)
 def gpu_cases():
     """name -> dict(scene, statics, state, dt, nsteps[, forces, wrench]); built once, the arrays read-only"""
@@ -280,6 +438,11 @@ def gpu_cases():
     sc, stt, st = table_batch(4, mu=0.4)
     rng = np.random.RandomState(7)
     add("forces", sc, stt, st, 1e-3, 20, forces=S.make_forces(1, stokes=(0.3, 0.05), damping=(0.1, 0.02, 0.05, 0.01)), wrench=rng.uniform(-2.0, 2.0, size=(20, 4, 1, 6)))
+    sc, stt, st = mixed_batch(8)
+    add("mixed", sc, stt, st, 2e-3, 60)
+    rng = np.random.RandomState(11)
+    add("mixed_forces", sc, stt, st, 2e-3, 60, forces=S.make_forces(3, stokes=((0.3, 0.2, 0.4), (0.05, 0.03, 0.02)), damping=((0.1, 0.02, 0.05, 0.01), (0.2, 0.03, 0.04, 0.02), (0.15, 0.01, 0.06, 0.03))),
+        wrench=rng.uniform(-1.0, 1.0, size=(60, 8, 3, 6)))
     return out
 
 
@@ -293,6 +456,10 @@ def reference_run(name):
     traj, census = reference().step(c["scene"], c["statics"], st, aux, c["dt"], c["nsteps"], want_traj=True, want_census=True, forces=c.get("forces"), wrench=c.get("wrench"))
     assert ((aux["status"] & FATAL) == 0).all(), (name, aux["status"])
     assert (aux["lcp_solves"] > 0).all(), (name, aux["lcp_solves"])
+    if name.startswith("mixed"):
+        assert (aux["mini_steps"] <= 50 * c["nsteps"]).all(), (name, aux["mini_steps"])     # bounds the GPU test's run time
+    if name == "mixed":
+        check_mixed_conditions(c, st, aux)
     for a in (st, aux, traj, census):
         a.setflags(write=False)
     return c, st, aux, traj, census
