@@ -192,7 +192,8 @@ int mh_lcp_solve_batch(int kind, int B, int n,
  *                        bounds only); pairs of two disabled bodies are dropped (CCD.cpp:864-866).
  * Canonical contact order is unchanged: pair-list order.  A static never moves, carries no velocity and is no node of an island.  Such a batch steps
  * through code objects of its own (mh_world_large_st.hip, mh_world_large_st_forces.hip: the large variant built with MHW_STATICS); every other batch
- * launches what it did.  NOT built: a box body against a static box (refused while the pair is enabled), static spheres, per-world or moving statics,
+ * launches what it did.  NOT built: a box body against a static box (refused while the pair is enabled), static spheres, statics that move within a launch (per-world
+ * statics: "Per-world parameters" below),
  * spokes bodies in a scene with statics (the plugin knows one ground), statics in the large-world and articulated steppers.
  */
 #define MH_MAX_BODIES 8
@@ -306,6 +307,8 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    batches created after it; default 0: only scenes with an enabled box-sphere pair; for A/B runs).
                                             key 16: world batches that would take the box-sphere build stepped by the statics build, mh_world_large_st*.hip (1, for
                                                    batches created after it; default 0: only batches created with statics; for A/B runs).
+                                            key 17: world batches that would take the statics build stepped by the per-world-parameters build, mh_world_large_pw*.hip, every
+                                                   record filled from the scene (1, for batches created after it; default 0: only batches created with records; for A/B runs).
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);
@@ -422,6 +425,67 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
 /* Host convenience: mh_world_step_batch_forces with static bodies (forces and statics may each be NULL). */
 int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
                                 double* state, mh_world_aux* aux, double* traj, const mh_world_statics* statics);
+
+
+/* Per-world parameters.  The worlds of a batch share one TOPOLOGY -- the scene's nb, has_ground, geom_type, pair_enabled, cp_nk, the three tolerances,
+ * cstab_max_iterations, lcp_n_max and the statics' n and type -- and may each carry VALUES of their own: one mh_world_params record per world, which
+ * replaces, for that world, the scene's mass / inertia / geom_dim / plane_R / plane_o / gravity / cp_epsilon / cp_mu_coulomb / cp_mu_viscous /
+ * cp_compliance and the statics' R / o / dim (same indexing: bodies 0 .. nb-1, pair slots triangular over ntot = nb + has_ground + n, static k).  The
+ * record holds doubles only, so nothing in it can become an index.  Rule: world w of such a batch is stepped exactly as a batch of the scene and statics
+ * with record w written into them would step it (that is how it is tested: one reference run per world).  The records follow the statics record in the
+ * batch's device allocation; the kernel entry copies the entries the scene uses (nb bodies, the pair slots, has_ground + n frames) into the wavefront's
+ * own cache at launch and reads nothing of the record afterwards.  The impact model is chosen per island from its contacts' own mu-coulomb, so worlds on
+ * either side of mu = 100 may share a batch.
+ * A spokes body keeps the SCENE's R and N in every world (the spoke-tip table is evaluated once on the host): its geom_dim row in the record is not read.
+ * Its mass, inertia, gravity (the wheel's slope), ground frame and contact parameters are per world like any other body's.
+ * A batch created with records steps through code objects of its own (mh_world_large_pw.hip, mh_world_large_pw_forces.hip: the statics build with
+ * MHW_PARAMS) whatever its scene -- also a scene that would otherwise take the small or the wheel variant; every other batch launches what it launched.
+ * There is no stamped build: mh_world_batch_profile launches the production object, steps the worlds and reports zero cycles; mh_world_batch_occupancy
+ * reports the object the batch launches.  Key 17 of mh_debug_set sends batches that would take the statics build through these objects with every record
+ * equal to the scene (A/B runs; no result changes).
+ * NOT built: per-world parameters inside the small and wheel variants (such batches take the objects above); per-world topology (nb, geometry types,
+ * enabled pairs, cp_nk, number or type of statics); per-world spoke radius or count; statics that move within a launch; per-world parameters in the
+ * large-world (moby_hip_stack.h) and articulated steppers; per-world drag coefficients (mh_world_forces stays the scene's). */
+/* (no existing layout changes, so MH_VERSION stays 102; a caller that needs to know tests this macro) */
+#define MH_WORLD_PARAMS 1
+typedef struct mh_world_params {
+  double mass[MH_MAX_BODIES];
+  double inertia[MH_MAX_BODIES][3];
+  double geom_dim[MH_MAX_BODIES][3];       /* sphere: radius,-,- ; box: xlen, ylen, zlen ; spokes: NOT READ (the scene's R and N hold in every world) */
+  double plane_R[9];
+  double plane_o[3];
+  double gravity[3];
+  double cp_epsilon[MH_MAX_PAIRS];
+  double cp_mu_coulomb[MH_MAX_PAIRS];
+  double cp_mu_viscous[MH_MAX_PAIRS];
+  double cp_compliance[MH_MAX_PAIRS];
+  double st_R[MH_MAX_STATICS][9];          /* mh_world_statics.R / o / dim of this world */
+  double st_o[MH_MAX_STATICS][3];
+  double st_dim[MH_MAX_STATICS][3];
+} mh_world_params;                         /* 335 doubles, 2680 bytes */
+/* The record that reproduces the shared scene (statics == NULL: the st_* rows are zero).  Host helper, no GPU needed. */
+void mh_world_params_from_scene(const mh_scene* scene, const mh_world_statics* statics, mh_world_params* out);
+/* mh_world_batch_create_statics with one record per world (HOST pointer, B records; copied).  params == NULL: exactly mh_world_batch_create_statics.
+ * Otherwise, after the refusals of the scene and the statics (which stay as they are: box-box, spokes beside statics, sizes), every record is validated as
+ * the shared values are: for each body of the scene mass and inertia > 0, a sphere's radius > 0, a box's three edges > 0 (a spokes body's row is not
+ * looked at); gravity finite; with has_ground the ground frame finite; the four contact parameters of every pair slot finite; each static's frame
+ * finite and a static box's edges > 0 and finite.  MH_ERR_INVALID_ARG with a message that names the world and the field; the checks run before the
+ * device is looked for. */
+int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, mh_world_batch** out);
+/* Replaces the records of worlds first .. first + count - 1 (HOST pointer, `count` records), validated as at create; synchronous.  Not to be called while
+ * a launch of the batch is in flight, like mh_world_batch_set_forces.  MH_ERR_INVALID_ARG: a batch created without records, a range outside the batch, a
+ * refused record (none is then written). */
+int mh_world_batch_set_params(mh_world_batch* wb, const mh_world_params* host, int first, int count);
+/* The same from DEVICE memory, as an asynchronous copy on `stream`: ordered with the launches of that stream, for a caller that randomises on the GPU
+ * between launches.  The records are NOT validated.  What a bad value does: that world's state goes non-finite or the world gets a status bit
+ * (MH_WORLD_STALLED, MH_WORLD_LCP_FAILED, MH_WORLD_STAB_FAILED); nothing outside the world's own memory is touched, because every index, count and
+ * loop bound of the kernel comes from the shared scene or from integers the kernel computes itself, and every loop a non-finite value can reach ends by
+ * a cap (MH_CA_HARD_CAP, the 100000 mini-step guard, MH_CSTAB_HARD_CAP, the solvers' pivot caps, Ridders' iteration count) or by a comparison that is
+ * false for NaN.  The other worlds of the batch are not affected. */
+int mh_world_batch_set_params_dev(mh_world_batch* wb, void* stream, const mh_world_params* dev, int first, int count);
+/* Host convenience: mh_world_step_batch_statics with per-world records (forces, statics and params may each be NULL). */
+int mh_world_step_batch_params(const mh_scene* scene, const mh_world_forces* forces, const mh_world_statics* statics, const mh_world_params* params,
+                               int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,11 @@ SYMBOLS = {
     "mh_world_step_batch_forces": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "mh_world_step_batch_statics": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "mh_world_batch_create_statics": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
+    "mh_world_params_from_scene": (None, [_vp, _vp, _vp]),
+    "mh_world_batch_create_params": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(_vp)]),
+    "mh_world_batch_set_params": (_i, [_vp, _vp, _i, _i]),
+    "mh_world_batch_set_params_dev": (_i, [_vp, _vp, _vp, _i, _i]),
+    "mh_world_step_batch_params": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     # include/moby_hip_impact.h
     "mh_impact_batch_create": (_i, [_i, _i, _i, _i, _vp, _vp, ctypes.POINTER(_vp)]),
     "mh_impact_batch_destroy": (_i, [_vp]),

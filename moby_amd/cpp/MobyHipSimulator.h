@@ -11,6 +11,9 @@
 //   sim.step_wrench(1e-3, wrench_dev);   // ... and what the bodies' controllers add_force this step: a DEVICE array B x nb x 6
 //   MobyHip::BatchedTimeSteppingSimulator* s2 = MobyHip::BatchedTimeSteppingSimulator::with_statics(scene, statics, B, state);
 //                                   // the same with static planes and boxes beside the scene's ground (mh_world_statics); delete it when done
+//   MobyHip::BatchedTimeSteppingSimulator* s3 = MobyHip::BatchedTimeSteppingSimulator::with_params(scene, &statics /* or NULL */, params, B, state);
+//                                   // ... and with one mh_world_params record per world: masses, shapes, gravity, frames, contact parameters of its own
+//   s3->set_params(records, first, count);   // replaces the records of worlds first .. first + count - 1 between steps
 //   sim.get_generalized_coordinates_euler(w, b, q);   // x y z qx qy qz qw of body b of world w
 //
 // Conventions kept from the reference: step() returns the step size; bodies are addressed in id order
@@ -41,7 +44,14 @@ class BatchedTimeSteppingSimulator {
   /// constructor overload, so that no existing call can become ambiguous; the caller owns the object.
   static BatchedTimeSteppingSimulator* with_statics(const mh_scene& scene, const mh_world_statics& statics, int B, const double* state, bool replicate = false)
   {
-    return new BatchedTimeSteppingSimulator(scene, &statics, B, state, replicate);
+    return new BatchedTimeSteppingSimulator(scene, &statics, NULL, B, state, replicate);
+  }
+  /// The simulator of B worlds that share the scene's topology and carry values of their own (include/moby_hip.h, "Per-world parameters"): `params` holds
+  /// B records (mh_world_params_from_scene gives the one that reproduces the scene); statics may be NULL.  The caller owns the object.
+  static BatchedTimeSteppingSimulator* with_params(const mh_scene& scene, const mh_world_statics* statics, const mh_world_params* params, int B, const double* state,
+                                                   bool replicate = false)
+  {
+    return new BatchedTimeSteppingSimulator(scene, statics, params, B, state, replicate);
   }
   ~BatchedTimeSteppingSimulator() { if (_wb) mh_world_batch_destroy(_wb); }
 
@@ -65,6 +75,10 @@ class BatchedTimeSteppingSimulator {
     current_time += dt * nsteps;
     return dt;
   }
+  /// Replaces the records of worlds first .. first + count - 1 (a simulator made by with_params only); not while a step is in flight on another stream.
+  void set_params(const mh_world_params* records, int first, int count) {
+    if (mh_world_batch_set_params(_wb, records, first, count) != MH_OK) throw std::runtime_error(mh_last_error());
+  }
   int num_worlds() const { return _B; }
   int num_bodies() const { return _scene.nb; }
   /// DynamicBodyd::get_generalized_coordinates_euler of body b of world w
@@ -76,14 +90,14 @@ class BatchedTimeSteppingSimulator {
   const std::vector<double>& state() { sync(); return _state; }
 
  private:
-  BatchedTimeSteppingSimulator(const mh_scene& scene, const mh_world_statics* statics, int B, const double* state, bool replicate)
+  BatchedTimeSteppingSimulator(const mh_scene& scene, const mh_world_statics* statics, const mh_world_params* params, int B, const double* state, bool replicate)
       : current_time(0.0), _scene(scene), _B(B), _wb(NULL), _dirty(false)
   {
-    init(statics, state, replicate);
+    init(statics, state, replicate, params);
   }
-  void init(const mh_world_statics* statics, const double* state, bool replicate)
+  void init(const mh_world_statics* statics, const double* state, bool replicate, const mh_world_params* params = NULL)
   {
-    if (mh_world_batch_create_statics(&_scene, statics, _B, &_wb) != MH_OK) throw std::runtime_error(mh_last_error());
+    if (mh_world_batch_create_params(&_scene, statics, params, _B, &_wb) != MH_OK) throw std::runtime_error(mh_last_error());
     const size_t nst = (size_t)_scene.nb * MH_BODY_STATE;
     _state.resize((size_t)_B * nst);
     for (int w = 0; w < _B; w++) for (size_t k = 0; k < nst; k++) _state[(size_t)w * nst + k] = state[replicate ? k : (size_t)w * nst + k];

@@ -30,6 +30,21 @@ int main(int argc, char** argv)
     d.step_wrench(1e-3, NULL, 100);
     const bool same_drag = std::memcmp(c.state().data(), d.state().data(), c.state().size() * sizeof(double)) == 0;
     std::printf("with drag: same_drag=%d status=%d\n", (int)same_drag, c.status(0));
-    return (same && same_drag) ? 0 : 1;
+    // per-world parameters: the same topology, gravity weaker from world to world; world 0 keeps the scene and must equal the plain simulator
+    std::vector<mh_world_params> rec((size_t)B);
+    for (int w = 0; w < B; w++) {
+      mh_world_params_from_scene(&io.scene, /*statics=*/NULL, &rec[w]);
+      for (int k = 0; k < 3; k++) rec[w].gravity[k] *= 1.0 - 0.1 * w;
+    }
+    MobyHip::BatchedTimeSteppingSimulator* e = MobyHip::BatchedTimeSteppingSimulator::with_params(io.scene, NULL, rec.data(), B, io.state, true);
+    e->step(1e-3, 50);
+    e->set_params(&rec[0], /*first=*/1, /*count=*/1);          // world 1 gets the scene's gravity back for the second half
+    e->step(1e-3, 50);
+    const size_t nst = (size_t)io.scene.nb * MH_BODY_STATE;
+    const bool same_w0 = std::memcmp(e->state().data(), b.state().data(), nst * sizeof(double)) == 0;
+    const bool differ = std::memcmp(e->state().data() + 3 * nst, b.state().data() + 3 * nst, nst * sizeof(double)) != 0;
+    std::printf("per-world gravity: same_w0=%d world 3 differs=%d status=%d\n", (int)same_w0, (int)differ, e->status(3));
+    delete e;
+    return (same && same_drag && same_w0 && differ) ? 0 : 1;
   } catch (const std::exception& e) { std::printf("error: %s\n", e.what()); return 1; }
 }

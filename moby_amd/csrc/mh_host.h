@@ -89,7 +89,7 @@ MH_HIDDEN hipError_t mh_launch_lcp_blky(MH_LCP_BLOCK_LAUNCH_ARGS);   // the lcp_
 MH_HIDDEN hipError_t mh_launch_lcp_blk1(MH_LCP_BLOCK_LAUNCH_ARGS);
 MH_HIDDEN hipError_t mh_launch_lcp_blk2(MH_LCP_BLOCK_LAUNCH_ARGS);   // two wavefronts per problem (lcp_lemke kinds, n <= 512, large batches)   // one wavefront per problem (lcp_lemke kinds, n <= 512, large batches)
 
-// the five builds of the many-worlds kernel, one translation unit each (mh_world_{small,wheel,large,large_bsp,large_st}.hip; the table in mh_world.hip)
+// the six builds of the many-worlds kernel, one translation unit each (mh_world_{small,wheel,large,large_bsp,large_st,large_pw}.hip; the table in mh_world.hip)
 typedef void (*mh_world_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*);
 struct mh_world_variant {
   mh_world_kernel kernel;
@@ -104,7 +104,8 @@ MH_HIDDEN const mh_world_variant* mh_world_variant_wheel_prof();
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_prof();
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_bsp();      // the large variant with box-sphere pairs (MHW_BSP; mh_world_large_bsp.hip)
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_st();       // ... and with static bodies (MHW_STATICS; mh_world_large_st.hip)
-// the same five with recurrent forces and the caller's wrench in the forward dynamics (mh_world_*_forces.hip): the plain arguments, then the stored terms
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_pw();       // ... and with per-world parameters (MHW_PARAMS; mh_world_large_pw.hip)
+// the same six with recurrent forces and the caller's wrench in the forward dynamics (mh_world_*_forces.hip): the plain arguments, then the stored terms
 // (device copy of mh_world_forces, or NULL), the wrench schedule (rows x B x nb x 6 doubles, or NULL) and its rows
 typedef void (*mh_world_forced_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*,
                                        const mh_world_forces*, const double*, int);
@@ -118,6 +119,7 @@ MH_HIDDEN const mh_world_forced_variant* mh_world_variant_wheel_forces();
 MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_forces();
 MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_bsp_forces();
 MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_st_forces();
+MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_pw_forces();
 
 // mh_debug_set keys 1 / 2 (test hooks; defined in mh_capi.hip)
 extern MH_HIDDEN int mh_g_debug_ka;
@@ -130,5 +132,6 @@ extern MH_HIDDEN int mh_g_debug_artic_pack;          // mh_debug_set(9, v): the 
 extern MH_HIDDEN int mh_g_debug_reglu;               // mh_debug_set(10, v): lcp_fast's register-resident dense LU (mh_lu_reg.inc)
 extern MH_HIDDEN int mh_g_debug_world_bsp;           // mh_debug_set(15, v): batches that would take the large world variant through its box-sphere build
 extern MH_HIDDEN int mh_g_debug_world_st;            // mh_debug_set(16, v): batches that would take the box-sphere build through the statics build
+extern MH_HIDDEN int mh_g_debug_world_pw;            // mh_debug_set(17, v): batches that would take the statics build through the per-world-parameters build
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Host side of the many-worlds stepping ABI (include/moby_hip.h: mh_world_batch_*).  The kernels live in
-// mh_world_{small,wheel,large,large_bsp,large_st}.hip; this file chooses the build for a scene (g_builds) and owns the device buffers.
+// mh_world_{small,wheel,large,large_bsp,large_st,large_pw}.hip; this file chooses the build for a scene (g_builds) and owns the device buffers.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -18,7 +18,7 @@ struct Pow10TableH { double v[64]; };
 namespace {
 // The builds of the world kernel (mh_world_wave.inc), one row each: the plain code object, the one with forces in its forward dynamics (MHW_FORCES) and the
 // one with the phase profiler's stamps -- null where there is none: mh_world_batch_profile then launches the production object and reports zeros.
-enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_COUNT };
+enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_LARGE_PW, WB_COUNT };
 struct world_build {
   const mh_world_variant* (*plain)();
   const mh_world_forced_variant* (*forced)();
@@ -30,6 +30,7 @@ const world_build g_builds[WB_COUNT] = {
   { mh_world_variant_large,     mh_world_variant_large_forces,     mh_world_variant_large_prof },
   { mh_world_variant_large_bsp, mh_world_variant_large_bsp_forces, nullptr },     // box-sphere pairs (MHW_BSP)
   { mh_world_variant_large_st,  mh_world_variant_large_st_forces,  nullptr },     // + static bodies (MHW_STATICS)
+  { mh_world_variant_large_pw,  mh_world_variant_large_pw_forces,  nullptr },     // + per-world parameters (MHW_PARAMS)
 };
 // The __constant__ tables are one copy per DEVICE (hipMemcpyToSymbol writes the current device's): uploaded once per device, keyed on the
 // device current at create, under a lock -- as mh_artic_batch_create does for its own table.
@@ -122,9 +123,59 @@ int check_statics(const mh_scene* sc, const mh_world_statics* st)
   }
   return MH_OK;
 }
+// the refusals of one mh_world_params record (include/moby_hip.h, "Per-world parameters"): the values that check_scene / check_statics validate in the shared
+// records, validated for world w.  sc and st (or null) have passed their own checks: they give the topology.
+int check_params(const mh_scene* sc, const mh_world_statics* st, const mh_world_params* r, int w)
+{
+  const int nstat = st ? st->n : 0, hg = sc->has_ground ? 1 : 0, ntot = sc->nb + hg + nstat;
+  for (int b = 0; b < sc->nb; b++) {
+    if (!(r->mass[b] > 0.0)) return fail(MH_ERR_INVALID_ARG, "world %d: mass[%d] must be > 0", w, b);
+    for (int k = 0; k < 3; k++) if (!(r->inertia[b][k] > 0.0)) return fail(MH_ERR_INVALID_ARG, "world %d: inertia[%d] must be > 0", w, b);
+    if (sc->geom_type[b] == MH_GEOM_SPHERE && !(r->geom_dim[b][0] > 0.0)) return fail(MH_ERR_INVALID_ARG, "world %d: geom_dim[%d]: radius must be > 0", w, b);
+    if (sc->geom_type[b] == MH_GEOM_BOX)
+      for (int k = 0; k < 3; k++) if (!(r->geom_dim[b][k] > 0.0)) return fail(MH_ERR_INVALID_ARG, "world %d: geom_dim[%d]: box edge lengths must be > 0", w, b);
+  }
+  for (int q = 0; q < 3; q++) if (!std::isfinite(r->gravity[q])) return fail(MH_ERR_INVALID_ARG, "world %d: gravity is not finite", w);
+  if (hg) {
+    for (int q = 0; q < 9; q++) if (!std::isfinite(r->plane_R[q])) return fail(MH_ERR_INVALID_ARG, "world %d: plane_R is not finite", w);
+    for (int q = 0; q < 3; q++) if (!std::isfinite(r->plane_o[q])) return fail(MH_ERR_INVALID_ARG, "world %d: plane_o is not finite", w);
+  }
+  for (int p = 0; p < ntot * (ntot - 1) / 2; p++) {
+    if (!std::isfinite(r->cp_epsilon[p])) return fail(MH_ERR_INVALID_ARG, "world %d: cp_epsilon[%d] is not finite", w, p);
+    if (!std::isfinite(r->cp_mu_coulomb[p])) return fail(MH_ERR_INVALID_ARG, "world %d: cp_mu_coulomb[%d] is not finite", w, p);
+    if (!std::isfinite(r->cp_mu_viscous[p])) return fail(MH_ERR_INVALID_ARG, "world %d: cp_mu_viscous[%d] is not finite", w, p);
+    if (!std::isfinite(r->cp_compliance[p])) return fail(MH_ERR_INVALID_ARG, "world %d: cp_compliance[%d] is not finite", w, p);
+  }
+  for (int k = 0; k < nstat; k++) {
+    for (int q = 0; q < 9; q++) if (!std::isfinite(r->st_R[k][q])) return fail(MH_ERR_INVALID_ARG, "world %d: st_R[%d] is not finite", w, k);
+    for (int q = 0; q < 3; q++) if (!std::isfinite(r->st_o[k][q])) return fail(MH_ERR_INVALID_ARG, "world %d: st_o[%d] is not finite", w, k);
+    if (st->type[k] != MH_STATIC_BOX) continue;
+    for (int q = 0; q < 3; q++) if (!(r->st_dim[k][q] > 0.0) || !std::isfinite(r->st_dim[k][q])) return fail(MH_ERR_INVALID_ARG, "world %d: st_dim[%d]: box edge lengths must be > 0", w, k);
+  }
+  return MH_OK;
+}
 } // namespace
 
 extern "C" {
+
+void mh_world_params_from_scene(const mh_scene* sc, const mh_world_statics* st, mh_world_params* out)
+{
+  std::memset(out, 0, sizeof(*out));
+  std::memcpy(out->mass, sc->mass, sizeof(out->mass));
+  std::memcpy(out->inertia, sc->inertia, sizeof(out->inertia));
+  std::memcpy(out->geom_dim, sc->geom_dim, sizeof(out->geom_dim));
+  std::memcpy(out->plane_R, sc->plane_R, sizeof(out->plane_R));
+  std::memcpy(out->plane_o, sc->plane_o, sizeof(out->plane_o));
+  std::memcpy(out->gravity, sc->gravity, sizeof(out->gravity));
+  std::memcpy(out->cp_epsilon, sc->cp_epsilon, sizeof(out->cp_epsilon));
+  std::memcpy(out->cp_mu_coulomb, sc->cp_mu_coulomb, sizeof(out->cp_mu_coulomb));
+  std::memcpy(out->cp_mu_viscous, sc->cp_mu_viscous, sizeof(out->cp_mu_viscous));
+  std::memcpy(out->cp_compliance, sc->cp_compliance, sizeof(out->cp_compliance));
+  if (!st) return;
+  std::memcpy(out->st_R, st->R, sizeof(out->st_R));
+  std::memcpy(out->st_o, st->o, sizeof(out->st_o));
+  std::memcpy(out->st_dim, st->dim, sizeof(out->st_dim));
+}
 
 void mh_scene_defaults(mh_scene* s)
 {
@@ -158,6 +209,9 @@ struct mh_world_batch {
   mh_world_forced_kernel fkernel;   // that row's forced object: launched while forces are stored or when a wrench is passed
   bool has_forces;                  // mh_world_batch_set_forces stored terms != 0
   mh_world_forces* d_forces;        // their device copy (allocated by the first set_forces)
+  bool has_params;                  // created with per-world records (mh_world_batch_create_params): set_params / set_params_dev may replace them
+  mh_world_params* d_params;        // the B records behind the statics record in d_scene's allocation (the per-world-parameters build only), or null
+  mh_world_statics statics;         // the statics the batch was created with (n = 0 without): the topology set_params validates against
 };
 
 namespace {
@@ -197,6 +251,11 @@ int mh_world_batch_create(const mh_scene* scene, int B, mh_world_batch** out)
 
 int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics* statics, int B, mh_world_batch** out)
 {
+  return mh_world_batch_create_params(scene, statics, nullptr, B, out);
+}
+
+int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, mh_world_batch** out)
+{
   if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
   *out = nullptr;
   int rc = statics ? check_statics(scene, statics) : MH_OK;
@@ -205,6 +264,7 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
   rc = check_scene(scene, nstat);
   if (rc != MH_OK) return rc;
   if (B <= 0) return fail(MH_ERR_INVALID_ARG, "batch must be > 0");
+  if (params) for (int w = 0; w < B; w++) { rc = check_params(scene, nstat > 0 ? statics : nullptr, params + w, w); if (rc != MH_OK) return rc; }
   if (mh_device_count() <= 0) return fail(MH_ERR_NO_DEVICE, "no HIP device visible");
   { const hipError_t te = tables_for_current_device();
     if (te != hipSuccess) return fail(MH_ERR_HIP, "constant table upload failed: %s", hipGetErrorString(te)); }
@@ -235,9 +295,13 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
     if (wb->build == WB_LARGE && (bsp || mh_g_debug_world_bsp != 0)) wb->build = WB_LARGE_BSP;       // (key 15: every large batch through the box-sphere build)
     // static bodies need the statics build; every other batch launches what it launched (key 16: the box-sphere batches through the statics build)
     if (nstat > 0 || (wb->build == WB_LARGE_BSP && mh_g_debug_world_st != 0)) wb->build = WB_LARGE_ST;
+    // per-world records need the per-world-parameters build, whatever the scene; every other batch launches what it launched (key 17: the statics batches
+    // through it, every record filled from the scene)
+    if (params || (wb->build == WB_LARGE_ST && mh_g_debug_world_pw != 0)) wb->build = WB_LARGE_PW;
     wb->kernel = g_builds[wb->build].plain()->kernel;
     wb->fkernel = g_builds[wb->build].forced()->kernel;
     wb->has_forces = false; wb->d_forces = nullptr;
+    wb->has_params = params != nullptr; wb->d_params = nullptr;
   }
   wb->d_scene = nullptr; wb->d_state = nullptr; wb->d_aux = nullptr; wb->d_lu_ws = nullptr;
   // device scene record, followed by the spoke-tip table p1 = (cos(theta) R, sin(theta) R), theta = pi i 2 / N
@@ -250,13 +314,28 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
   // ... and by the statics record (n = 0 without statics), which only the statics build reads
   mh_world_statics strec; std::memset(&strec, 0, sizeof(strec));
   if (nstat > 0) strec = *statics;
-  hipError_t e = hipMalloc(&wb->d_scene, sizeof(mh_scene) + sizeof(tips) + sizeof(strec));
+  wb->statics = strec;
+  // ... and, in the per-world-parameters build, by the B records (scene | spoke tips | statics | params[B]): the kernel finds them behind the statics record
+  const size_t params_off = sizeof(mh_scene) + sizeof(tips) + sizeof(strec);
+  static_assert((sizeof(mh_scene) + sizeof(tips) + sizeof(mh_world_statics)) % 8 == 0 && sizeof(mh_world_params) == 335 * sizeof(double), "params records: 8-byte aligned, doubles only");
+  const size_t params_bytes = wb->build == WB_LARGE_PW ? (size_t)B * sizeof(mh_world_params) : 0;
+  hipError_t e = hipMalloc(&wb->d_scene, params_off + params_bytes);
   if (e == hipSuccess) e = hipMalloc(&wb->d_lu_ws, (size_t)B * wb->nmax * wb->nmax * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&wb->d_state, (size_t)B * scene->nb * MH_BODY_STATE * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&wb->d_aux, (size_t)B * sizeof(mh_world_aux));
   if (e == hipSuccess) e = hipMemcpy(wb->d_scene, scene, sizeof(mh_scene), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<char*>(wb->d_scene) + sizeof(mh_scene), tips, sizeof(tips), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<char*>(wb->d_scene) + sizeof(mh_scene) + sizeof(tips), &strec, sizeof(strec), hipMemcpyHostToDevice);
+  if (e == hipSuccess && params_bytes) {
+    wb->d_params = reinterpret_cast<mh_world_params*>(reinterpret_cast<char*>(wb->d_scene) + params_off);
+    if (params) e = hipMemcpy(wb->d_params, params, params_bytes, hipMemcpyHostToDevice);
+    else {                                                        // key 17: every world's record is the scene
+      std::vector<mh_world_params> rec((size_t)B);
+      mh_world_params_from_scene(scene, nstat > 0 ? statics : nullptr, &rec[0]);
+      for (int w = 1; w < B; w++) rec[w] = rec[0];
+      e = hipMemcpy(wb->d_params, rec.data(), params_bytes, hipMemcpyHostToDevice);
+    }
+  }
   if (e == hipSuccess) e = hipMemset(wb->d_state, 0, (size_t)B * scene->nb * MH_BODY_STATE * sizeof(double));
   if (e == hipSuccess) {
     std::vector<mh_world_aux> a((size_t)B);
@@ -337,6 +416,37 @@ int mh_world_batch_set_forces(mh_world_batch* wb, const mh_world_forces* host)
   return MH_OK;
 }
 
+namespace {
+int params_range(mh_world_batch* wb, const void* src, int first, int count)
+{
+  if (!wb || !src) return fail(MH_ERR_INVALID_ARG, "null batch / records");
+  if (!wb->has_params || !wb->d_params) return fail(MH_ERR_INVALID_ARG, "the batch was created without per-world parameters (mh_world_batch_create_params)");
+  if (first < 0 || count < 0 || first > wb->B || count > wb->B - first) return fail(MH_ERR_INVALID_ARG, "worlds %d .. %d outside the batch of %d", first, first + count, wb->B);
+  return MH_OK;
+}
+}  // namespace
+
+int mh_world_batch_set_params(mh_world_batch* wb, const mh_world_params* host, int first, int count)
+{
+  int rc = params_range(wb, host, first, count);
+  if (rc != MH_OK) return rc;
+  for (int k = 0; k < count; k++) { rc = check_params(&wb->scene, wb->statics.n > 0 ? &wb->statics : nullptr, host + k, first + k); if (rc != MH_OK) return rc; }
+  if (count == 0) return MH_OK;
+  MH_ON_DEVICE(wb);
+  MH_HIP(hipMemcpy(wb->d_params + first, host, (size_t)count * sizeof(mh_world_params), hipMemcpyHostToDevice));
+  return MH_OK;
+}
+
+int mh_world_batch_set_params_dev(mh_world_batch* wb, void* stream, const mh_world_params* dev, int first, int count)
+{
+  const int rc = params_range(wb, dev, first, count);
+  if (rc != MH_OK) return rc;
+  if (count == 0) return MH_OK;
+  MH_ON_DEVICE(wb);
+  MH_HIP(hipMemcpyAsync(wb->d_params + first, dev, (size_t)count * sizeof(mh_world_params), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return MH_OK;
+}
+
 int mh_world_batch_step_wrench(mh_world_batch* wb, void* stream, double dt, int nsteps, double* traj_dev,
                                const int* ids_dev, int count, const double* wrench_dev, int rows)
 {
@@ -367,7 +477,7 @@ int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* ph
   // the PROFILE object of the batch's build: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
   const world_build& row = g_builds[wb->build];
   // (a batch with stored forces: the forced production kernel -- it steps the worlds under their forces and has no stamps, so every cycle count is 0)
-  // (a batch on the box-sphere or the statics build: likewise, there is no stamped object of it -- the production kernel steps the worlds, every cycle count is 0)
+  // (a batch on the box-sphere, the statics or the per-world-parameters build: likewise, there is no stamped object of it -- the production kernel steps the worlds, every cycle count is 0)
   if (wb->has_forces || !row.prof) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
   else
   hipLaunchKernelGGL(row.prof()->kernel, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
@@ -482,11 +592,17 @@ int mh_world_step_batch_forces(const mh_scene* scene, const mh_world_forces* for
 int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* forces, int B, double dt, int nsteps,
                                 double* state, mh_world_aux* aux, double* traj, const mh_world_statics* statics)
 {
+  return mh_world_step_batch_params(scene, forces, statics, nullptr, B, dt, nsteps, state, aux, traj);
+}
+
+int mh_world_step_batch_params(const mh_scene* scene, const mh_world_forces* forces, const mh_world_statics* statics, const mh_world_params* params,
+                               int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj)
+{
   if (B == 0 || nsteps == 0) return MH_OK;
   if (B < 0 || nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative batch or step count");
   if (!state || !aux) return fail(MH_ERR_INVALID_ARG, "null state/aux");
   mh_world_batch* wb = nullptr;
-  int rc = mh_world_batch_create_statics(scene, statics, B, &wb);
+  int rc = mh_world_batch_create_params(scene, statics, params, B, &wb);
   if (rc != MH_OK) return rc;
   double* dtraj = nullptr;
   const size_t sz_tr = (size_t)B * nsteps * scene->nb * 7 * sizeof(double);

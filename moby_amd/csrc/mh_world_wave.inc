@@ -46,12 +46,18 @@
 //               "box-sphere pairs").
 //   MHW_STATICS (mh_world_large_st*.hip; needs MHW_BSP) adds several static bodies -- planes and boxes, each with a frame of its own -- beside the free
 //               bodies (include/moby_hip.h, "static bodies").
+//   MHW_PARAMS  (mh_world_large_pw*.hip; needs MHW_STATICS) takes every VALUE of the scene -- masses, inertias, shapes, gravity, the ground frame, contact
+//               parameters, the statics' frames and sizes -- from the world's own mh_world_params record instead of the shared scene and statics records
+//               (include/moby_hip.h, "per-world parameters").  The topology (counts, types, enabled pairs, cone edges, tolerances) stays the scene's.
 // The geometry that mirrors the reference is written ONCE for all builds.  A plane is always named by its body index; the builds differ in a few small
 // accessors only, and these are all the MHW_BSP / MHW_STATICS conditionals of the file:
 //   MHW_STATICS  the gs / gst tables (declaration; filled in the kernel entry, with ntot); plane_R / plane_o / plane_body; is_ground / is_sbox (is_sbox is
 //                `false` without); the table arm of box_frame; the static-box arm of bounds()
 //   MHW_BSP      the box-sphere section itself (is_sphere ... bsp_sdist) and its two call sites in pair_geom and contact_geom_body; box_plane_pair; the
 //                box-box arm of broad_phase (without MHW_BSP a box-sphere pair is not kept either)
+//   MHW_PARAMS   in the kernel entry only: `pv`, the record the cache fill reads its values from (the world's mh_world_params, or the scene itself), and
+//                MHW_ST_R / MHW_ST_O / MHW_ST_DIM, the statics' values (the world's st_* rows, or the shared statics record).  The fill under them is
+//                written once; nothing after the fill reads global scene memory, so there is no other conditional and no LDS of its own.
 // A feature that changes this file keeps the INSTRUCTIONS of the builds it does not concern, not their text: tools/world_asm_diff.py compares every world
 // code object of two source trees function by function (DESIGN.md 4.1).
 #include "mh_world_common.h"
@@ -1922,6 +1928,22 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
 #if MHW_STATICS
   // the statics record follows the spoke-tip table behind the scene record (mh_world.hip lays all three out in one allocation)
   const mh_world_statics& sst = *reinterpret_cast<const mh_world_statics*>(reinterpret_cast<const double*>(scp + 1) + 2 * MH_MAX_SPOKES);
+#endif
+  // `pv` is where the cache fill below takes the scene's VALUES from; counts, types, enabled pairs, cone edges and tolerances are always `sc`'s / `sst`'s
+#if MHW_PARAMS
+  // the B per-world records follow the statics record (scene | spoke tips | statics | params[B]); w is the world's index in the batch, also under ids
+  static_assert((sizeof(mh_scene) + 2 * MH_MAX_SPOKES * sizeof(double) + sizeof(mh_world_statics)) % 8 == 0 && sizeof(mh_world_params) % 8 == 0, "params records must be 8-byte aligned");
+  const mh_world_params& pv = reinterpret_cast<const mh_world_params*>(&sst + 1)[w];
+#define MHW_ST_R(k) pv.st_R[k]
+#define MHW_ST_O(k) pv.st_o[k]
+#define MHW_ST_DIM(k) pv.st_dim[k]
+#else
+  const mh_scene& pv = sc;
+#define MHW_ST_R(k) sst.R[k]
+#define MHW_ST_O(k) sst.o[k]
+#define MHW_ST_DIM(k) sst.dim[k]
+#endif
+#if MHW_STATICS
   const int hg = sc.has_ground ? 1 : 0, nst_ = sst.n;
   const int nb = sc.nb, ntot = sc.nb + hg + nst_, npt = ntot * (ntot - 1) / 2;
   if (nb < 1 || nst_ < 0 || ntot > MH_MAX_BODIES + 1) return;      // (refused at create; never index past the tables)
@@ -1929,9 +1951,9 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
     const int k = lane - hg;                                        // slot `lane` = body nb + lane: the scene's ground first, static k at has_ground + k
     const bool gr = k < 0;
     gst[lane] = gr ? MH_STATIC_PLANE : sst.type[k];
-    for (int q = 0; q < 9; q++) gs[S_R + 9*lane + q] = gr ? sc.plane_R[q] : sst.R[k][q];
-    for (int q = 0; q < 3; q++) gs[S_O + 3*lane + q] = gr ? sc.plane_o[q] : sst.o[k][q];
-    const double x = gr ? 0.0 : sst.dim[k][0], y = gr ? 0.0 : sst.dim[k][1], z = gr ? 0.0 : sst.dim[k][2];
+    for (int q = 0; q < 9; q++) gs[S_R + 9*lane + q] = gr ? pv.plane_R[q] : MHW_ST_R(k)[q];
+    for (int q = 0; q < 3; q++) gs[S_O + 3*lane + q] = gr ? pv.plane_o[q] : MHW_ST_O(k)[q];
+    const double x = gr ? 0.0 : MHW_ST_DIM(k)[0], y = gr ? 0.0 : MHW_ST_DIM(k)[1], z = gr ? 0.0 : MHW_ST_DIM(k)[2];
     gs[S_DIM + 3*lane] = x; gs[S_DIM + 3*lane + 1] = y; gs[S_DIM + 3*lane + 2] = z;
     const double hx = x / 2.0, hy = y / 2.0, hz = z / 2.0;
     gs[S_RAD + lane] = sqrt((hx*hx + hy*hy) + hz*hz);
@@ -1943,7 +1965,7 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
   if (lane < nb) {
     gi[I_GEOM + lane] = sc.geom_type[lane];
     { const int gt = sc.geom_type[lane];
-      const double x = sc.geom_dim[lane][0], y = sc.geom_dim[lane][1], z = sc.geom_dim[lane][2];
+      const double x = pv.geom_dim[lane][0], y = pv.geom_dim[lane][1], z = pv.geom_dim[lane][2];
       double rad = 0.0, rmax = 0.0;
       if (gt == MH_GEOM_SPHERE) { rad = x; rmax = x; }
       else if (gt == MH_GEOM_BOX) {                                  // CCD.cpp:1056-1063 (half diagonal) / BoxPrimitive.h:44 (full diagonal)
@@ -1955,14 +1977,14 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
       gd[D_GDIM + 3*lane] = x; gd[D_GDIM + 3*lane + 1] = y; gd[D_GDIM + 3*lane + 2] = z;
 #endif
     }
-    gd[D_MASS + lane] = sc.mass[lane];
-    for (int k = 0; k < 3; k++) gd[D_INERTIA + 3*lane + k] = sc.inertia[lane][k];
+    gd[D_MASS + lane] = pv.mass[lane];
+    for (int k = 0; k < 3; k++) gd[D_INERTIA + 3*lane + k] = pv.inertia[lane][k];
   }
-  if (lane < 9) gd[D_PLANE_R + lane] = sc.plane_R[lane];
-  if (lane < 3) { gd[D_PLANE_O + lane] = sc.plane_o[lane]; gd[D_GRAV + lane] = sc.gravity[lane]; }
+  if (lane < 9) gd[D_PLANE_R + lane] = pv.plane_R[lane];
+  if (lane < 3) { gd[D_PLANE_O + lane] = pv.plane_o[lane]; gd[D_GRAV + lane] = pv.gravity[lane]; }
   if (lane < npt) {
-    gd[D_PMU + lane] = sc.cp_mu_coulomb[lane]; gd[D_PMUV + lane] = sc.cp_mu_viscous[lane];
-    gd[D_PEPS + lane] = sc.cp_epsilon[lane]; gd[D_PCOMP + lane] = sc.cp_compliance[lane];
+    gd[D_PMU + lane] = pv.cp_mu_coulomb[lane]; gd[D_PMUV + lane] = pv.cp_mu_viscous[lane];
+    gd[D_PEPS + lane] = pv.cp_epsilon[lane]; gd[D_PCOMP + lane] = pv.cp_compliance[lane];
     gi[I_PNK + lane] = sc.cp_nk[lane]; gi[I_PEN + lane] = sc.pair_enabled[lane];
   }
 #if MHW_FORCES
@@ -2033,6 +2055,9 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
 }
 
 #undef MHW_FN
+#undef MHW_ST_R
+#undef MHW_ST_O
+#undef MHW_ST_DIM
 #undef plane_body
 #undef box_plane_pair
 } } // namespace mh::MHW_NS

@@ -1,6 +1,7 @@
 """Host-side scene description for the many-worlds stepper.
 
-ctypes mirrors of ``mh_scene`` / ``mh_world_aux`` (include/moby_hip.h) and
+ctypes mirrors of ``mh_scene`` / ``mh_world_aux`` / ``mh_world_forces`` /
+``mh_world_statics`` / ``mh_world_params`` (include/moby_hip.h) and
 builders for the reference scenes the BASELINE configs name:
 
 * ``sphere_stack_scene``   /root/reference/example/stacks/sphere-stack.xml
@@ -132,6 +133,48 @@ def make_statics(items):
             st.o[k][q] = o[q]
             st.dim[k][q] = it["box"][q] if "box" in it else 0.0
     return st
+
+
+class mh_world_params(ctypes.Structure):
+    """One world's values (include/moby_hip.h, "Per-world parameters"): what a world of a batch may have of its own while the topology stays the
+    scene's.  Doubles only; a spokes body's ``geom_dim`` row is not read."""
+    _fields_ = [("mass", ctypes.c_double * MH_MAX_BODIES), ("inertia", (ctypes.c_double * 3) * MH_MAX_BODIES),
+                ("geom_dim", (ctypes.c_double * 3) * MH_MAX_BODIES),
+                ("plane_R", ctypes.c_double * 9), ("plane_o", ctypes.c_double * 3), ("gravity", ctypes.c_double * 3),
+                ("cp_epsilon", ctypes.c_double * MH_MAX_PAIRS), ("cp_mu_coulomb", ctypes.c_double * MH_MAX_PAIRS),
+                ("cp_mu_viscous", ctypes.c_double * MH_MAX_PAIRS), ("cp_compliance", ctypes.c_double * MH_MAX_PAIRS),
+                ("st_R", (ctypes.c_double * 9) * MH_MAX_STATICS), ("st_o", (ctypes.c_double * 3) * MH_MAX_STATICS),
+                ("st_dim", (ctypes.c_double * 3) * MH_MAX_STATICS)]
+
+
+PARAMS_DTYPE = np.dtype([
+    ("mass", np.float64, MH_MAX_BODIES), ("inertia", np.float64, (MH_MAX_BODIES, 3)), ("geom_dim", np.float64, (MH_MAX_BODIES, 3)),
+    ("plane_R", np.float64, 9), ("plane_o", np.float64, 3), ("gravity", np.float64, 3),
+    ("cp_epsilon", np.float64, MH_MAX_PAIRS), ("cp_mu_coulomb", np.float64, MH_MAX_PAIRS),
+    ("cp_mu_viscous", np.float64, MH_MAX_PAIRS), ("cp_compliance", np.float64, MH_MAX_PAIRS),
+    ("st_R", np.float64, (MH_MAX_STATICS, 9)), ("st_o", np.float64, (MH_MAX_STATICS, 3)), ("st_dim", np.float64, (MH_MAX_STATICS, 3))])
+PARAMS_DOUBLES = 335
+assert PARAMS_DTYPE.itemsize == ctypes.sizeof(mh_world_params) == 8 * PARAMS_DOUBLES, (PARAMS_DTYPE.itemsize, ctypes.sizeof(mh_world_params))
+
+
+def make_params(sc, statics, B):
+    """B records (numpy structured array of PARAMS_DTYPE) equal to the scene and its statics (or None), for the caller to edit by field:
+    ``p["gravity"][w] = ...``, ``p["cp_mu_coulomb"][w, slot] = ...``, ``p["st_o"][w, k] = ...``.  Pure Python: what mh_world_params_from_scene gives."""
+    p = np.zeros(B, dtype=PARAMS_DTYPE)
+    for f in ("mass", "inertia", "geom_dim", "plane_R", "plane_o", "gravity", "cp_epsilon", "cp_mu_coulomb", "cp_mu_viscous", "cp_compliance"):
+        p[f][:] = np.ctypeslib.as_array(getattr(sc, f))
+    if statics is not None:
+        for f, g in (("st_R", "R"), ("st_o", "o"), ("st_dim", "dim")):
+            p[f][:] = np.ctypeslib.as_array(getattr(statics, g))
+    return p
+
+
+def params_array(params, B=None):
+    """a contiguous PARAMS_DTYPE array of the caller's records (checked: dtype and, if given, the number of records)"""
+    p = np.ascontiguousarray(params)
+    if p.dtype != PARAMS_DTYPE or p.ndim != 1 or (B is not None and p.shape[0] != B):
+        raise ValueError("params: a 1-d array of scene.PARAMS_DTYPE%s is needed" % ("" if B is None else " with %d records" % B))
+    return p
 
 
 def set_pair_params(sc, i, j, ntot, epsilon=0.0, mu_coulomb=0.0, mu_viscous=0.0, compliance=0.0, nk=4, enabled=1):

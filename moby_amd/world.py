@@ -16,7 +16,7 @@ from . import scene as S
 class WorldBatch:
     """B worlds of one scene; numpy host arrays in/out (copies through the library)."""
 
-    def __init__(self, scene, state, aux=None, seed=1, forces=None, statics=None):
+    def __init__(self, scene, state, aux=None, seed=1, forces=None, statics=None, params=None):
         self.scene = scene
         self.state = np.ascontiguousarray(state, dtype=np.float64)
         self.B = self.state.shape[0]
@@ -24,12 +24,15 @@ class WorldBatch:
         self.aux = S.new_aux(self.B, seed) if aux is None else aux
         self.forces = forces       # S.mh_world_forces (S.make_forces) or None: the scene's recurrent forces
         self.statics = statics     # S.mh_world_statics (S.make_statics, io.load_xml_statics) or None: static bodies beside the scene's ground
+        self.params = None if params is None else S.params_array(params, self.B)   # S.PARAMS_DTYPE records (S.make_params), one per world, or None
 
     def step(self, dt, nsteps=1, want_traj=False, wrench=None):
         """wrench: (B, nb, 6) or (rows >= nsteps, B, nb, 6) host array (fx fy fz tx ty tz per world and body), or None."""
         if self.forces is not None or wrench is not None:
             return self._step_forced(dt, nsteps, want_traj, wrench)
         lib = _lib.load()
+        if self.params is not None:
+            return self._step_params(dt, nsteps, want_traj)
         if self.statics is not None:
             traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
             _lib.check(lib.mh_world_step_batch_statics(ctypes.addressof(self.scene), None, self.B, float(dt), int(nsteps), self.state.ctypes.data,
@@ -42,9 +45,20 @@ class WorldBatch:
         _lib.check(rc)
         return traj
 
+    def _step_params(self, dt, nsteps, want_traj):
+        """per-world records (and forces, if any): the host convenience mh_world_step_batch_params"""
+        traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
+        _lib.check(_lib.load().mh_world_step_batch_params(ctypes.addressof(self.scene), None if self.forces is None else ctypes.addressof(self.forces),
+                                                          None if self.statics is None else ctypes.addressof(self.statics), self.params.ctypes.data,
+                                                          self.B, float(dt), int(nsteps), self.state.ctypes.data, self.aux.ctypes.data,
+                                                          None if traj is None else traj.ctypes.data))
+        return traj
+
     def _step_forced(self, dt, nsteps, want_traj, wrench):
         """forces alone: the host convenience mh_world_step_batch_forces; with a wrench: the same round trip through a device batch, which is what
         takes one (a DEVICE array)"""
+        if wrench is None and self.params is not None:
+            return self._step_params(dt, nsteps, want_traj)
         if wrench is None:
             traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
             _lib.check(_lib.load().mh_world_step_batch_statics(ctypes.addressof(self.scene), ctypes.addressof(self.forces), self.B, float(dt), int(nsteps),
@@ -52,7 +66,7 @@ class WorldBatch:
                                                                None if self.statics is None else ctypes.addressof(self.statics)))
             return traj
         import torch
-        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics)
+        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics, params=self.params)
         try:
             if self.forces is not None:
                 dev.set_forces(self.forces)
@@ -75,12 +89,16 @@ class WorldBatchDevice:
     """Same, with state/aux resident in HBM behind an ``mh_world_batch`` handle;
     ``step`` is asynchronous on the given (torch) stream."""
 
-    def __init__(self, scene, state, seed=1, aux=None, statics=None):
+    def __init__(self, scene, state, seed=1, aux=None, statics=None, params=None):
         lib = _lib.load()
         self.scene = scene
         self.B = state.shape[0]
         self.handle = ctypes.c_void_p()
-        if statics is None:
+        if params is not None:
+            p = S.params_array(params, self.B)
+            _lib.check(lib.mh_world_batch_create_params(ctypes.addressof(scene), None if statics is None else ctypes.addressof(statics), p.ctypes.data, self.B,
+                                                        ctypes.byref(self.handle)))
+        elif statics is None:
             _lib.check(lib.mh_world_batch_create(ctypes.addressof(scene), self.B, ctypes.byref(self.handle)))
         else:
             _lib.check(lib.mh_world_batch_create_statics(ctypes.addressof(scene), ctypes.addressof(statics), self.B, ctypes.byref(self.handle)))
@@ -91,6 +109,28 @@ class WorldBatchDevice:
     def set_forces(self, forces):
         """The scene's recurrent forces (S.mh_world_forces from S.make_forces / io.load_xml_forces; None clears them): every later step honours them."""
         _lib.check(_lib.load().mh_world_batch_set_forces(self.handle, None if forces is None else ctypes.addressof(forces)))
+
+    def set_params(self, params, first=0):
+        """Replaces the records of worlds first .. first + len(params) (a host array of S.PARAMS_DTYPE; validated by the library).  The batch must have been
+        created with params=; not while a launch is in flight."""
+        p = S.params_array(params)
+        _lib.check(_lib.load().mh_world_batch_set_params(self.handle, p.ctypes.data, int(first), int(p.shape[0])))
+
+    def set_params_dev(self, params, first=0, count=None, stream=None):
+        """The same from DEVICE memory, an asynchronous copy on `stream`, NOT validated (include/moby_hip.h): a contiguous float64 tensor on the batch's
+        device shaped (count, S.PARAMS_DOUBLES), or a raw device pointer with `count` given."""
+        if hasattr(params, "data_ptr"):
+            if not (params.is_cuda and params.is_contiguous() and str(params.dtype) == "torch.float64"):
+                raise ValueError("params: a contiguous float64 tensor on the device is needed")
+            shape = tuple(params.shape)
+            if len(shape) != 2 or shape[1] != S.PARAMS_DOUBLES or (count is not None and int(count) != shape[0]):
+                raise ValueError("params: shape %s, expected (%s, %d)" % (shape, "count" if count is None else int(count), S.PARAMS_DOUBLES))
+            ptr, count = ctypes.c_void_p(params.data_ptr()), shape[0]
+        else:
+            if count is None:
+                raise ValueError("params: a raw device pointer needs count")
+            ptr = ctypes.c_void_p(int(params))
+        _lib.check(_lib.load().mh_world_batch_set_params_dev(self.handle, stream, ptr, int(first), int(count)))
 
     def _wrench_args(self, wrench, rows):
         """(device pointer, rows) of a wrench schedule: a float64 torch tensor on the batch's device shaped (B, nb, 6) or (rows, B, nb, 6), or a raw
