@@ -309,6 +309,8 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    batches created after it; default 0: only batches created with statics; for A/B runs).
                                             key 17: world batches that would take the statics build stepped by the per-world-parameters build, mh_world_large_pw*.hip, every
                                                    record filled from the scene (1, for batches created after it; default 0: only batches created with records; for A/B runs).
+                                            key 18: world batches that would take the per-world-parameters build stepped by the contact-report build, mh_world_large_rp*.hip, with
+                                                   a NULL report (1, for batches created after it; default 0: only batches created for the report; for A/B runs).
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);
@@ -486,6 +488,50 @@ int mh_world_batch_set_params_dev(mh_world_batch* wb, void* stream, const mh_wor
 /* Host convenience: mh_world_step_batch_statics with per-world records (forces, statics and params may each be NULL). */
 int mh_world_step_batch_params(const mh_scene* scene, const mh_world_forces* forces, const mh_world_statics* statics, const mh_world_params* params,
                                int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj);
+
+
+/* Contact report.  What the reference hands to ConstraintSimulator::constraint_post_callback_fn (ConstraintSimulator.cpp:353) -- the step's contact
+ * constraints, each with the contact_impulse that ImpactConstraintHandler::update_from_stacked accumulated (ImpactConstraintHandler.cpp:298-327) --
+ * reduced per PAIR inside the step and left in device memory.  For world w (its index in the BATCH, also under ids_dev, as the wrench schedule is
+ * indexed), step s of the launch and pair slot p (the scene's triangular index over ntot = nb + has_ground + n bodies, npt = ntot (ntot - 1) / 2 slots)
+ * there is one row of MH_REPORT_PAIR doubles at report_dev[((w * nsteps + s) * npt + p) * MH_REPORT_PAIR].  The rows of a step start at zero and
+ * accumulate over the step's mini-steps, in mini-step order.
+ * A mini-step's contacts are folded once handle_impacts has returned without a throw (the point of CSim:353), in constraint-list order (canonical:
+ * pair-list order, then generator order) -- also when the handler returned early because nothing was impacting: its contacts then count, with zero
+ * impulse.  A mini-step whose handler threw is not folded: the step's rows keep what earlier mini-steps left.  Every step of a world that is passed
+ * over (MH_WORLD_LCP_FAILED) writes zero rows.  A world with MH_WORLD_UNSUPPORTED or MH_WORLD_STALLED has undefined rows from then on, as its state is.
+ * Contact c of pair p = (i < j) carries accumulated (cn, cs, ct): zeroed when the list is built; every application of impulses of the impact side adds
+ * to them (QP model, restitution passes, no-slip model; oracle/world.hpp Contact::imp is the same quantity, moby_hip_impact.h returns it per contact);
+ * the stabiliser's corrections add nothing.  It adds to the row:
+ *   [0]     += 1.0                  contacts, summed over mini-steps
+ *   [1]     += cn
+ *   [2..4]  += sign * jv            jv = (n cn + s cs) + t ct componentwise, every product and sum rounded on its own, n / s / t the stored normal and
+ *                                   tangents; sign = +1 if contact_geom1 is body i, otherwise -1: the impulse ON THE LOWER-INDEX BODY of the pair, in world
+ *                                   axes (body j received the negative; against the ground or a static, i is the body)
+ *   [5..7]  += pt * cn              the contact point weighted by its normal impulse: the centre of pressure is [5..7] / [1]
+ * Entries of disabled or never-touching slots stay 0.
+ * Such a batch steps through code objects of its own (mh_world_large_rp.hip, mh_world_large_rp_forces.hip: the per-world-parameters build with
+ * MHW_REPORT) whatever its scene; every other batch launches what it launched.  There is no stamped build: mh_world_batch_profile reports zero cycles.
+ * Key 18 of mh_debug_set sends batches that would take the per-world-parameters build through these objects with a NULL report (A/B runs; no result
+ * changes).
+ * NOT built: the report inside the small and wheel variants (such batches take the objects above, as batches with records take theirs); per-contact
+ * lists (the row is per pair); the angular impulse about the centre of mass ([5..7] gives the lever); the report in the large-world (moby_hip_stack.h)
+ * and articulated steppers; the stabiliser's corrections (they move positions and carry no impulse in the reference either,
+ * ConstraintStabilization.cpp:457). */
+/* (no existing layout changes, so MH_VERSION stays 102; a caller that needs to know tests this macro) */
+#define MH_WORLD_REPORT 1
+#define MH_REPORT_PAIR 8
+/* mh_world_batch_create_params with the report build.  params == NULL fills every record from the scene (as key 17 does); mh_world_batch_set_params
+ * then refuses, as for any batch created without records.  The refusals are mh_world_batch_create_params' and run before the device is looked for. */
+int mh_world_batch_create_report(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, mh_world_batch** out);
+/* mh_world_batch_step_wrench plus the report: report_dev is a DEVICE array B x nsteps x npt x MH_REPORT_PAIR doubles (B the worlds of the batch, also
+ * with ids_dev: only the listed worlds' rows are written).  report_dev == NULL IS mh_world_batch_step_wrench.  MH_ERR_INVALID_ARG if report_dev != NULL
+ * on a batch not created by mh_world_batch_create_report.  Every other stepping entry takes such a batch and writes no report. */
+int mh_world_batch_step_report(mh_world_batch* wb, void* stream, double dt, int nsteps, double* traj_dev,
+                               const int* ids_dev, int count, const double* wrench_dev, int rows, double* report_dev);
+/* Host convenience: mh_world_step_batch_params with the report in a HOST array B x nsteps x npt x MH_REPORT_PAIR (NULL: mh_world_step_batch_params). */
+int mh_world_step_batch_report(const mh_scene* scene, const mh_world_forces* forces, const mh_world_statics* statics, const mh_world_params* params,
+                               int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj, double* report);
 
 #ifdef __cplusplus
 }

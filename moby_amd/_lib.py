@@ -76,6 +76,9 @@ SYMBOLS = {
     "mh_world_batch_set_params": (_i, [_vp, _vp, _i, _i]),
     "mh_world_batch_set_params_dev": (_i, [_vp, _vp, _vp, _i, _i]),
     "mh_world_step_batch_params": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "mh_world_batch_create_report": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(_vp)]),
+    "mh_world_batch_step_report": (_i, [_vp, _vp, _d, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "mh_world_step_batch_report": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
     # include/moby_hip_impact.h
     "mh_impact_batch_create": (_i, [_i, _i, _i, _i, _vp, _vp, ctypes.POINTER(_vp)]),
     "mh_impact_batch_destroy": (_i, [_vp]),

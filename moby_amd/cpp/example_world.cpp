@@ -6,6 +6,8 @@
 #include "MobyHipSimulator.h"
 #include "../../include/moby_hip_io.h"
 
+static bool same_drag_is_plain(const std::vector<double>& a, const std::vector<double>& b) { return std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0; }
+
 int main(int argc, char** argv)
 {
   if (argc < 2) { std::printf("usage: example_world <scene.xml>\n"); return 2; }
@@ -45,6 +47,23 @@ int main(int argc, char** argv)
     const bool differ = std::memcmp(e->state().data() + 3 * nst, b.state().data() + 3 * nst, nst * sizeof(double)) != 0;
     std::printf("per-world gravity: same_w0=%d world 3 differs=%d status=%d\n", (int)same_w0, (int)differ, e->status(3));
     delete e;
-    return (same && same_drag && same_w0 && differ) ? 0 : 1;
+    // the contact report: the same worlds with the per-pair impulse rows of each step; the state must equal the plain simulator's, and the normal impulses
+    // of the 100 steps must be what holds the spheres up somewhere (a positive sum)
+    MobyHip::BatchedTimeSteppingSimulator* r = MobyHip::BatchedTimeSteppingSimulator::with_report(io.scene, NULL, NULL, B, io.state, true);
+    r->step_report(1e-3, 100);
+    const bool same_rep = std::memcmp(r->state().data(), b.state().data(), b.state().size() * sizeof(double)) == 0;
+    double cn_sum = 0.0, contacts = 0.0;
+    for (int s = 0; s < 100; s++) for (int p = 0; p < r->num_pair_slots(); p++) { contacts += r->report_row(0, s, p)[0]; cn_sum += r->report_row(0, s, p)[1]; }
+    std::printf("contact report: same_state=%d contacts=%g sum cn=%g\n", (int)same_rep, contacts, cn_sum);
+    // ... and under the drag: step_report steps what step steps, so it must end where the drag simulator `d` ended (not where the plain one did)
+    MobyHip::BatchedTimeSteppingSimulator* q2 = MobyHip::BatchedTimeSteppingSimulator::with_report(io.scene, NULL, NULL, B, io.state, true);
+    q2->set_forces(drag);
+    q2->step_report(1e-3, 50);
+    q2->step_wrench(1e-3, NULL, 50);
+    const bool same_rep_drag = std::memcmp(q2->state().data(), d.state().data(), d.state().size() * sizeof(double)) == 0 && !same_drag_is_plain(d.state(), b.state());
+    std::printf("contact report with drag: same_rep_drag=%d\n", (int)same_rep_drag);
+    delete q2;
+    delete r;
+    return (same && same_drag && same_w0 && differ && same_rep && same_rep_drag && cn_sum > 0.0 && contacts > 0.0) ? 0 : 1;
   } catch (const std::exception& e) { std::printf("error: %s\n", e.what()); return 1; }
 }

@@ -186,6 +186,7 @@ int mh_g_debug_artic_pair = 0;
 int mh_g_debug_artic_bsp = 0;
 int mh_g_debug_world_st = 0;   // mh_debug_set(16, v): 1 = a batch that would take the box-sphere build, created after the call, launches mh_world_large_st*.hip instead (A/B runs)
 int mh_g_debug_world_pw = 0;   // mh_debug_set(17, v): 1 = a batch that would take the statics build, created after the call, launches mh_world_large_pw*.hip instead, every record = the scene (A/B runs)
+int mh_g_debug_world_rp = 0;   // mh_debug_set(18, v): 1 = a batch that would take the per-world-parameters build, created after the call, launches mh_world_large_rp*.hip instead, with a NULL report (A/B runs)
 int mh_g_debug_world_bsp = 0;  // mh_debug_set(15, v): 1 = a batch that would take the large world variant, created after the call, launches mh_world_large_bsp*.hip instead (A/B runs)
 int mh_g_debug_reglu = 1;    // mh_debug_set(10, v): 1 = lcp_fast (n > 64, 1024-thread geometry) solves _Msub of up to 191 rows in registers (mh_lu_reg.inc), 0 = through the HBM workspace
 int mh_g_debug_fastgeom = 0; // mh_debug_set(8, v): the lcp_fast kinds' thread geometry for n <= 512 -- 0 choose, 1 = 256, 2 = 1024, 3 = 64, 4 = 128 threads per problem
@@ -365,6 +366,7 @@ extern "C" int mh_debug_set(int key, int value)
   if (key == 15) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "world box-sphere-kernel switch outside {0, 1}"); mh_g_debug_world_bsp = value; return MH_OK; }
   if (key == 16) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "world statics-kernel switch outside {0, 1}"); mh_g_debug_world_st = value; return MH_OK; }
   if (key == 17) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "world per-world-parameters-kernel switch outside {0, 1}"); mh_g_debug_world_pw = value; return MH_OK; }
+  if (key == 18) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "world contact-report-kernel switch outside {0, 1}"); mh_g_debug_world_rp = value; return MH_OK; }
   if (key == 9) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "articulated packing outside {0, 1}"); mh_g_debug_artic_pack = value; return MH_OK; }
   if (key == 8) { if (value < 0 || value > 4) return fail(MH_ERR_INVALID_ARG, "lcp_fast geometry outside {0 .. 4}"); mh_g_debug_fastgeom = value; return MH_OK; }
   if (key == 2) { if (value < 0 || value > 5) return fail(MH_ERR_INVALID_ARG, "block solver geometry outside {0 .. 5}"); mh_g_debug_blk = value; return MH_OK; }

@@ -89,7 +89,7 @@ MH_HIDDEN hipError_t mh_launch_lcp_blky(MH_LCP_BLOCK_LAUNCH_ARGS);   // the lcp_
 MH_HIDDEN hipError_t mh_launch_lcp_blk1(MH_LCP_BLOCK_LAUNCH_ARGS);
 MH_HIDDEN hipError_t mh_launch_lcp_blk2(MH_LCP_BLOCK_LAUNCH_ARGS);   // two wavefronts per problem (lcp_lemke kinds, n <= 512, large batches)   // one wavefront per problem (lcp_lemke kinds, n <= 512, large batches)
 
-// the six builds of the many-worlds kernel, one translation unit each (mh_world_{small,wheel,large,large_bsp,large_st,large_pw}.hip; the table in mh_world.hip)
+// the seven builds of the many-worlds kernel, one translation unit each (mh_world_{small,wheel,large,large_bsp,large_st,large_pw,large_rp}.hip; the table in mh_world.hip)
 typedef void (*mh_world_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*);
 struct mh_world_variant {
   mh_world_kernel kernel;
@@ -120,6 +120,23 @@ MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_forces();
 MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_bsp_forces();
 MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_st_forces();
 MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_pw_forces();
+// the per-world-parameters build with the contact report (MHW_REPORT; mh_world_large_rp.hip, mh_world_large_rp_forces.hip): the arguments of the plain / the
+// forced kernel, then the report rows (B x nsteps x npt x MH_REPORT_PAIR doubles, or NULL: nothing is written)
+typedef void (*mh_world_report_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*, double*);
+typedef void (*mh_world_report_forced_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*,
+                                              const mh_world_forces*, const double*, int, double*);
+struct mh_world_report_variant {
+  mh_world_report_kernel kernel;
+  int ph_count;
+  hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
+};
+struct mh_world_report_forced_variant {
+  mh_world_report_forced_kernel kernel;
+  int ph_count;
+  hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
+};
+MH_HIDDEN const mh_world_report_variant* mh_world_variant_large_rp();
+MH_HIDDEN const mh_world_report_forced_variant* mh_world_variant_large_rp_forces();
 
 // mh_debug_set keys 1 / 2 (test hooks; defined in mh_capi.hip)
 extern MH_HIDDEN int mh_g_debug_ka;
@@ -133,5 +150,6 @@ extern MH_HIDDEN int mh_g_debug_reglu;               // mh_debug_set(10, v): lcp
 extern MH_HIDDEN int mh_g_debug_world_bsp;           // mh_debug_set(15, v): batches that would take the large world variant through its box-sphere build
 extern MH_HIDDEN int mh_g_debug_world_st;            // mh_debug_set(16, v): batches that would take the box-sphere build through the statics build
 extern MH_HIDDEN int mh_g_debug_world_pw;            // mh_debug_set(17, v): batches that would take the statics build through the per-world-parameters build
+extern MH_HIDDEN int mh_g_debug_world_rp;            // mh_debug_set(18, v): batches that would take the per-world-parameters build through the report build
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Host side of the many-worlds stepping ABI (include/moby_hip.h: mh_world_batch_*).  The kernels live in
-// mh_world_{small,wheel,large,large_bsp,large_st,large_pw}.hip; this file chooses the build for a scene (g_builds) and owns the device buffers.
+// mh_world_{small,wheel,large,large_bsp,large_st,large_pw,large_rp}.hip; this file chooses the build for a scene (g_builds) and owns the device buffers.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -18,7 +18,9 @@ struct Pow10TableH { double v[64]; };
 namespace {
 // The builds of the world kernel (mh_world_wave.inc), one row each: the plain code object, the one with forces in its forward dynamics (MHW_FORCES) and the
 // one with the phase profiler's stamps -- null where there is none: mh_world_batch_profile then launches the production object and reports zeros.
-enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_LARGE_PW, WB_COUNT };
+// The report build (MHW_REPORT) is no row of the table: its kernels take one more argument, the report rows, so it has an entry of its own types below
+// (g_report_build) and WB_LARGE_RP names it in mh_world_batch::build.
+enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_LARGE_PW, WB_COUNT, WB_LARGE_RP = WB_COUNT };
 struct world_build {
   const mh_world_variant* (*plain)();
   const mh_world_forced_variant* (*forced)();
@@ -32,6 +34,11 @@ const world_build g_builds[WB_COUNT] = {
   { mh_world_variant_large_st,  mh_world_variant_large_st_forces,  nullptr },     // + static bodies (MHW_STATICS)
   { mh_world_variant_large_pw,  mh_world_variant_large_pw_forces,  nullptr },     // + per-world parameters (MHW_PARAMS)
 };
+// + the contact report (MHW_REPORT; mh_world_large_rp.hip, mh_world_large_rp_forces.hip): the plain and the forced object, no stamped one
+const struct {
+  const mh_world_report_variant* (*plain)();
+  const mh_world_report_forced_variant* (*forced)();
+} g_report_build = { mh_world_variant_large_rp, mh_world_variant_large_rp_forces };
 // The __constant__ tables are one copy per DEVICE (hipMemcpyToSymbol writes the current device's): uploaded once per device, keyed on the
 // device current at create, under a lock -- as mh_artic_batch_create does for its own table.
 std::mutex g_tables_mu;
@@ -54,6 +61,8 @@ hipError_t init_tables()
     if (g_tables_err == hipSuccess) g_tables_err = r.forced()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
     if (g_tables_err == hipSuccess && r.prof) g_tables_err = r.prof()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   }
+  if (g_tables_err == hipSuccess) g_tables_err = g_report_build.plain()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
+  if (g_tables_err == hipSuccess) g_tables_err = g_report_build.forced()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   return g_tables_err;
 }
 hipError_t tables_for_current_device()
@@ -212,14 +221,26 @@ struct mh_world_batch {
   bool has_params;                  // created with per-world records (mh_world_batch_create_params): set_params / set_params_dev may replace them
   mh_world_params* d_params;        // the B records behind the statics record in d_scene's allocation (the per-world-parameters build only), or null
   mh_world_statics statics;         // the statics the batch was created with (n = 0 without): the topology set_params validates against
+  bool has_report;                  // created for the contact report (mh_world_batch_create_report): mh_world_batch_step_report may pass rows
+  mh_world_report_kernel rkernel;   // the report build's objects (build == WB_LARGE_RP: launched instead of kernel / fkernel, which are then null)
+  mh_world_report_forced_kernel rfkernel;
 };
 
 namespace {
 // the one launch behind every stepping entry: the plain kernel, or the forced one when the batch stores forces or the caller passes a wrench
 int launch_step(mh_world_batch* wb, hipStream_t stream, int grid, double dt, int nsteps, double* traj_dev, unsigned long long* prof, const int* ids_dev,
-                const double* wrench_dev, int rows)
+                const double* wrench_dev, int rows, double* report_dev = nullptr)
 {
-  if (wb->has_forces || wrench_dev)
+  if (wb->build == WB_LARGE_RP) {                                   // the report build: the same arguments, then the report rows (or null)
+    if (wb->has_forces || wrench_dev)
+      hipLaunchKernelGGL(wb->rfkernel, dim3(grid), dim3(64), 0, stream,
+                         (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev,
+                         (const mh_world_forces*)(wb->has_forces ? wb->d_forces : nullptr), wrench_dev, rows, report_dev);
+    else
+      hipLaunchKernelGGL(wb->rkernel, dim3(grid), dim3(64), 0, stream,
+                         (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev, report_dev);
+  }
+  else if (wb->has_forces || wrench_dev)
     hipLaunchKernelGGL(wb->fkernel, dim3(grid), dim3(64), 0, stream,
                        (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev,
                        (const mh_world_forces*)(wb->has_forces ? wb->d_forces : nullptr), wrench_dev, rows);
@@ -238,8 +259,10 @@ int mh_world_batch_occupancy(mh_world_batch* wb)
   if (!wb) return fail(MH_ERR_INVALID_ARG, "null batch");
   MH_ON_DEVICE(wb);
   int n = 0;
-  hipError_t e = wb->has_forces ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->fkernel, 64, 0)
-                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->kernel, 64, 0);
+  hipError_t e = wb->build == WB_LARGE_RP ? (wb->has_forces ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->rfkernel, 64, 0)
+                                                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->rkernel, 64, 0))
+                 : wb->has_forces ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->fkernel, 64, 0)
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->kernel, 64, 0);
   if (e != hipSuccess) return fail(MH_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
   return n;
 }
@@ -254,7 +277,21 @@ int mh_world_batch_create_statics(const mh_scene* scene, const mh_world_statics*
   return mh_world_batch_create_params(scene, statics, nullptr, B, out);
 }
 
+namespace { int create_batch(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, bool report, mh_world_batch** out); }
+
 int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, mh_world_batch** out)
+{
+  return create_batch(scene, statics, params, B, false, out);
+}
+
+int mh_world_batch_create_report(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, mh_world_batch** out)
+{
+  return create_batch(scene, statics, params, B, true, out);
+}
+
+namespace {
+// the one create behind every entry.  report: the batch takes the contact-report build (its records filled from the scene where the caller gave none)
+int create_batch(const mh_scene* scene, const mh_world_statics* statics, const mh_world_params* params, int B, bool report, mh_world_batch** out)
 {
   if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
   *out = nullptr;
@@ -298,8 +335,12 @@ int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* 
     // per-world records need the per-world-parameters build, whatever the scene; every other batch launches what it launched (key 17: the statics batches
     // through it, every record filled from the scene)
     if (params || (wb->build == WB_LARGE_ST && mh_g_debug_world_pw != 0)) wb->build = WB_LARGE_PW;
-    wb->kernel = g_builds[wb->build].plain()->kernel;
-    wb->fkernel = g_builds[wb->build].forced()->kernel;
+    // the contact report needs the report build, whatever the scene; every other batch launches what it launched (key 18: the per-world-parameters
+    // batches through it, with a null report)
+    if (report || (wb->build == WB_LARGE_PW && mh_g_debug_world_rp != 0)) wb->build = WB_LARGE_RP;
+    wb->has_report = report; wb->kernel = nullptr; wb->fkernel = nullptr; wb->rkernel = nullptr; wb->rfkernel = nullptr;
+    if (wb->build == WB_LARGE_RP) { wb->rkernel = g_report_build.plain()->kernel; wb->rfkernel = g_report_build.forced()->kernel; }
+    else { wb->kernel = g_builds[wb->build].plain()->kernel; wb->fkernel = g_builds[wb->build].forced()->kernel; }
     wb->has_forces = false; wb->d_forces = nullptr;
     wb->has_params = params != nullptr; wb->d_params = nullptr;
   }
@@ -315,10 +356,10 @@ int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* 
   mh_world_statics strec; std::memset(&strec, 0, sizeof(strec));
   if (nstat > 0) strec = *statics;
   wb->statics = strec;
-  // ... and, in the per-world-parameters build, by the B records (scene | spoke tips | statics | params[B]): the kernel finds them behind the statics record
+  // ... and, in the per-world-parameters build and the report build, by the B records (scene | spoke tips | statics | params[B]): the kernel finds them behind the statics record
   const size_t params_off = sizeof(mh_scene) + sizeof(tips) + sizeof(strec);
   static_assert((sizeof(mh_scene) + sizeof(tips) + sizeof(mh_world_statics)) % 8 == 0 && sizeof(mh_world_params) == 335 * sizeof(double), "params records: 8-byte aligned, doubles only");
-  const size_t params_bytes = wb->build == WB_LARGE_PW ? (size_t)B * sizeof(mh_world_params) : 0;
+  const size_t params_bytes = (wb->build == WB_LARGE_PW || wb->build == WB_LARGE_RP) ? (size_t)B * sizeof(mh_world_params) : 0;
   hipError_t e = hipMalloc(&wb->d_scene, params_off + params_bytes);
   if (e == hipSuccess) e = hipMalloc(&wb->d_lu_ws, (size_t)B * wb->nmax * wb->nmax * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&wb->d_state, (size_t)B * scene->nb * MH_BODY_STATE * sizeof(double));
@@ -329,7 +370,7 @@ int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* 
   if (e == hipSuccess && params_bytes) {
     wb->d_params = reinterpret_cast<mh_world_params*>(reinterpret_cast<char*>(wb->d_scene) + params_off);
     if (params) e = hipMemcpy(wb->d_params, params, params_bytes, hipMemcpyHostToDevice);
-    else {                                                        // key 17: every world's record is the scene
+    else {                                                        // key 17, or a report batch without records: every world's record is the scene
       std::vector<mh_world_params> rec((size_t)B);
       mh_world_params_from_scene(scene, nstat > 0 ? statics : nullptr, &rec[0]);
       for (int w = 1; w < B; w++) rec[w] = rec[0];
@@ -347,6 +388,7 @@ int mh_world_batch_create_params(const mh_scene* scene, const mh_world_statics* 
   *out = wb;
   return MH_OK;
 }
+}  // namespace
 
 int mh_world_batch_device(const mh_world_batch* wb) { return wb ? wb->device : fail(MH_ERR_INVALID_ARG, "null batch"); }
 
@@ -450,16 +492,24 @@ int mh_world_batch_set_params_dev(mh_world_batch* wb, void* stream, const mh_wor
 int mh_world_batch_step_wrench(mh_world_batch* wb, void* stream, double dt, int nsteps, double* traj_dev,
                                const int* ids_dev, int count, const double* wrench_dev, int rows)
 {
+  return mh_world_batch_step_report(wb, stream, dt, nsteps, traj_dev, ids_dev, count, wrench_dev, rows, nullptr);
+}
+
+// the one stepping entry with every optional argument: report_dev == NULL is mh_world_batch_step_wrench, with its checks and messages
+int mh_world_batch_step_report(mh_world_batch* wb, void* stream, double dt, int nsteps, double* traj_dev,
+                               const int* ids_dev, int count, const double* wrench_dev, int rows, double* report_dev)
+{
   if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
   if (rows < 1) return fail(MH_ERR_INVALID_ARG, "wrench: rows = %d (must be >= 1)", rows);
   if (rows > 1 && rows < nsteps) return fail(MH_ERR_INVALID_ARG, "wrench: %d rows for %d steps (1 row, or one per step)", rows, nsteps);
   if (traj_dev && ids_dev) return fail(MH_ERR_INVALID_ARG, "a trajectory buffer cannot be combined with an id list");
   if (!wb) return fail(MH_ERR_INVALID_ARG, "null batch");
+  if (report_dev && (!wb->has_report || wb->build != WB_LARGE_RP)) return fail(MH_ERR_INVALID_ARG, "the batch was created without the contact report (mh_world_batch_create_report)");
   MH_ON_DEVICE(wb);
   if (ids_dev && (count < 0 || count > wb->B)) return fail(MH_ERR_INVALID_ARG, "bad id count (%d of %d)", count, wb->B);
   if (nsteps == 0 || (ids_dev && count == 0)) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
-  return launch_step(wb, (hipStream_t)stream, ids_dev ? count : wb->B, dt, nsteps, traj_dev, nullptr, ids_dev, wrench_dev, rows);
+  return launch_step(wb, (hipStream_t)stream, ids_dev ? count : wb->B, dt, nsteps, traj_dev, nullptr, ids_dev, wrench_dev, rows, report_dev);
 }
 
 int mh_world_profile_phase_count(void) { return g_builds[WB_LARGE].plain()->ph_count; }
@@ -475,12 +525,12 @@ int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* ph
   MH_HIP(hipMalloc(&dprof, sz));
   MH_HIP(hipMemset(dprof, 0, sz));
   // the PROFILE object of the batch's build: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
-  const world_build& row = g_builds[wb->build];
+  const bool stamped = wb->build < WB_COUNT && g_builds[wb->build].prof != nullptr;
   // (a batch with stored forces: the forced production kernel -- it steps the worlds under their forces and has no stamps, so every cycle count is 0)
-  // (a batch on the box-sphere, the statics or the per-world-parameters build: likewise, there is no stamped object of it -- the production kernel steps the worlds, every cycle count is 0)
-  if (wb->has_forces || !row.prof) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
+  // (a batch on the box-sphere, the statics, the per-world-parameters or the report build: likewise, there is no stamped object of it -- the production kernel steps the worlds, every cycle count is 0)
+  if (wb->has_forces || !stamped) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
   else
-  hipLaunchKernelGGL(row.prof()->kernel, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
+  hipLaunchKernelGGL(g_builds[wb->build].prof()->kernel, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
                      (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, (double*)nullptr, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, dprof, (const int*)nullptr);
   hipError_t e = hipDeviceSynchronize();
   std::vector<unsigned long long> h((size_t)wb->B * PHC);
@@ -598,21 +648,33 @@ int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* fo
 int mh_world_step_batch_params(const mh_scene* scene, const mh_world_forces* forces, const mh_world_statics* statics, const mh_world_params* params,
                                int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj)
 {
+  return mh_world_step_batch_report(scene, forces, statics, params, B, dt, nsteps, state, aux, traj, nullptr);
+}
+
+// report == NULL: mh_world_step_batch_params (a batch created by mh_world_batch_create_params); otherwise a report batch and its rows
+int mh_world_step_batch_report(const mh_scene* scene, const mh_world_forces* forces, const mh_world_statics* statics, const mh_world_params* params,
+                               int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj, double* report)
+{
   if (B == 0 || nsteps == 0) return MH_OK;
   if (B < 0 || nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative batch or step count");
   if (!state || !aux) return fail(MH_ERR_INVALID_ARG, "null state/aux");
   mh_world_batch* wb = nullptr;
-  int rc = mh_world_batch_create_params(scene, statics, params, B, &wb);
+  int rc = report ? mh_world_batch_create_report(scene, statics, params, B, &wb) : mh_world_batch_create_params(scene, statics, params, B, &wb);
   if (rc != MH_OK) return rc;
-  double* dtraj = nullptr;
+  double* dtraj = nullptr; double* drep = nullptr;
   const size_t sz_tr = (size_t)B * nsteps * scene->nb * 7 * sizeof(double);
+  const int ntot = scene->nb + (scene->has_ground ? 1 : 0) + (statics ? statics->n : 0);
+  const size_t sz_rep = (size_t)B * nsteps * (ntot * (ntot - 1) / 2) * MH_REPORT_PAIR * sizeof(double);
   rc = mh_world_batch_upload(wb, state, aux);
   if (rc == MH_OK && forces) rc = mh_world_batch_set_forces(wb, forces);
   if (rc == MH_OK && traj && hipMalloc(&dtraj, sz_tr) != hipSuccess) rc = fail(MH_ERR_HIP, "trajectory allocation failed");
-  if (rc == MH_OK) rc = mh_world_batch_step(wb, nullptr, dt, nsteps, dtraj);
+  if (rc == MH_OK && report && sz_rep && hipMalloc(&drep, sz_rep) != hipSuccess) rc = fail(MH_ERR_HIP, "report allocation failed");
+  if (rc == MH_OK) rc = mh_world_batch_step_report(wb, nullptr, dt, nsteps, dtraj, nullptr, 0, nullptr, 1, drep);
   if (rc == MH_OK) rc = mh_world_batch_download(wb, state, aux);
   if (rc == MH_OK && traj && hipMemcpy(traj, dtraj, sz_tr, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MH_ERR_HIP, "trajectory download failed");
+  if (rc == MH_OK && drep && hipMemcpy(report, drep, sz_rep, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MH_ERR_HIP, "report download failed");
   if (dtraj) (void)hipFree(dtraj);
+  if (drep) (void)hipFree(drep);
   mh_world_batch_destroy(wb);
   return rc;
 }

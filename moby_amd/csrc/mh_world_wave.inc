@@ -49,6 +49,10 @@
 //   MHW_PARAMS  (mh_world_large_pw*.hip; needs MHW_STATICS) takes every VALUE of the scene -- masses, inertias, shapes, gravity, the ground frame, contact
 //               parameters, the statics' frames and sizes -- from the world's own mh_world_params record instead of the shared scene and statics records
 //               (include/moby_hip.h, "per-world parameters").  The topology (counts, types, enabled pairs, cone edges, tolerances) stays the scene's.
+//   MHW_REPORT  (mh_world_large_rp*.hip; needs MHW_PARAMS) adds the per-pair contact impulse report (include/moby_hip.h, "Contact report"): one trailing kernel
+//               argument, the report rows (or NULL: nothing is written, the steps are the same).  Every line it adds sits under #if MHW_REPORT: the
+//               per-contact accumulators g_racc (cleared when the simulator's constraint list is built, added to by apply_impulses(.., 3)) and the fold of
+//               a mini-step's contacts into the step's rows after handle_impacts (report_fold).
 // The geometry that mirrors the reference is written ONCE for all builds.  A plane is always named by its body index; the builds differ in a few small
 // accessors only, and these are all the MHW_BSP / MHW_STATICS conditionals of the file:
 //   MHW_STATICS  the gs / gst tables (declaration; filled in the kernel entry, with ntot); plane_R / plane_o / plane_body; is_ground / is_sbox (is_sbox is
@@ -177,6 +181,15 @@ __shared__ int g_fterms;
 enum { S_R = 0, S_O = 9 * MH_MAX_STATICS, S_DIM = 12 * MH_MAX_STATICS, S_RAD = 15 * MH_MAX_STATICS, S_END = 16 * MH_MAX_STATICS };
 __shared__ double gs[S_END];
 __shared__ int gst[MH_MAX_STATICS];
+#endif
+
+#if MHW_REPORT
+// The contact report (include/moby_hip.h, "Contact report").  g_racc: accumulated (cn, cs, ct) of every contact of the simulator's constraint list -- the
+// reference's contact_impulse in the contact frame, oracle Contact::imp -- 3 MHW_MAX_CONTACTS doubles; g_rep: the rows of this world's current step in the
+// caller's report (npt rows of MH_REPORT_PAIR doubles), or null.  The rows themselves stay in global memory: lane p owns row p, zeroes it at the step's start
+// and adds to it once per mini-step, so no lane ever reads what another wrote.
+__shared__ double g_racc[3 * MHW_MAX_CONTACTS];
+__shared__ double* g_rep;
 #endif
 
 #define MHW_FN __device__ __noinline__
@@ -1265,6 +1278,14 @@ MHW_FN void apply_impulses(int nic, int nib, int ndir) {
     const int b = gi[I_ISLB + bi];
     gd[D_ST + 13*b + 7 + k] = gd[D_ST + 13*b + 7 + k] + dv;
   }
+#if MHW_REPORT
+  // contact_impulse += (cn, cs, ct) (ICH:298-327; oracle apply_impulses): the impact side only -- the stabiliser's call (ndir == 1) moves positions and
+  // leaves no impulse (CStab:457).  Lane j owns contact gi[I_ISLC + j]; the contacts of an island are distinct.
+  if (ndir == 3 && lane < nic) {
+    const int ci = gi[I_ISLC + lane];
+    for (int d = 0; d < 3; d++) g_racc[3*ci + d] = g_racc[3*ci + d] + gd[D_IMP + d * nic + lane];
+  }
+#endif
   wave_sync();
 }
 // update_constraint_velocities_from_impulses (ICH:427-464); row lanes
@@ -1547,6 +1568,9 @@ MH_DEV bool handle_impacts() {                                      // returns t
 MH_DEV void find_unilateral_constraints() {
   const int lane = lane_id();
   const int npairs = geti(I_NPAIRS);
+#if MHW_REPORT
+  for (int e = lane; e < 3 * MHW_MAX_CONTACTS; e += 64) g_racc[e] = 0.0;    // a new constraint list: no contact has received an impulse yet
+#endif
   ContactGeom c; c.has = 0; c.g1 = 0; c.g2 = 0; c.pt = v3(0, 0, 0); c.n = v3(0, 0, 0); c.dist = 0.0;
   int p = 0;
   const double thresh = gd[D_THRESH];
@@ -1669,6 +1693,32 @@ MH_DEV double wheel_ca_loop(double dt) {
 }
 #endif
 
+#if MHW_REPORT
+// Folds the mini-step's contacts into the step's rows, where ConstraintSimulator::constraint_post_callback_fn sees them (CSim:353): after handle_impacts
+// returned without a throw, also when it returned early (the contacts then count with zero impulse).  Lane p owns pair slot p and walks the constraint
+// list in its order, so the order of a row's additions is fixed and no two lanes share a row.
+MH_DEV void report_fold() {
+  const int lane = lane_id();
+  double* rep = g_rep;
+  const int nc = geti(I_NC);
+  wave_sync();
+  if (!rep || lane >= gi[I_NPT]) return;
+  int a, b; pair_bodies(lane, a, b);                                // a < b: the row holds the impulse on body a
+  double* row = rep + MH_REPORT_PAIR * lane;
+  for (int c = 0; c < nc; c++) {
+    if (gi[I_CPAIR + c] != lane) continue;
+    const double cn = g_racc[3*c], cs = g_racc[3*c + 1], ct = g_racc[3*c + 2];
+    const V3 n = Cdir(c, 0), s = Cdir(c, 1), t = Cdir(c, 2), pt = Cpt(c);
+    const V3 jv = (n * cn + s * cs) + t * ct;
+    const double sg = (gi[I_CG1 + c] == a) ? 1.0 : -1.0;
+    row[0] = row[0] + 1.0;
+    row[1] = row[1] + cn;
+    row[2] = row[2] + sg * jv.x; row[3] = row[3] + sg * jv.y; row[4] = row[4] + sg * jv.z;
+    row[5] = row[5] + pt.x * cn; row[6] = row[6] + pt.y * cn; row[7] = row[7] + pt.z * cn;
+  }
+}
+#endif
+
 MH_DEV double do_mini_step(double dt, bool& threw) {               // TSS:114-222; threw: the impact handler's exception left the mini-step before TSS:215
   const int lane = lane_id();
   wave_sync();
@@ -1706,6 +1756,9 @@ MH_DEV double do_mini_step(double dt, bool& threw) {               // TSS:114-22
   tock(PH_CONTACTS, t1);
   threw = handle_impacts();
   if (threw) return h;
+#if MHW_REPORT
+  report_fold();
+#endif
   if (lane == 0) { gd[D_TIME] = gd[D_TIME] + h; g_cnt[CN_MINI]++; }
   wave_sync();
   return h;
@@ -1919,6 +1972,9 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
 #if MHW_FORCES
                      , const mh_world_forces* __restrict__ frc, const double* __restrict__ wrench, int wrows   // stored terms (or NULL), rows x B x nb x 6 wrench (or NULL)
 #endif
+#if MHW_REPORT
+                     , double* __restrict__ report                                                            // B x nsteps x npt x MH_REPORT_PAIR rows (or NULL)
+#endif
                      )
 {
   const int w = ids ? ids[blockIdx.x] : (int)blockIdx.x;      // ids: a subset of the batch in its own launch (mh_world_batch_step_ids)
@@ -2031,6 +2087,15 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
       if (lane < 6 * nb) gf[F_WR + lane] = wrench[((size_t)(wrows > 1 ? s : 0) * B + w) * (size_t)(6 * nb) + lane];
       wave_sync();
     }
+#endif
+#if MHW_REPORT
+    // this step's rows of THIS world (its index in the batch, also under ids) start at zero, each zeroed by the lane that folds into it; a world that
+    // is passed over keeps them zero
+    wave_sync();
+    { double* rows = report ? report + ((size_t)w * nsteps + s) * (size_t)npt * MH_REPORT_PAIR : nullptr;
+      if (lane == 0) g_rep = rows;
+      if (rows && lane < npt) for (int k = 0; k < MH_REPORT_PAIR; k++) rows[MH_REPORT_PAIR * lane + k] = 0.0; }
+    wave_sync();
 #endif
     if (!dead) dead = world_step(dt);
     if (traj) {

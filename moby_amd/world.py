@@ -13,6 +13,31 @@ from . import _lib
 from . import scene as S
 
 
+REPORT_PAIR = 8      # MH_REPORT_PAIR: doubles per (world, step, pair slot) row of the contact report (include/moby_hip.h, "Contact report")
+
+
+def report_npt(scene, statics=None):
+    """pair slots of a scene: triangular over ntot = nb + has_ground + n bodies"""
+    ntot = scene.nb + (1 if scene.has_ground else 0) + (statics.n if statics is not None else 0)
+    return ntot * (ntot - 1) // 2
+
+
+def body_impulses(report, nb, ntot):
+    """Net linear contact impulse per enabled body from a contact report (..., npt, 8) -> (..., nb, 3): row [2..4] of pair slot (i, j) is the impulse on
+    body i; body j, if it is a body (j < nb), received the negative.  Array operators only: numpy arrays and torch tensors alike."""
+    shape = tuple(report.shape[:-2]) + (nb, 3)
+    out = report.new_zeros(shape) if hasattr(report, "new_zeros") else np.zeros(shape, dtype=report.dtype)   # (the one line that asks which of the two)
+    p = 0
+    for i in range(ntot):
+        for j in range(i + 1, ntot):
+            if i < nb:
+                out[..., i, :] = out[..., i, :] + report[..., p, 2:5]
+            if j < nb:
+                out[..., j, :] = out[..., j, :] - report[..., p, 2:5]
+            p += 1
+    return out
+
+
 class WorldBatch:
     """B worlds of one scene; numpy host arrays in/out (copies through the library)."""
 
@@ -26,8 +51,11 @@ class WorldBatch:
         self.statics = statics     # S.mh_world_statics (S.make_statics, io.load_xml_statics) or None: static bodies beside the scene's ground
         self.params = None if params is None else S.params_array(params, self.B)   # S.PARAMS_DTYPE records (S.make_params), one per world, or None
 
-    def step(self, dt, nsteps=1, want_traj=False, wrench=None):
-        """wrench: (B, nb, 6) or (rows >= nsteps, B, nb, 6) host array (fx fy fz tx ty tz per world and body), or None."""
+    def step(self, dt, nsteps=1, want_traj=False, wrench=None, want_report=False):
+        """wrench: (B, nb, 6) or (rows >= nsteps, B, nb, 6) host array (fx fy fz tx ty tz per world and body), or None.
+        want_report: returns (trajectory or None, report) with the contact report (B, nsteps, npt, 8) of include/moby_hip.h, "Contact report"."""
+        if want_report:
+            return self._step_report(dt, nsteps, want_traj, wrench)
         if self.forces is not None or wrench is not None:
             return self._step_forced(dt, nsteps, want_traj, wrench)
         lib = _lib.load()
@@ -53,6 +81,32 @@ class WorldBatch:
                                                           self.B, float(dt), int(nsteps), self.state.ctypes.data, self.aux.ctypes.data,
                                                           None if traj is None else traj.ctypes.data))
         return traj
+
+    def _step_report(self, dt, nsteps, want_traj, wrench):
+        """the report build: the host convenience mh_world_step_batch_report, or with a wrench a device batch created for the report"""
+        traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
+        report = np.zeros((self.B, nsteps, report_npt(self.scene, self.statics), REPORT_PAIR))
+        if wrench is None:
+            _lib.check(_lib.load().mh_world_step_batch_report(ctypes.addressof(self.scene), None if self.forces is None else ctypes.addressof(self.forces),
+                                                              None if self.statics is None else ctypes.addressof(self.statics),
+                                                              None if self.params is None else self.params.ctypes.data,
+                                                              self.B, float(dt), int(nsteps), self.state.ctypes.data, self.aux.ctypes.data,
+                                                              None if traj is None else traj.ctypes.data, report.ctypes.data))
+            return traj, report
+        import torch
+        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics, params=self.params, report=True)
+        try:
+            if self.forces is not None:
+                dev.set_forces(self.forces)
+            tj = torch.zeros(traj.shape, dtype=torch.float64, device="cuda") if want_traj else None
+            rp = torch.zeros(report.shape, dtype=torch.float64, device="cuda")
+            w = torch.as_tensor(np.ascontiguousarray(wrench, dtype=np.float64), device="cuda")
+            dev.step(dt, nsteps, traj_ptr=None if tj is None else tj.data_ptr(), wrench=w, report=rp)
+            self.state[...], aux = dev.download()
+            self.aux[...] = aux
+        finally:
+            dev.close()
+        return (None if tj is None else tj.cpu().numpy()), rp.cpu().numpy()
 
     def _step_forced(self, dt, nsteps, want_traj, wrench):
         """forces alone: the host convenience mh_world_step_batch_forces; with a wrench: the same round trip through a device batch, which is what
@@ -89,12 +143,18 @@ class WorldBatchDevice:
     """Same, with state/aux resident in HBM behind an ``mh_world_batch`` handle;
     ``step`` is asynchronous on the given (torch) stream."""
 
-    def __init__(self, scene, state, seed=1, aux=None, statics=None, params=None):
+    def __init__(self, scene, state, seed=1, aux=None, statics=None, params=None, report=False):
+        """report: the batch is created for the contact report (mh_world_batch_create_report): step / step_ids take report="""
         lib = _lib.load()
         self.scene = scene
         self.B = state.shape[0]
         self.handle = ctypes.c_void_p()
-        if params is not None:
+        self.npt = report_npt(scene, statics)
+        if report:
+            p = None if params is None else S.params_array(params, self.B)
+            _lib.check(lib.mh_world_batch_create_report(ctypes.addressof(scene), None if statics is None else ctypes.addressof(statics),
+                                                        None if p is None else p.ctypes.data, self.B, ctypes.byref(self.handle)))
+        elif params is not None:
             p = S.params_array(params, self.B)
             _lib.check(lib.mh_world_batch_create_params(ctypes.addressof(scene), None if statics is None else ctypes.addressof(statics), p.ctypes.data, self.B,
                                                         ctypes.byref(self.handle)))
@@ -102,6 +162,7 @@ class WorldBatchDevice:
             _lib.check(lib.mh_world_batch_create(ctypes.addressof(scene), self.B, ctypes.byref(self.handle)))
         else:
             _lib.check(lib.mh_world_batch_create_statics(ctypes.addressof(scene), ctypes.addressof(statics), self.B, ctypes.byref(self.handle)))
+        self.device = lib.mh_world_batch_device(self.handle)      # the HIP device the batch lives on: device tensors handed to it must be that device's
         st = np.ascontiguousarray(state, dtype=np.float64)
         aux = S.new_aux(self.B, seed) if aux is None else np.ascontiguousarray(aux)      # aux given: resume from a checkpoint
         _lib.check(lib.mh_world_batch_upload(self.handle, st.ctypes.data, aux.ctypes.data))
@@ -132,13 +193,19 @@ class WorldBatchDevice:
             ptr = ctypes.c_void_p(int(params))
         _lib.check(_lib.load().mh_world_batch_set_params_dev(self.handle, stream, ptr, int(first), int(count)))
 
+    def _on_device(self, t, name):
+        """a contiguous float64 tensor on the batch's own device, or ValueError"""
+        if not (hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64"):
+            raise ValueError("%s: a contiguous float64 tensor on the device is needed" % name)
+        if t.device.index != self.device:
+            raise ValueError("%s: the tensor is on device %s, the batch on device %d" % (name, t.device.index, self.device))
+
     def _wrench_args(self, wrench, rows):
         """(device pointer, rows) of a wrench schedule: a float64 torch tensor on the batch's device shaped (B, nb, 6) or (rows, B, nb, 6), or a raw
         device pointer with `rows` given (rows x B x nb x 6 doubles)."""
         if hasattr(wrench, "data_ptr"):
             nb = self.scene.nb
-            if not (wrench.is_cuda and wrench.is_contiguous() and str(wrench.dtype) == "torch.float64"):
-                raise ValueError("wrench: a contiguous float64 tensor on the device is needed")
+            self._on_device(wrench, "wrench")
             shape = tuple(wrench.shape)
             if shape == (self.B, nb, 6):
                 shape = (1,) + shape
@@ -147,17 +214,36 @@ class WorldBatchDevice:
             return ctypes.c_void_p(wrench.data_ptr()), shape[0]
         return ctypes.c_void_p(int(wrench)), 1 if rows is None else int(rows)
 
-    def step(self, dt, nsteps=1, stream=None, traj_ptr=None, wrench=None, rows=None):
-        """wrench: per-world body wrenches for this launch (see _wrench_args; rows == 1 holds for the launch, rows >= nsteps is one row per step)."""
+    def _report_ptr(self, report, nsteps):
+        """device pointer of a report tensor: contiguous float64 on the batch's device, shaped (B, nsteps, npt, 8) -- B the worlds of the batch"""
+        self._on_device(report, "report")
+        want = (self.B, int(nsteps), self.npt, REPORT_PAIR)
+        if tuple(report.shape) != want:
+            raise ValueError("report: shape %s, expected %s" % (tuple(report.shape), want))
+        return ctypes.c_void_p(report.data_ptr())
+
+    def _step_report(self, dt, nsteps, stream, traj_ptr, ids_ptr, count, wrench, rows, report):
+        wptr, rows = (None, 1) if wrench is None else self._wrench_args(wrench, rows)
+        _lib.check(_lib.load().mh_world_batch_step_report(self.handle, stream, float(dt), int(nsteps), traj_ptr, ids_ptr, int(count), wptr, rows,
+                                                          self._report_ptr(report, nsteps)))
+
+    def step(self, dt, nsteps=1, stream=None, traj_ptr=None, wrench=None, rows=None, report=None):
+        """wrench: per-world body wrenches for this launch (see _wrench_args; rows == 1 holds for the launch, rows >= nsteps is one row per step).
+        report: the contact report of this launch (see _report_ptr; a batch created with report=True)."""
+        if report is not None:
+            return self._step_report(dt, nsteps, stream, traj_ptr, None, 0, wrench, rows, report)
         if wrench is None:
             _lib.check(_lib.load().mh_world_batch_step(self.handle, stream, float(dt), int(nsteps), traj_ptr))
             return
         ptr, rows = self._wrench_args(wrench, rows)
         _lib.check(_lib.load().mh_world_batch_step_wrench(self.handle, stream, float(dt), int(nsteps), traj_ptr, None, 0, ptr, rows))
 
-    def step_ids(self, dt, nsteps, ids_dev_ptr, count, stream=None, wrench=None, rows=None):
+    def step_ids(self, dt, nsteps, ids_dev_ptr, count, stream=None, wrench=None, rows=None, report=None):
         """nsteps of the worlds listed in a DEVICE int32 array (e.g. a torch tensor's data_ptr()) on `stream` (mh_world_batch_step_ids); with a
-        wrench, each listed world reads the schedule at its own index in the batch."""
+        wrench, each listed world reads the schedule at its own index in the batch; with a report (the whole batch's shape), only the listed worlds'
+        rows are written, each at its own index in the batch."""
+        if report is not None:
+            return self._step_report(dt, nsteps, stream, None, ctypes.c_void_p(int(ids_dev_ptr)), count, wrench, rows, report)
         if wrench is None:
             _lib.check(_lib.load().mh_world_batch_step_ids(self.handle, stream, float(dt), int(nsteps), ctypes.c_void_p(int(ids_dev_ptr)), int(count)))
             return
