@@ -90,9 +90,20 @@ MH_HIDDEN hipError_t mh_launch_lcp_blk1(MH_LCP_BLOCK_LAUNCH_ARGS);
 MH_HIDDEN hipError_t mh_launch_lcp_blk2(MH_LCP_BLOCK_LAUNCH_ARGS);   // two wavefronts per problem (lcp_lemke kinds, n <= 512, large batches)   // one wavefront per problem (lcp_lemke kinds, n <= 512, large batches)
 
 // the seven builds of the many-worlds kernel, one translation unit each (mh_world_{small,wheel,large,large_bsp,large_st,large_pw,large_rp}.hip; the table in mh_world.hip)
-typedef void (*mh_world_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*);
+// Everything a stepping launch can carry.  The kernels' argument lists differ by build (mh_world_wave.inc: the forced objects take forces / wrench / wrench_rows,
+// the report objects take report); each code object's launcher passes what its kernel has a parameter for and ignores the rest.
+struct mh_world_launch {
+  hipStream_t stream; int grid;                        // one 64-thread workgroup per world stepped
+  const mh_scene* scene; int B; double dt; int nsteps; double* state; mh_world_aux* aux; double* traj; int nmax; double* lu_ws; int ka;
+  unsigned long long* prof; const int* ids;
+  const mh_world_forces* forces;                       // device copy of the stored terms, or NULL
+  const double* wrench; int wrench_rows;               // the wrench schedule (rows x B x nb x 6 doubles, or NULL) and its rows
+  double* report;                                      // the report rows (B x nsteps x npt x MH_REPORT_PAIR doubles, or NULL: nothing is written)
+};
+// what the host sees of one code object (defined at the end of mh_world_wave.inc)
 struct mh_world_variant {
-  mh_world_kernel kernel;
+  hipError_t (*launch)(const mh_world_launch&);        // launches this object's kernel; hipGetLastError() of the launch
+  hipError_t (*occupancy)(int* blocks_per_cu);         // the runtime's occupancy query for it, 64 threads, no dynamic LDS
   int ph_count;                                        // per-phase cycle accumulators of the profiling launch
   hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
 };
@@ -105,38 +116,15 @@ MH_HIDDEN const mh_world_variant* mh_world_variant_large_prof();
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_bsp();      // the large variant with box-sphere pairs (MHW_BSP; mh_world_large_bsp.hip)
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_st();       // ... and with static bodies (MHW_STATICS; mh_world_large_st.hip)
 MH_HIDDEN const mh_world_variant* mh_world_variant_large_pw();       // ... and with per-world parameters (MHW_PARAMS; mh_world_large_pw.hip)
-// the same six with recurrent forces and the caller's wrench in the forward dynamics (mh_world_*_forces.hip): the plain arguments, then the stored terms
-// (device copy of mh_world_forces, or NULL), the wrench schedule (rows x B x nb x 6 doubles, or NULL) and its rows
-typedef void (*mh_world_forced_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*,
-                                       const mh_world_forces*, const double*, int);
-struct mh_world_forced_variant {
-  mh_world_forced_kernel kernel;
-  int ph_count;
-  hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
-};
-MH_HIDDEN const mh_world_forced_variant* mh_world_variant_small_forces();
-MH_HIDDEN const mh_world_forced_variant* mh_world_variant_wheel_forces();
-MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_forces();
-MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_bsp_forces();
-MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_st_forces();
-MH_HIDDEN const mh_world_forced_variant* mh_world_variant_large_pw_forces();
-// the per-world-parameters build with the contact report (MHW_REPORT; mh_world_large_rp.hip, mh_world_large_rp_forces.hip): the arguments of the plain / the
-// forced kernel, then the report rows (B x nsteps x npt x MH_REPORT_PAIR doubles, or NULL: nothing is written)
-typedef void (*mh_world_report_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*, double*);
-typedef void (*mh_world_report_forced_kernel)(const mh_scene*, int, double, int, double*, mh_world_aux*, double*, int, double*, int, unsigned long long*, const int*,
-                                              const mh_world_forces*, const double*, int, double*);
-struct mh_world_report_variant {
-  mh_world_report_kernel kernel;
-  int ph_count;
-  hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
-};
-struct mh_world_report_forced_variant {
-  mh_world_report_forced_kernel kernel;
-  int ph_count;
-  hipError_t (*upload_tables)(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes);
-};
-MH_HIDDEN const mh_world_report_variant* mh_world_variant_large_rp();
-MH_HIDDEN const mh_world_report_forced_variant* mh_world_variant_large_rp_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_rp();       // ... and with the contact report (MHW_REPORT; mh_world_large_rp.hip)
+// the same seven with recurrent forces and the caller's wrench in the forward dynamics (MHW_FORCES; mh_world_*_forces.hip)
+MH_HIDDEN const mh_world_variant* mh_world_variant_small_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_wheel_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_bsp_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_st_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_pw_forces();
+MH_HIDDEN const mh_world_variant* mh_world_variant_large_rp_forces();
 
 // mh_debug_set keys 1 / 2 (test hooks; defined in mh_capi.hip)
 extern MH_HIDDEN int mh_g_debug_ka;

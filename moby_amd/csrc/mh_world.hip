@@ -18,12 +18,12 @@ struct Pow10TableH { double v[64]; };
 namespace {
 // The builds of the world kernel (mh_world_wave.inc), one row each: the plain code object, the one with forces in its forward dynamics (MHW_FORCES) and the
 // one with the phase profiler's stamps -- null where there is none: mh_world_batch_profile then launches the production object and reports zeros.
-// The report build (MHW_REPORT) is no row of the table: its kernels take one more argument, the report rows, so it has an entry of its own types below
-// (g_report_build) and WB_LARGE_RP names it in mh_world_batch::build.
-enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_LARGE_PW, WB_COUNT, WB_LARGE_RP = WB_COUNT };
+// Every object is one mh_world_variant (mh_host.h): its kernel is launched inside its own translation unit, so the kernels' differing argument lists
+// (forces and wrench in the forced objects, the report rows in the report build) do not show here.
+enum { WB_SMALL = 0, WB_WHEEL, WB_LARGE, WB_LARGE_BSP, WB_LARGE_ST, WB_LARGE_PW, WB_LARGE_RP, WB_COUNT };
 struct world_build {
   const mh_world_variant* (*plain)();
-  const mh_world_forced_variant* (*forced)();
+  const mh_world_variant* (*forced)();
   const mh_world_variant* (*prof)();
 };
 const world_build g_builds[WB_COUNT] = {
@@ -33,12 +33,8 @@ const world_build g_builds[WB_COUNT] = {
   { mh_world_variant_large_bsp, mh_world_variant_large_bsp_forces, nullptr },     // box-sphere pairs (MHW_BSP)
   { mh_world_variant_large_st,  mh_world_variant_large_st_forces,  nullptr },     // + static bodies (MHW_STATICS)
   { mh_world_variant_large_pw,  mh_world_variant_large_pw_forces,  nullptr },     // + per-world parameters (MHW_PARAMS)
+  { mh_world_variant_large_rp,  mh_world_variant_large_rp_forces,  nullptr },     // + the contact report (MHW_REPORT)
 };
-// + the contact report (MHW_REPORT; mh_world_large_rp.hip, mh_world_large_rp_forces.hip): the plain and the forced object, no stamped one
-const struct {
-  const mh_world_report_variant* (*plain)();
-  const mh_world_report_forced_variant* (*forced)();
-} g_report_build = { mh_world_variant_large_rp, mh_world_variant_large_rp_forces };
 // The __constant__ tables are one copy per DEVICE (hipMemcpyToSymbol writes the current device's): uploaded once per device, keyed on the
 // device current at create, under a lock -- as mh_artic_batch_create does for its own table.
 std::mutex g_tables_mu;
@@ -61,8 +57,6 @@ hipError_t init_tables()
     if (g_tables_err == hipSuccess) g_tables_err = r.forced()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
     if (g_tables_err == hipSuccess && r.prof) g_tables_err = r.prof()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   }
-  if (g_tables_err == hipSuccess) g_tables_err = g_report_build.plain()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
-  if (g_tables_err == hipSuccess) g_tables_err = g_report_build.forced()->upload_tables(&ft, sizeof(ft), &p10, sizeof(p10));
   return g_tables_err;
 }
 hipError_t tables_for_current_device()
@@ -210,44 +204,33 @@ struct mh_world_batch {
   int B;
   int nmax;
   int build;                 // row of g_builds (WB_*)
-  mh_world_kernel kernel;    // that row's plain object
   mh_scene* d_scene;
   double* d_lu_ws;
   double* d_state;
   mh_world_aux* d_aux;
-  mh_world_forced_kernel fkernel;   // that row's forced object: launched while forces are stored or when a wrench is passed
-  bool has_forces;                  // mh_world_batch_set_forces stored terms != 0
+  bool has_forces;                  // mh_world_batch_set_forces stored terms != 0: the row's forced object is launched (as it is when a wrench is passed)
   mh_world_forces* d_forces;        // their device copy (allocated by the first set_forces)
   bool has_params;                  // created with per-world records (mh_world_batch_create_params): set_params / set_params_dev may replace them
   mh_world_params* d_params;        // the B records behind the statics record in d_scene's allocation (the per-world-parameters build only), or null
   mh_world_statics statics;         // the statics the batch was created with (n = 0 without): the topology set_params validates against
   bool has_report;                  // created for the contact report (mh_world_batch_create_report): mh_world_batch_step_report may pass rows
-  mh_world_report_kernel rkernel;   // the report build's objects (build == WB_LARGE_RP: launched instead of kernel / fkernel, which are then null)
-  mh_world_report_forced_kernel rfkernel;
 };
 
 namespace {
-// the one launch behind every stepping entry: the plain kernel, or the forced one when the batch stores forces or the caller passes a wrench
+// the one launch behind every stepping entry: the row's plain object, or the forced one when the batch stores forces or the caller passes a wrench
+// (stamped: mh_world_batch_profile's object instead, the row's plain kernel with the profiler's stamps)
 int launch_step(mh_world_batch* wb, hipStream_t stream, int grid, double dt, int nsteps, double* traj_dev, unsigned long long* prof, const int* ids_dev,
-                const double* wrench_dev, int rows, double* report_dev = nullptr)
+                const double* wrench_dev, int rows, double* report_dev = nullptr, const mh_world_variant* stamped = nullptr)
 {
-  if (wb->build == WB_LARGE_RP) {                                   // the report build: the same arguments, then the report rows (or null)
-    if (wb->has_forces || wrench_dev)
-      hipLaunchKernelGGL(wb->rfkernel, dim3(grid), dim3(64), 0, stream,
-                         (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev,
-                         (const mh_world_forces*)(wb->has_forces ? wb->d_forces : nullptr), wrench_dev, rows, report_dev);
-    else
-      hipLaunchKernelGGL(wb->rkernel, dim3(grid), dim3(64), 0, stream,
-                         (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev, report_dev);
-  }
-  else if (wb->has_forces || wrench_dev)
-    hipLaunchKernelGGL(wb->fkernel, dim3(grid), dim3(64), 0, stream,
-                       (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev,
-                       (const mh_world_forces*)(wb->has_forces ? wb->d_forces : nullptr), wrench_dev, rows);
-  else
-    hipLaunchKernelGGL(wb->kernel, dim3(grid), dim3(64), 0, stream,
-                       (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, traj_dev, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, prof, ids_dev);
-  MH_HIP(hipGetLastError());
+  mh_world_launch a;
+  a.stream = stream; a.grid = grid;
+  a.scene = wb->d_scene; a.B = wb->B; a.dt = dt; a.nsteps = nsteps; a.state = wb->d_state; a.aux = wb->d_aux; a.traj = traj_dev; a.nmax = wb->nmax;
+  a.lu_ws = wb->d_lu_ws; a.ka = mh_g_debug_ka; a.prof = prof; a.ids = ids_dev;
+  a.forces = wb->has_forces ? wb->d_forces : nullptr; a.wrench = wrench_dev; a.wrench_rows = rows;
+  a.report = report_dev;
+  const world_build& r = g_builds[wb->build];
+  const hipError_t e = (stamped ? stamped : (wb->has_forces || wrench_dev) ? r.forced() : r.plain())->launch(a);
+  if (e != hipSuccess) return fail(MH_ERR_HIP, "hipGetLastError() failed: %s", hipGetErrorString(e));
   return MH_OK;
 }
 }  // namespace
@@ -259,10 +242,7 @@ int mh_world_batch_occupancy(mh_world_batch* wb)
   if (!wb) return fail(MH_ERR_INVALID_ARG, "null batch");
   MH_ON_DEVICE(wb);
   int n = 0;
-  hipError_t e = wb->build == WB_LARGE_RP ? (wb->has_forces ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->rfkernel, 64, 0)
-                                                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->rkernel, 64, 0))
-                 : wb->has_forces ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->fkernel, 64, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wb->kernel, 64, 0);
+  const hipError_t e = (wb->has_forces ? g_builds[wb->build].forced() : g_builds[wb->build].plain())->occupancy(&n);
   if (e != hipSuccess) return fail(MH_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
   return n;
 }
@@ -338,9 +318,7 @@ int create_batch(const mh_scene* scene, const mh_world_statics* statics, const m
     // the contact report needs the report build, whatever the scene; every other batch launches what it launched (key 18: the per-world-parameters
     // batches through it, with a null report)
     if (report || (wb->build == WB_LARGE_PW && mh_g_debug_world_rp != 0)) wb->build = WB_LARGE_RP;
-    wb->has_report = report; wb->kernel = nullptr; wb->fkernel = nullptr; wb->rkernel = nullptr; wb->rfkernel = nullptr;
-    if (wb->build == WB_LARGE_RP) { wb->rkernel = g_report_build.plain()->kernel; wb->rfkernel = g_report_build.forced()->kernel; }
-    else { wb->kernel = g_builds[wb->build].plain()->kernel; wb->fkernel = g_builds[wb->build].forced()->kernel; }
+    wb->has_report = report;
     wb->has_forces = false; wb->d_forces = nullptr;
     wb->has_params = params != nullptr; wb->d_params = nullptr;
   }
@@ -525,13 +503,11 @@ int mh_world_batch_profile(mh_world_batch* wb, double dt, int nsteps, double* ph
   MH_HIP(hipMalloc(&dprof, sz));
   MH_HIP(hipMemset(dprof, 0, sz));
   // the PROFILE object of the batch's build: the production kernel has no stamp code (mh_lcp_wave.h lp_tick)
-  const bool stamped = wb->build < WB_COUNT && g_builds[wb->build].prof != nullptr;
   // (a batch with stored forces: the forced production kernel -- it steps the worlds under their forces and has no stamps, so every cycle count is 0)
   // (a batch on the box-sphere, the statics, the per-world-parameters or the report build: likewise, there is no stamped object of it -- the production kernel steps the worlds, every cycle count is 0)
-  if (wb->has_forces || !stamped) { const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1); if (rc != MH_OK) { (void)hipFree(dprof); return rc; } }
-  else
-  hipLaunchKernelGGL(g_builds[wb->build].prof()->kernel, dim3(wb->B), dim3(64), 0, (hipStream_t)nullptr,
-                     (const mh_scene*)wb->d_scene, wb->B, dt, nsteps, wb->d_state, wb->d_aux, (double*)nullptr, wb->nmax, wb->d_lu_ws, mh_g_debug_ka, dprof, (const int*)nullptr);
+  const mh_world_variant* stamped = (wb->has_forces || !g_builds[wb->build].prof) ? nullptr : g_builds[wb->build].prof();
+  const int rc = launch_step(wb, (hipStream_t)nullptr, wb->B, dt, nsteps, nullptr, dprof, nullptr, nullptr, 1, nullptr, stamped);
+  if (rc != MH_OK) { (void)hipFree(dprof); return rc; }
   hipError_t e = hipDeviceSynchronize();
   std::vector<unsigned long long> h((size_t)wb->B * PHC);
   if (e == hipSuccess) e = hipMemcpy(h.data(), dprof, sz, hipMemcpyDeviceToHost);

@@ -3,18 +3,9 @@
 #include <hip/hip_runtime.h>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#ifdef MH_PROFILE_BUILD      /* mh_world_large_prof.hip: the same kernel with the s_memtime stamps compiled in (mh_world_batch_profile) */
-#define MHW_NS large_prof
-#define MHW_VARIANT_GETTER mh_world_variant_large_prof
-#elif defined(MH_FORCES_BUILD) /* mh_world_large_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
-#define MHW_NS large_forces
-#define MHW_VARIANT_GETTER mh_world_variant_large_forces
-#define MHW_VARIANT_T mh_world_forced_variant
-#define MHW_FORCES 1
-#else
-#define MHW_NS large
-#define MHW_VARIANT_GETTER mh_world_variant_large
-#endif
+// mh_world_large_prof.hip (MH_PROFILE_BUILD) is the same kernel with the s_memtime stamps compiled in (mh_world_batch_profile), mh_world_large_forces.hip
+// (MH_FORCES_BUILD) the one with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES): mh_world_wave.inc derives their names.
+#define MHW_BASE large
 #define MHW_NOSLIP 1
 #define MHW_BOX 1
 #define MHW_NB MH_MAX_BODIES

@@ -6,16 +6,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#if defined(MH_FORCES_BUILD)   /* mh_world_large_rp_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
-#define MHW_NS large_rp_forces
-#define MHW_VARIANT_GETTER mh_world_variant_large_rp_forces
-#define MHW_VARIANT_T mh_world_report_forced_variant
-#define MHW_FORCES 1
-#else
-#define MHW_NS large_rp
-#define MHW_VARIANT_GETTER mh_world_variant_large_rp
-#define MHW_VARIANT_T mh_world_report_variant
-#endif
+#define MHW_BASE large_rp      /* mh_world_large_rp_forces.hip (MH_FORCES_BUILD): the same kernel with recurrent forces and the caller's wrench in its forward dynamics */
 #define MHW_REPORT 1
 #define MHW_PARAMS 1
 #define MHW_STATICS 1

@@ -5,15 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/moby_hip.h"
 #include "mh_host.h"
-#if defined(MH_FORCES_BUILD)   /* mh_world_large_st_forces.hip: the same kernel with recurrent forces and the caller's wrench in its forward dynamics (MHW_FORCES) */
-#define MHW_NS large_st_forces
-#define MHW_VARIANT_GETTER mh_world_variant_large_st_forces
-#define MHW_VARIANT_T mh_world_forced_variant
-#define MHW_FORCES 1
-#else
-#define MHW_NS large_st
-#define MHW_VARIANT_GETTER mh_world_variant_large_st
-#endif
+#define MHW_BASE large_st      /* mh_world_large_st_forces.hip (MH_FORCES_BUILD): the same kernel with recurrent forces and the caller's wrench in its forward dynamics */
 #define MHW_STATICS 1
 #define MHW_BSP 1
 #define MHW_NOSLIP 1

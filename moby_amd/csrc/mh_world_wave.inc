@@ -36,12 +36,12 @@
 //   * HBM is touched only to load the state once and to store it (and the optional trajectory), plus the LU
 //     workspace of the rare factorisations that do not fit LDS: all `nsteps` steps run inside one launch.
 //
-// This file is compiled once per variant: the includer defines MHW_NS (namespace), MHW_NB, MHW_MAX_PAIRS,
-// MHW_MAX_CONTACTS, MHW_MAX_ROWS, MHW_MAX_GROWS, MHW_WAVES_PER_SIMD, MHW_VARIANT_GETTER (the host-side getter at the end of this file) and the feature
-// switches MHW_NOSLIP (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).  Three more switches are 1 in the units named and undefined = 0
+// This file is compiled once per variant: the includer defines MHW_BASE (its base name: the namespace mh::MHW_NS and the host-side getter at the end of this
+// file, mh_world_variant_<MHW_NS>, are derived from it below), MHW_NB, MHW_MAX_PAIRS, MHW_MAX_CONTACTS, MHW_MAX_ROWS, MHW_MAX_GROWS, MHW_WAVES_PER_SIMD and the
+// feature switches MHW_NOSLIP (no-slip model + spokes geometry) and MHW_BOX (box-plane contacts).  More switches are 1 in the units named and undefined = 0
 // elsewhere:
-//   MHW_FORCES  (mh_world_*_forces.hip) adds the scene's recurrent forces and the caller's wrench to the forward dynamics; every line it adds sits under
-//               #if MHW_FORCES.
+//   MHW_FORCES  (mh_world_*_forces.hip, which define MH_FORCES_BUILD: set below) adds the scene's recurrent forces and the caller's wrench to the forward
+//               dynamics; every line it adds sits under #if MHW_FORCES.
 //   MHW_BSP     (mh_world_large_bsp*.hip, mh_world_large_st*.hip; needs MHW_BOX) adds box-sphere contacts between two free bodies (include/moby_hip.h,
 //               "box-sphere pairs").
 //   MHW_STATICS (mh_world_large_st*.hip; needs MHW_BSP) adds several static bodies -- planes and boxes, each with a frame of its own -- beside the free
@@ -65,6 +65,19 @@
 // A feature that changes this file keeps the INSTRUCTIONS of the builds it does not concern, not their text: tools/world_asm_diff.py compares every world
 // code object of two source trees function by function (DESIGN.md 4.1).
 #include "mh_world_common.h"
+
+// the build's names from its base name: <base>_prof (MH_PROFILE_BUILD: the stamped object), <base>_forces (MH_FORCES_BUILD) or <base>
+#define MHW_CAT_(a, b) a##b
+#define MHW_CAT(a, b) MHW_CAT_(a, b)
+#if defined(MH_PROFILE_BUILD)
+#define MHW_NS MHW_CAT(MHW_BASE, _prof)
+#elif defined(MH_FORCES_BUILD)
+#define MHW_NS MHW_CAT(MHW_BASE, _forces)
+#define MHW_FORCES 1
+#else
+#define MHW_NS MHW_BASE
+#endif
+#define MHW_VARIANT_GETTER MHW_CAT(mh_world_variant_, MHW_NS)
 
 #define MHW_NS_MAXC ((MHW_MAX_CONTACTS < 6) ? MHW_MAX_CONTACTS : 6)   /* contacts of a no-slip island */
 /* edge of the LDS-resident LU block: the largest square inside the 12 * MHW_MAX_ROWS doubles of D_J */
@@ -2127,11 +2140,29 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
 #undef box_plane_pair
 } } // namespace mh::MHW_NS
 
-// ---- what the host side (mh_world.hip) sees of this code object: its kernel, and the upload of the __constant__ tables, of which every code object has a
-// copy of its own.  MHW_VARIANT_GETTER names the getter (declared in mh_host.h); MHW_VARIANT_T is mh_world_forced_variant in the MHW_FORCES units. ----
-#ifndef MHW_VARIANT_T
-#define MHW_VARIANT_T mh_world_variant
+// ---- what the host side (mh_world.hip) sees of this code object (mh_world_variant, mh_host.h): the launch of its kernel, the occupancy query for it, and the
+// upload of the __constant__ tables, of which every code object has a copy of its own.  The kernel is named here only: the host holds no typed kernel pointer. ----
+// the trailing arguments stand under the switches of the kernel's own parameter list; a field this build has no parameter for is ignored
+#if MHW_FORCES
+#define MHW_FORCES_ARGS(a) , (a).forces, (a).wrench, (a).wrench_rows
+#else
+#define MHW_FORCES_ARGS(a)
 #endif
+#if MHW_REPORT
+#define MHW_REPORT_ARGS(a) , (a).report
+#else
+#define MHW_REPORT_ARGS(a)
+#endif
+static hipError_t launch(const mh_world_launch& a)
+{
+  hipLaunchKernelGGL(mh::MHW_NS::mh_k_world_step, dim3(a.grid), dim3(64), 0, a.stream,
+                     a.scene, a.B, a.dt, a.nsteps, a.state, a.aux, a.traj, a.nmax, a.lu_ws, a.ka, a.prof, a.ids MHW_FORCES_ARGS(a) MHW_REPORT_ARGS(a));
+  return hipGetLastError();
+}
+static hipError_t occupancy(int* blocks_per_cu)
+{
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mh::MHW_NS::mh_k_world_step, 64, 0);
+}
 static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void* pow10, size_t pow10_bytes)
 {
   if (fric_bytes != sizeof(mh::FricTable) || pow10_bytes != sizeof(mh::Pow10Table)) return hipErrorInvalidValue;
@@ -2140,8 +2171,8 @@ static hipError_t upload_tables(const void* fric, size_t fric_bytes, const void*
   return e;
 }
 
-const MHW_VARIANT_T* MHW_VARIANT_GETTER()
+const mh_world_variant* MHW_VARIANT_GETTER()
 {
-  static const MHW_VARIANT_T v = { mh::MHW_NS::mh_k_world_step, mh::MHW_NS::PH_COUNT, upload_tables };
+  static const mh_world_variant v = { launch, occupancy, mh::MHW_NS::PH_COUNT, upload_tables };
   return &v;
 }

@@ -54,84 +54,35 @@ class WorldBatch:
     def step(self, dt, nsteps=1, want_traj=False, wrench=None, want_report=False):
         """wrench: (B, nb, 6) or (rows >= nsteps, B, nb, 6) host array (fx fy fz tx ty tz per world and body), or None.
         want_report: returns (trajectory or None, report) with the contact report (B, nsteps, npt, 8) of include/moby_hip.h, "Contact report"."""
-        if want_report:
-            return self._step_report(dt, nsteps, want_traj, wrench)
-        if self.forces is not None or wrench is not None:
-            return self._step_forced(dt, nsteps, want_traj, wrench)
-        lib = _lib.load()
-        if self.params is not None:
-            return self._step_params(dt, nsteps, want_traj)
-        if self.statics is not None:
-            traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
-            _lib.check(lib.mh_world_step_batch_statics(ctypes.addressof(self.scene), None, self.B, float(dt), int(nsteps), self.state.ctypes.data,
-                                                       self.aux.ctypes.data, None if traj is None else traj.ctypes.data, ctypes.addressof(self.statics)))
-            return traj
+        if wrench is not None:
+            return self._step_wrench(dt, nsteps, want_traj, wrench, want_report)
+        # the host convenience with every optional argument: NULL for what the batch has not (a NULL report keeps it off the report build)
         traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
-        rc = lib.mh_world_step_batch(ctypes.addressof(self.scene), self.B, float(dt), int(nsteps),
-                                     self.state.ctypes.data, self.aux.ctypes.data,
-                                     None if traj is None else traj.ctypes.data)
-        _lib.check(rc)
-        return traj
-
-    def _step_params(self, dt, nsteps, want_traj):
-        """per-world records (and forces, if any): the host convenience mh_world_step_batch_params"""
-        traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
-        _lib.check(_lib.load().mh_world_step_batch_params(ctypes.addressof(self.scene), None if self.forces is None else ctypes.addressof(self.forces),
-                                                          None if self.statics is None else ctypes.addressof(self.statics), self.params.ctypes.data,
+        report = np.zeros((self.B, nsteps, report_npt(self.scene, self.statics), REPORT_PAIR)) if want_report else None
+        _lib.check(_lib.load().mh_world_step_batch_report(ctypes.addressof(self.scene), None if self.forces is None else ctypes.addressof(self.forces),
+                                                          None if self.statics is None else ctypes.addressof(self.statics),
+                                                          None if self.params is None else self.params.ctypes.data,
                                                           self.B, float(dt), int(nsteps), self.state.ctypes.data, self.aux.ctypes.data,
-                                                          None if traj is None else traj.ctypes.data))
-        return traj
+                                                          None if traj is None else traj.ctypes.data, None if report is None else report.ctypes.data))
+        return (traj, report) if want_report else traj
 
-    def _step_report(self, dt, nsteps, want_traj, wrench):
-        """the report build: the host convenience mh_world_step_batch_report, or with a wrench a device batch created for the report"""
-        traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
-        report = np.zeros((self.B, nsteps, report_npt(self.scene, self.statics), REPORT_PAIR))
-        if wrench is None:
-            _lib.check(_lib.load().mh_world_step_batch_report(ctypes.addressof(self.scene), None if self.forces is None else ctypes.addressof(self.forces),
-                                                              None if self.statics is None else ctypes.addressof(self.statics),
-                                                              None if self.params is None else self.params.ctypes.data,
-                                                              self.B, float(dt), int(nsteps), self.state.ctypes.data, self.aux.ctypes.data,
-                                                              None if traj is None else traj.ctypes.data, report.ctypes.data))
-            return traj, report
+    def _step_wrench(self, dt, nsteps, want_traj, wrench, want_report):
+        """a wrench is a DEVICE array: the same round trip through a device batch (created for the report if one is wanted)"""
         import torch
-        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics, params=self.params, report=True)
-        try:
-            if self.forces is not None:
-                dev.set_forces(self.forces)
-            tj = torch.zeros(traj.shape, dtype=torch.float64, device="cuda") if want_traj else None
-            rp = torch.zeros(report.shape, dtype=torch.float64, device="cuda")
-            w = torch.as_tensor(np.ascontiguousarray(wrench, dtype=np.float64), device="cuda")
-            dev.step(dt, nsteps, traj_ptr=None if tj is None else tj.data_ptr(), wrench=w, report=rp)
-            self.state[...], aux = dev.download()
-            self.aux[...] = aux
-        finally:
-            dev.close()
-        return (None if tj is None else tj.cpu().numpy()), rp.cpu().numpy()
-
-    def _step_forced(self, dt, nsteps, want_traj, wrench):
-        """forces alone: the host convenience mh_world_step_batch_forces; with a wrench: the same round trip through a device batch, which is what
-        takes one (a DEVICE array)"""
-        if wrench is None and self.params is not None:
-            return self._step_params(dt, nsteps, want_traj)
-        if wrench is None:
-            traj = np.zeros((self.B, nsteps, self.scene.nb, 7)) if want_traj else None
-            _lib.check(_lib.load().mh_world_step_batch_statics(ctypes.addressof(self.scene), ctypes.addressof(self.forces), self.B, float(dt), int(nsteps),
-                                                               self.state.ctypes.data, self.aux.ctypes.data, None if traj is None else traj.ctypes.data,
-                                                               None if self.statics is None else ctypes.addressof(self.statics)))
-            return traj
-        import torch
-        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics, params=self.params)
+        dev = WorldBatchDevice(self.scene, self.state, aux=self.aux, statics=self.statics, params=self.params, report=want_report)
         try:
             if self.forces is not None:
                 dev.set_forces(self.forces)
             traj = torch.zeros((self.B, nsteps, self.scene.nb, 7), dtype=torch.float64, device="cuda") if want_traj else None
-            w = None if wrench is None else torch.as_tensor(np.ascontiguousarray(wrench, dtype=np.float64), device="cuda")
-            dev.step(dt, nsteps, traj_ptr=None if traj is None else traj.data_ptr(), wrench=w)
+            report = torch.zeros((self.B, nsteps, dev.npt, REPORT_PAIR), dtype=torch.float64, device="cuda") if want_report else None
+            w = torch.as_tensor(np.ascontiguousarray(wrench, dtype=np.float64), device="cuda")
+            dev.step(dt, nsteps, traj_ptr=None if traj is None else traj.data_ptr(), wrench=w, report=report)
             self.state[...], aux = dev.download()
             self.aux[...] = aux
         finally:
             dev.close()
-        return None if traj is None else traj.cpu().numpy()
+        traj = None if traj is None else traj.cpu().numpy()
+        return (traj, report.cpu().numpy()) if want_report else traj
 
     def regress_rows(self):
         """(B, 1 + 7*nb): current_time followed by the Euler coordinates of every body."""
@@ -150,18 +101,10 @@ class WorldBatchDevice:
         self.B = state.shape[0]
         self.handle = ctypes.c_void_p()
         self.npt = report_npt(scene, statics)
-        if report:
-            p = None if params is None else S.params_array(params, self.B)
-            _lib.check(lib.mh_world_batch_create_report(ctypes.addressof(scene), None if statics is None else ctypes.addressof(statics),
-                                                        None if p is None else p.ctypes.data, self.B, ctypes.byref(self.handle)))
-        elif params is not None:
-            p = S.params_array(params, self.B)
-            _lib.check(lib.mh_world_batch_create_params(ctypes.addressof(scene), None if statics is None else ctypes.addressof(statics), p.ctypes.data, self.B,
-                                                        ctypes.byref(self.handle)))
-        elif statics is None:
-            _lib.check(lib.mh_world_batch_create(ctypes.addressof(scene), self.B, ctypes.byref(self.handle)))
-        else:
-            _lib.check(lib.mh_world_batch_create_statics(ctypes.addressof(scene), ctypes.addressof(statics), self.B, ctypes.byref(self.handle)))
+        p = None if params is None else S.params_array(params, self.B)
+        create = lib.mh_world_batch_create_report if report else lib.mh_world_batch_create_params      # (NULL for what the batch has not)
+        _lib.check(create(ctypes.addressof(scene), None if statics is None else ctypes.addressof(statics), None if p is None else p.ctypes.data, self.B,
+                          ctypes.byref(self.handle)))
         self.device = lib.mh_world_batch_device(self.handle)      # the HIP device the batch lives on: device tensors handed to it must be that device's
         st = np.ascontiguousarray(state, dtype=np.float64)
         aux = S.new_aux(self.B, seed) if aux is None else np.ascontiguousarray(aux)      # aux given: resume from a checkpoint
@@ -222,33 +165,26 @@ class WorldBatchDevice:
             raise ValueError("report: shape %s, expected %s" % (tuple(report.shape), want))
         return ctypes.c_void_p(report.data_ptr())
 
-    def _step_report(self, dt, nsteps, stream, traj_ptr, ids_ptr, count, wrench, rows, report):
+    def _launch(self, dt, nsteps, stream, traj_ptr, ids_ptr, count, wrench, rows, report):
+        """the stepping entry with every optional argument (mh_world_batch_step_report): NULL for what the launch has not"""
         wptr, rows = (None, 1) if wrench is None else self._wrench_args(wrench, rows)
         _lib.check(_lib.load().mh_world_batch_step_report(self.handle, stream, float(dt), int(nsteps), traj_ptr, ids_ptr, int(count), wptr, rows,
-                                                          self._report_ptr(report, nsteps)))
+                                                          None if report is None else self._report_ptr(report, nsteps)))
 
     def step(self, dt, nsteps=1, stream=None, traj_ptr=None, wrench=None, rows=None, report=None):
         """wrench: per-world body wrenches for this launch (see _wrench_args; rows == 1 holds for the launch, rows >= nsteps is one row per step).
         report: the contact report of this launch (see _report_ptr; a batch created with report=True)."""
-        if report is not None:
-            return self._step_report(dt, nsteps, stream, traj_ptr, None, 0, wrench, rows, report)
-        if wrench is None:
-            _lib.check(_lib.load().mh_world_batch_step(self.handle, stream, float(dt), int(nsteps), traj_ptr))
-            return
-        ptr, rows = self._wrench_args(wrench, rows)
-        _lib.check(_lib.load().mh_world_batch_step_wrench(self.handle, stream, float(dt), int(nsteps), traj_ptr, None, 0, ptr, rows))
+        self._launch(dt, nsteps, stream, traj_ptr, None, 0, wrench, rows, report)
 
     def step_ids(self, dt, nsteps, ids_dev_ptr, count, stream=None, wrench=None, rows=None, report=None):
         """nsteps of the worlds listed in a DEVICE int32 array (e.g. a torch tensor's data_ptr()) on `stream` (mh_world_batch_step_ids); with a
         wrench, each listed world reads the schedule at its own index in the batch; with a report (the whole batch's shape), only the listed worlds'
         rows are written, each at its own index in the batch."""
-        if report is not None:
-            return self._step_report(dt, nsteps, stream, None, ctypes.c_void_p(int(ids_dev_ptr)), count, wrench, rows, report)
-        if wrench is None:
-            _lib.check(_lib.load().mh_world_batch_step_ids(self.handle, stream, float(dt), int(nsteps), ctypes.c_void_p(int(ids_dev_ptr)), int(count)))
+        ids_ptr = ctypes.c_void_p(int(ids_dev_ptr))
+        if wrench is None and report is None:      # (its own entry: it refuses a null id list, and words its count / step refusals its own way)
+            _lib.check(_lib.load().mh_world_batch_step_ids(self.handle, stream, float(dt), int(nsteps), ids_ptr, int(count)))
             return
-        ptr, rows = self._wrench_args(wrench, rows)
-        _lib.check(_lib.load().mh_world_batch_step_wrench(self.handle, stream, float(dt), int(nsteps), None, ctypes.c_void_p(int(ids_dev_ptr)), int(count), ptr, rows))
+        self._launch(dt, nsteps, stream, None, ids_ptr, count, wrench, rows, report)
 
     def occupancy(self):
         """resident workgroups per CU of the kernel this batch launches now (runtime query; the forced kernel once forces are stored)"""

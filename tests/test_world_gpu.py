@@ -75,6 +75,21 @@ def test_split_launches_equal_one_launch(oracle):
     np.testing.assert_array_equal(a.aux, b.aux)
 
 
+def test_world_batch_step_equals_the_plain_library_entry():
+    """WorldBatch.step goes through the entry with every optional argument; mh_world_step_batch is that entry with NULLs: the same bytes."""
+    import ctypes
+    from moby_amd import _lib
+    sc = S.sphere_stack_scene()
+    st0 = S.sphere_stack_state(3)
+    st, aux, traj = st0.copy(), S.new_aux(3), np.zeros((3, 20, sc.nb, 7))
+    _lib.check(_lib.load().mh_world_step_batch(ctypes.addressof(sc), 3, 1e-3, 20, st.ctypes.data, aux.ctypes.data, traj.ctypes.data))
+    wb = WorldBatch(sc, st0.copy())
+    traj_w = wb.step(1e-3, 20, want_traj=True)
+    for direct, wrapped in ((st, wb.state), (aux, wb.aux), (traj, traj_w)):
+        np.testing.assert_array_equal(np.frombuffer(direct.tobytes(), dtype=np.uint8), np.frombuffer(wrapped.tobytes(), dtype=np.uint8))
+    assert np.any(st != st0) and int(aux["steps"].min()) == 20
+
+
 def test_bouncing_ball_bit_exact(oracle):
     sc = S.bouncing_ball_scene()
     st0 = S.bouncing_ball_state(2)
