@@ -36,8 +36,13 @@ __shared__ int g_lcp_prof_on;
 // switch was the run-time flag alone and every stamp point of the production kernels paid a ds_read + s_waitcnt lgkmcnt(0) + branch for it -- a full LDS
 // round trip on the dependent chain of a latency-bound kernel, about a hundred times per world-step.
 #ifdef MH_PROFILE_BUILD
+// *p += v by lane 0 as ONE LDS add that returns nothing (a relaxed wavefront-scope fetch-add whose result is dropped: ds_add_u64), where `*p += v` is a
+// read, a wait for it, an add and a write: the cycle accumulators, which only the end of the launch reads
+MH_DEV void lds_add(unsigned long long* p, unsigned long long v) {
+  if (lane_id() == 0) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
 MH_DEV unsigned long long lp_tick() { return g_lcp_prof_on ? __builtin_amdgcn_s_memtime() : 0ull; }
-MH_DEV void lp_tock(int ph, unsigned long long t0) { if (g_lcp_prof_on) { const unsigned long long d = __builtin_amdgcn_s_memtime() - t0; if (lane_id() == 0) g_lcp_prof[ph] += d; } }
+MH_DEV void lp_tock(int ph, unsigned long long t0) { if (g_lcp_prof_on) { const unsigned long long d = __builtin_amdgcn_s_memtime() - t0; lds_add(&g_lcp_prof[ph], d); } }
 #else
 MH_DEV unsigned long long lp_tick() { return 0ull; }
 MH_DEV void lp_tock(int, unsigned long long) {}

@@ -30,6 +30,10 @@
 //     rand() ring, the scene constants and every scalar of the stepper -- lives in one LDS image (9.2 KB for
 //     the small variant => 16 worlds per CU); nothing persistent is held in registers, the 42x42 LCP matrix
 //     is never materialised (WorldMat), the LU block aliases the dead Jacobian rows;
+//   * what one phase hands to the NEXT one of the same call chain is a value, not a word of the image: the pair count (broad_phase -> do_mini_step ->
+//     find_unilateral_constraints), the contact count (-> handle_impacts, report_fold, the island search), the island search's masks and each island's
+//     body and contact sets (islands_begin -> next_island -> the handlers: IslandSearch, Island), the matrix norm (compute_problem_data -> the LCP
+//     chain) and the polygon offsets (poly_index -> WorldMat).  The words of the image that are still mailboxes are listed at the I_* enum below;
 //   * routines with several call sites are single out-of-line device functions over that image, single-site
 //     ones and the LCP chain are inlined: fully inlined the kernel is 31 K instructions and instruction-fetch
 //     bound, fully out-of-line it drowns in callee-saved register traffic;
@@ -161,7 +165,12 @@ enum {
   I_NB = I_PEN + MHW_MAX_PAIRS, I_NTOT, I_NPT, I_NMAX, I_KA, I_NPAIRS, I_NC, I_STATUS,
   I_ZLAST_SIZE, I_ZBUF_SIZE, I_ZBUF_CAP, I_NODEMASK, I_DONEMASK, I_DONEMASK_HI, I_CSTAB_MAXIT,
   I_NSPOKES, I_VNS_SIZE, I_NSM, I_NSNS,
-  I_GEOM,                                    // geometry type per body
+  // Of the scalars above, the ones a phase hands to the next travel as values (return values, arguments, uniform registers), not through their word here:
+  // the contact count and the island search's masks are never stored (I_NC, I_NODEMASK, I_DONEMASK, I_DONEMASK_HI keep their slots so that the image is
+  // laid out as it was); I_NPAIRS is stored once per mini-step for the stabiliser (eval_unilateral, update_q), which reads it at the end of the step;
+  // I_KOFF is filled for the polygon columns of islands of more than 7 contacts only (WorldMat::at_row).  What stays a mailbox: I_STATUS (read at the
+  // launch's end and by world_step's entry test), the sizes of _z/_zlast/_v, and I_NSM / I_NSNS between noslip_setup and noslip_finish.
+  I_GEOM,                                   // geometry type per body
   I_NSS = I_GEOM + MHW_NB,                   // no-slip S / T index sets
   I_NST = I_NSS + (MHW_NOSLIP ? MHW_NS_MAXC : 0),
   I_END = I_NST + (MHW_NOSLIP ? MHW_NS_MAXC : 0)
@@ -213,13 +222,15 @@ MH_DEV int geti(int i) { return uni(gi[i]); }
 MH_DEV void seti(int i, int v) { if (lane_id() == 0) gi[i] = v; }
 #ifdef MH_PROFILE_BUILD      /* (see lp_tick in mh_lcp_wave.h: the stamps exist in the profile translation units only) */
 MH_DEV unsigned long long tick() { return g_lcp_prof_on ? __builtin_amdgcn_s_memtime() : 0ull; }
-MH_DEV void tock(int ph, unsigned long long t0) { if (g_lcp_prof_on) { const unsigned long long d = __builtin_amdgcn_s_memtime() - t0; if (lane_id() == 0) g_pacc[ph] += d; } }
+MH_DEV void tock(int ph, unsigned long long t0) { if (g_lcp_prof_on) { const unsigned long long d = __builtin_amdgcn_s_memtime() - t0; lds_add(&g_pacc[ph], d); } }
 #else
 MH_DEV unsigned long long tick() { return 0ull; }
 MH_DEV void tock(int, unsigned long long) {}
 #endif
+// the counters of the aux record
+MH_DEV void count(int c, unsigned long long v) { if (lane_id() == 0) g_cnt[c] += v; }
 MH_DEV void account(int n, unsigned piv) {
-  if (lane_id() == 0) { g_cnt[CN_LCP]++; g_cnt[CN_ROWS] += (unsigned long long)n; g_cnt[CN_PIV] += piv; g_cnt[CN_BYTES] += 8ull * ((unsigned long long)n * n + 2ull * n); }
+  count(CN_LCP, 1ull); count(CN_ROWS, (unsigned long long)n); count(CN_PIV, piv); count(CN_BYTES, 8ull * ((unsigned long long)n * n + 2ull * n));
 }
 
 // ---- state helpers (any lane, any body) ---------------------------------------------------
@@ -946,37 +957,42 @@ MHW_FN int gen_contacts(int list_off, int count, int mode) {
 #endif
 
 // ---- islands (UC:940-1194): uniform scalar BFS; one island at a time ----------------------------------
-MH_DEV void islands_begin() {
+// The search's state is two wave-uniform masks that the caller holds between the calls: the enabled bodies not yet visited and the contacts already
+// handed out.
+struct IslandSearch { unsigned node_mask; uint64_t done; };
+struct Island { int nic, nib; unsigned bodies; uint64_t contacts; };   // counts, and the same two sets as bit masks (body b, contact lane c)
+MH_DEV IslandSearch islands_begin(int nc) {
+  nc = uni(nc);
   const int lane = lane_id();
-  const int nc = geti(I_NC), nb = geti(I_NB);
+  const int nb = geti(I_NB);
   const bool in = lane < nc;
   const int a = in ? gi[I_CG1 + lane] : -1, b = in ? gi[I_CG2 + lane] : -1;
   unsigned nodes = 0;
   for (int k = 0; k < nb; k++) if (ballot(in && (a == k || b == k)) != 0ull) nodes |= 1u << k;   // enabled bodies are 0..nb-1
-  wave_sync();
-  seti(I_NODEMASK, (int)nodes); seti(I_DONEMASK, 0); seti(I_DONEMASK_HI, 0);
-  wave_sync();
+  IslandSearch s; s.node_mask = nodes; s.done = 0ull;
+  return s;
 }
 // pops the next island into gi[I_ISLC..] (contacts, in the order the reference's BFS collects them)
-// and gi[I_ISLB..] (sorted unique bodies); returns nic | (nib << 8), or -1 when none is left.
+// and gi[I_ISLB..] (sorted unique bodies) and describes it in `isl`; returns false when none is left.
 // Contact lanes hold (g1, g2); the BFS itself runs on wave-uniform bit masks: a node's contacts and
 // neighbours are ballots, the FIFO is a string of nibbles.  (The reference pushes a neighbour again
 // while it waits in the queue; the second visit adds nothing, so visiting on push gives the same order.)
-MH_DEV int next_island() {
+MH_DEV bool next_island(int nc, IslandSearch& s, Island& isl) {
+  nc = uni(nc);
   const int lane = lane_id();
-  const int nc = geti(I_NC);
-  unsigned node_mask = (unsigned)geti(I_NODEMASK);
-  uint64_t done = (uint64_t)(unsigned)geti(I_DONEMASK) | ((uint64_t)(unsigned)geti(I_DONEMASK_HI) << 32);
+  unsigned node_mask = s.node_mask;
+  uint64_t done = s.done;
   const bool in = lane < nc;
   const int a = in ? gi[I_CG1 + lane] : -1, b = in ? gi[I_CG2 + lane] : -1;
   const uint64_t both = ballot(in && enabled(a) && enabled(b));
-  int result = -1;
+  bool found = false;
   wave_sync();
   while (node_mask) {
     const int start = __ffs((int)node_mask) - 1;
     unsigned visited = 1u << start, bodies = 0;
     uint64_t queue = (uint64_t)start; int qlen = 1;
     int nic = 0;
+    uint64_t contacts = 0ull;
     while (qlen > 0) {
       const int nd = (int)(queue & 15ull); queue >>= 4; qlen--;
       node_mask &= ~(1u << nd);
@@ -992,23 +1008,26 @@ MH_DEV int next_island() {
       const uint64_t fresh = touch & ~done;
       if ((fresh >> lane) & 1ull) gi[I_ISLC + nic + popc(fresh & lanes_below(lane))] = lane;
       nic += popc(fresh);
-      done |= fresh;
+      done |= fresh; contacts |= fresh;
     }
     if (nic == 0) continue;
     if (lane < 32 && ((bodies >> lane) & 1u)) gi[I_ISLB + popc((uint64_t)(bodies & ((1u << lane) - 1u)))] = lane;
-    result = nic | (popc((uint64_t)bodies) << 8);
+    isl.nic = nic; isl.nib = popc((uint64_t)bodies); isl.bodies = bodies; isl.contacts = contacts;
+    found = true;
     break;
   }
   wave_sync();
-  seti(I_NODEMASK, (int)node_mask); seti(I_DONEMASK, (int)(unsigned)done); seti(I_DONEMASK_HI, (int)(unsigned)(done >> 32));
-  wave_sync();
-  return result;
+  s.node_mask = node_mask; s.done = done;
+  return found;
 }
 
 // ---- problem data (Jacobian-row lanes): rows r = d*nic + i, ndir = 3 (impact) or 1 (stabilisation) ----
-MH_DEV int gc_of(int body, int nib) { for (int k = 0; k < nib; k++) if (gi[I_ISLB + k] == body) return 6 * k; return -1; }
-MH_DEV void compute_problem_data(int nic, int nib, int ndir, int fresh_xinv) {
-  nic = uni(nic); nib = uni(nib); ndir = uni(ndir); fresh_xinv = uni(fresh_xinv);
+// offset of `body`'s generalised coordinates among the island's: gi[I_ISLB..] lists the bodies of the mask `bodies` in ascending order, so the position
+// of a body in that list is the number of the island's bodies below it
+MH_DEV int gc_of(int body, unsigned bodies) { return ((bodies >> body) & 1u) ? 6 * popc((uint64_t)(bodies & ((1u << body) - 1u))) : -1; }
+// Returns norm_inf of the QP model's LCP matrix (want_norm, which needs ndir == 3; 0.0 otherwise), uniform.
+MH_DEV double compute_problem_data(int nic, unsigned bodies, int ndir, int fresh_xinv, bool want_norm) {   // bodies: Island::bodies
+  nic = uni(nic); bodies = uni(bodies); ndir = uni(ndir); fresh_xinv = uni(fresh_xinv);
   const int lane = lane_id();
   const int R = ndir * nic;   // callers guarantee R <= MHW_MAX_ROWS (rows_fit)
   // the X blocks depend on the orientations only: the impact handler reuses the ones
@@ -1027,7 +1046,7 @@ MH_DEV void compute_problem_data(int nic, int nib, int ndir, int fresh_xinv) {
       const V3 dd = (k == 0) ? dir : -dir;
       const V3 r = pt - X(b);
       const V3 rxd = cross(r, dd);
-      gi[I_ROWOFF + 2*lane + k] = gc_of(b, nib);
+      gi[I_ROWOFF + 2*lane + k] = gc_of(b, bodies);
       Jr[0] = dd.x; Jr[1] = dd.y; Jr[2] = dd.z; Jr[3] = rxd.x; Jr[4] = rxd.y; Jr[5] = rxd.z;
       const double im = gd[D_XINV + 10*b]; const double* Ji = gd + D_XINV + 10*b + 1;
       XJr[0] = dd.x * im; XJr[1] = dd.y * im; XJr[2] = dd.z * im;
@@ -1045,10 +1064,15 @@ MH_DEV void compute_problem_data(int nic, int nib, int ndir, int fresh_xinv) {
   // G(r,c) = sum over the blocks of row r of dot6(J_r[blk], XJ_c[same body]) for the direction blocks a <= b;
   // the lower blocks are the transposes setup_QP reads (ICH-QP:392-401): entry (r,c) there is computed as
   // (c,r).  One ENTRY per lane (R^2 <= 144 entries over 64 lanes), not one row per lane.
+  // The QP model (want_norm) also takes norm_inf of the LCP matrix here, where every entry of G passes through a register: max |entry| over G (the
+  // compliance added on the normal diagonal first), the mu's and the polygon edges (cos 0 = sin pi/2 = 1), which is what WorldMat::norm_all() found by
+  // scanning G again (a > m ? a : m from 0.0: independent of the order, and a NaN is passed over as there).
+  double nmax = 0.0;
   {
     const unsigned mnic = small_div_magic(nic), mR = small_div_magic(R);
     for (int e = lane; e < R * R; e += 64) {
       int r = small_div_m(e, mR), c = e - r * R;
+      const bool ndiag = (r == c) && (r < nic);                     // entry e of G itself: the swap below keeps a diagonal entry where it is
       if (small_div_m(c, mnic) < small_div_m(r, mnic)) { const int t = r; r = c; c = t; }
       double res = 0.0;
 #pragma unroll
@@ -1066,9 +1090,20 @@ MH_DEV void compute_problem_data(int nic, int nib, int ndir, int fresh_xinv) {
         res = res + tmp;
       }
       gd[D_G + e] = res;
+      if (want_norm) {
+        double g = res;
+        if (ndiag) g = g + gd[D_CCOMP + gi[I_ISLC + r]];
+        const double a = fabs(g); nmax = (a > nmax) ? a : nmax;
+      }
     }
   }
+  if (want_norm) {
+    if (lane < nic) { const double a = fabs(gd[D_CMU + gi[I_ISLC + lane]]); nmax = (a > nmax) ? a : nmax; }
+    nmax = wave_max(nmax);
+    nmax = (nmax > 1.0) ? nmax : 1.0;
+  }
   wave_sync();
+  return nmax;
 }
 
 // ---- implicit LCP matrices ------------------------------------------------------------------------
@@ -1079,16 +1114,43 @@ MH_DEV void compute_problem_data(int nic, int nib, int ndir, int fresh_xinv) {
 // read transposed exactly as setup_QP does), mu_i, or -cos/-sin of a polygon edge.
 // mode 1: the stabilisation matrix Cn X Cn' (CStab:932-947), read straight from G.
 // Lane r caches the description of ITS row; the column is wave-uniform.
+//
+// The friction polygons of mode 0 (rows and columns from 6 nic on): contact i of the island owns the edges [koff_i, koff_i+1), koff being the running sum
+// of the contacts' edge counts gi[I_CNK] / 2.  poly_index() forms the sums once per solve, one contact per lane: `total` is koff_nic; `pack` holds koff_0
+// .. koff_7 in one byte each (a sum is at most MH_LCP_MAX_N_WAVE), which serves every island of up to POLY_PACK contacts from a uniform register -- a
+// larger island reads gi[I_KOFF..], filled for it alone; `ri` / `rbase` are the contact and its koff of the polygon row this lane stands for, if it does.
+struct PolyIndex { int total; uint64_t pack; int ri, rbase; };
+enum { POLY_PACK = 7 };
+MH_DEV int poly_koff(uint64_t pack, int i) { return (int)((pack >> (8 * i)) & 0xffull); }
+MH_DEV PolyIndex poly_index(int nic) {
+  const int lane = lane_id();
+  const int cnk = (lane < nic) ? gi[I_CNK + gi[I_ISLC + lane]] / 2 : 0;
+  const int rr = lane - 6 * nic;
+  PolyIndex x; x.pack = 0ull; x.ri = 0; x.rbase = 0;
+  int off = 0, total = 0;
+  for (int k = 0; k < nic; k++) {
+    const int ck = read_lane(cnk, k);
+    if (lane > k) off += ck;
+    total += ck;                                            // koff_k+1
+    if (k < POLY_PACK) x.pack |= (uint64_t)(unsigned)total << (8 * (k + 1));
+    if (k + 1 < nic && rr >= total) { x.ri = k + 1; x.rbase = total; }   // (the sums do not decrease: the last one at or below rr is the row's)
+  }
+  if (nic > POLY_PACK && lane <= nic) gi[I_KOFF + lane] = off;
+  x.total = total;
+  return x;
+}
 struct WorldMat {
   int mode, nic, R, nvars, n, doff; unsigned mnic;
+  uint64_t kpack;                                          // PolyIndex::pack (uniform)
   // this lane's row: kind 0 = a row of G (variable rows and the Cn v+ >= 0 rows, which repeat block-row 0),
   // 2 = friction polygon row, 3 = none.  grow = offset of the row in G, gcol = its column index in G
   // (the transposed reads of -N'), rneg = the row belongs to a -s / -t block.
   int rkind, ra, ri, grow, gcol, rneg, rvar;
   double rmu, rcos, rsin, rcomp;
+  double nrm;                                              // mode 0: norm_inf(M), from compute_problem_data (uniform)
   MH_DEV static int dir_of(int a) { return (a == 0) ? 0 : ((a == 1 || a == 3) ? 1 : 2); }
-  MH_DEV void init(int mode_, int nic_, int n_) {
-    mode = mode_; nic = nic_; n = n_;
+  MH_DEV void init(int mode_, int nic_, int n_, double nrm_, const PolyIndex& px) {
+    mode = mode_; nic = nic_; n = n_; nrm = nrm_; kpack = uni(px.pack);
     doff = (mode == 2) ? (int)D_NSMM : (int)D_G;          // mode 2: the no-slip model's dense Schur complement
     R = (mode == 0) ? 3 * nic_ : nic_; nvars = 5 * nic_; mnic = 0u;
     const int r = lane_id();
@@ -1100,8 +1162,8 @@ struct WorldMat {
     else if (r < n) {
       rkind = 2;
       const int rr = r - nvars - nic;
-      int i = 0; while (rr >= gi[I_KOFF + i + 1]) i++;
-      ri = i; const int rj = rr - gi[I_KOFF + i];
+      const int i = px.ri;
+      ri = i; const int rj = rr - px.rbase;
       const int ci = gi[I_ISLC + i]; const int kh = gi[I_CNK + ci] / 2;
       rmu = gd[D_CMU + ci]; rcos = c_fric.c[kh][rj]; rsin = c_fric.s[kh][rj];
     }
@@ -1133,9 +1195,11 @@ struct WorldMat {
       if (ra == 0 && ri == cc) g = g + rcomp;
       return -g;
     }
-    int i = 0; const int rr = cc - nic; while (rr >= gi[I_KOFF + i + 1]) i++;
+    int i = 0, k0; const int rr = cc - nic;
+    if (nic <= POLY_PACK) { while (rr >= poly_koff(kpack, i + 1)) i++; k0 = poly_koff(kpack, i); }
+    else { while (rr >= gi[I_KOFF + i + 1]) i++; k0 = gi[I_KOFF + i]; }
     if (i != ri) return -0.0;
-    const int jj = rr - gi[I_KOFF + i]; const int ci = gi[I_ISLC + i]; const int kh = gi[I_CNK + ci] / 2;
+    const int jj = rr - k0; const int ci = gi[I_ISLC + i]; const int kh = gi[I_CNK + ci] / 2;
     const double v = (ra == 0) ? gd[D_CMU + ci] : ((ra == 1 || ra == 3) ? -c_fric.c[kh][jj] : -c_fric.s[kh][jj]);
     return -v;
   }
@@ -1146,23 +1210,13 @@ struct WorldMat {
     if (ra == 0) g = g + rcomp;
     return g;
   }
-  // norm_inf(M) = max |entry|.  mode 0: H entries, mu, and the polygon edges (cos 0 = sin pi/2 = 1)
+  // norm_inf(M) = max |entry|.  mode 0: H entries, mu, and the polygon edges (cos 0 = sin pi/2 = 1): taken by compute_problem_data while it builds G
   MH_DEV double norm_all() const {
+    if (mode == 0) return nrm;
     const int lane = lane_id();
     double m = 0.0;
-    if (mode != 0) {
-      if (lane < n) for (int c = 0; c < n; c++) { const double a = fabs(gd[doff + lane * n + c]); m = (a > m) ? a : m; }
-      return wave_max(m);
-    }
-    for (int e = lane; e < R * R; e += 64) {
-      const int r = small_div(e, R), c = e - r * R;           // (the mirrored lower blocks repeat values of the upper ones)
-      double g = gd[D_G + e];
-      if (r == c && r < nic) g = g + gd[D_CCOMP + gi[I_ISLC + r]];
-      const double a = fabs(g); m = (a > m) ? a : m;
-    }
-    if (lane < nic) { const double a = fabs(gd[D_CMU + gi[I_ISLC + lane]]); m = (a > m) ? a : m; }
-    m = wave_max(m);
-    return (m > 1.0) ? m : 1.0;
+    if (lane < n) for (int c = 0; c < n; c++) { const double a = fabs(gd[doff + lane * n + c]); m = (a > m) ? a : m; }
+    return wave_max(m);
   }
   MH_DEV double offdiag_max() const {
     if (mode != 0) {
@@ -1171,8 +1225,8 @@ struct WorldMat {
       return wave_max(m);
     }
     // mode 0: the off-diagonal part contains every polygon edge, every mu, every off-diagonal
-    // H entry and the H DIAGONAL values again through the Cn v+ rows / -N' columns
-    return norm_all();
+    // H entry and the H DIAGONAL values again through the Cn v+ rows / -N' columns: norm_inf(M) itself
+    return nrm;
   }
 };
 
@@ -1184,12 +1238,13 @@ struct WorldMat {
 //   mode 2  ICH:1239,1281   the same chain on the no-slip model's dense matrix, warm-started from _v
 // The rand() ring is read from / written back to the image.
 struct ChainOut { int ok; double zi; int zsize; unsigned piv; };
-MH_DEV ChainOut world_lcp_chain(int mode, int nic, int n, double qi, double zi, int zsize)
+// nrm, px: mode 0's norm_inf(M) (compute_problem_data) and polygon index (poly_index); modes 1 and 2 scan their dense matrix and look at neither.
+MH_DEV ChainOut world_lcp_chain(int mode, int nic, int n, double qi, double zi, int zsize, double nrm, const PolyIndex& px)
 {
-  mode = uni(mode); nic = uni(nic); n = uni(n); zsize = uni(zsize);
+  mode = uni(mode); nic = uni(nic); n = uni(n); zsize = uni(zsize); nrm = uni(nrm);
   const int lane = lane_id();
   const unsigned long long ts = lp_tick();
-  WorldMat M; M.init(mode, nic, n);
+  WorldMat M; M.init(mode, nic, n, nrm, px);
   const double nrm0 = M.norm_all(), dii = M.diag();
   lp_tock(LP_SETUP, ts);
   WaveRand rng; rng.r = (lane < 31) ? (unsigned)gi[I_RNG + lane] : 0u; rng.idx = geti(I_RNG + 31);
@@ -1222,13 +1277,12 @@ MH_DEV ChainOut world_lcp_chain(int mode, int nic, int n, double qi, double zi, 
 
 // solve_qp_work's chain on the persistent _z/_zlast (ICH-QP:157-233); on success the solution is
 // left in gd[D_ZSOL..] and in zlast/zbuf.  Returns 1 on success, 0 when the island is beyond this variant (MH_WORLD_UNSUPPORTED), -1 when the handler threw.
-MH_DEV int solve_impact_lcp(int nic) {
+MH_DEV int solve_impact_lcp(int nic, double nrm) {               // nrm: norm_inf of _MM, as compute_problem_data returned it
   nic = uni(nic);
   const int lane = lane_id();
+  const PolyIndex px = poly_index(nic);
   wave_sync();
-  if (lane == 0) { int acc = 0; for (int i = 0; i < nic; i++) { gi[I_KOFF + i] = acc; acc += gi[I_CNK + gi[I_ISLC + i]] / 2; } gi[I_KOFF + nic] = acc; }
-  wave_sync();
-  const int nk_total = geti(I_KOFF + nic);
+  const int nk_total = px.total;
   const int nvars = 5 * nic, n = nvars + nic + nk_total;
   if (n > geti(I_NMAX) || n > MH_LCP_MAX_N_WAVE) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); return 0; }
   // _MM stays implicit (WorldMat mode 0); _qq per lane
@@ -1239,7 +1293,7 @@ MH_DEV int solve_impact_lcp(int nic) {
     if (r < nvars) { const int a = small_div(r, nic), i = r - a * nic; const double v = gd[D_CV + WorldMat::dir_of(a) * nic + i]; qi = (a >= 3) ? -v : v; }
     else if (r < nvars + nic) qi = gd[D_CV + r - nvars];
     else {
-      int i = 0; const int rr = r - nvars - nic; while (rr >= gi[I_KOFF + i + 1]) i++;
+      const int i = px.ri;
       const double cs = gd[D_CV + nic + i], ct = gd[D_CV + 2 * nic + i];
       const double vel = sqrt(cs * cs + ct * ct);
       qi = gd[D_CMUV + gi[I_ISLC + i]] * vel;
@@ -1253,7 +1307,7 @@ MH_DEV int solve_impact_lcp(int nic) {
   if (n > zbuf_cap) zi = 0.0; else zi = gd[D_ZBUF + lane];
   if (lane >= n) zi = 0.0;
   if (n == zlast_size) zi = (lane < n) ? gd[D_ZLAST + lane] : 0.0;
-  const ChainOut co = world_lcp_chain(0, nic, n, qi, zi, n);
+  const ChainOut co = world_lcp_chain(0, nic, n, qi, zi, n, nrm, px);
   zi = co.zi;
   const bool ok = uni(co.ok) != 0;
   account(n, uni(co.piv));
@@ -1340,16 +1394,16 @@ MH_DEV void impulses_from_z_and_apply(int nic, int nib) {
 MH_DEV double min_cnv(int nic) { const int lane = lane_id(); return wave_min((lane < nic) ? gd[D_CV + lane] : MHW_INF); }
 
 // apply_model_to_connected_constraints (ICH:530-626)
-MH_DEV bool apply_model(int nic, int nib) {                         // returns true when the handler threw (LCPSolverException)
-  nic = uni(nic); nib = uni(nib);
+MH_DEV bool apply_model(const Island& isl) {                        // returns true when the handler threw (LCPSolverException)
+  const int nic = uni(isl.nic), nib = uni(isl.nib);
   const int lane = lane_id();
   if (3 * nic > MHW_MAX_ROWS) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); return false; }
   unsigned long long t0 = tick();
-  compute_problem_data(nic, nib, 3, 0);
+  const double nrm = compute_problem_data(nic, isl.bodies, 3, 0, true);  // G, and with it the matrix's norm, is the same for both passes
   tock(PH_PDATA, t0);
   double minv = 0.0;
   for (int pass = 0; pass < 2; pass++) {
-    { const int rs = solve_impact_lcp(nic); if (rs <= 0) return rs < 0; }
+    { const int rs = solve_impact_lcp(nic, nrm); if (rs <= 0) return rs < 0; }
     t0 = tick();
     impulses_from_z_and_apply(nic, nib);                            // ICH:569 / :600
     if (pass == 1) { tock(PH_APPLY, t0); break; }
@@ -1488,12 +1542,12 @@ MHW_FN void noslip_finish(int nic) {
   wave_sync();
 }
 // apply_no_slip_model_to_connected_constraints (ICH:236-295)
-MH_DEV bool apply_no_slip_model_to_island(int nic, int nib) {       // returns true when the handler threw (the assert of ICH:1184-1186, std::runtime_error of ICH:1282)
-  nic = uni(nic); nib = uni(nib);
+MH_DEV bool apply_no_slip_model_to_island(const Island& isl) {      // returns true when the handler threw (the assert of ICH:1184-1186, std::runtime_error of ICH:1282)
+  const int nic = uni(isl.nic), nib = uni(isl.nib);
   const int lane = lane_id();
   if (3 * nic > MHW_MAX_ROWS || nic > MHW_NS_MAXC) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); return false; }
   unsigned long long t0 = tick();
-  compute_problem_data(nic, nib, 3, 0);
+  compute_problem_data(nic, isl.bodies, 3, 0, false);
   tock(PH_PDATA, t0);
   t0 = tick();
   if (!noslip_setup(nic)) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_LCP_FAILED); wave_sync(); return true; }   // assert(success), ICH:1184-1186
@@ -1504,7 +1558,7 @@ MH_DEV bool apply_no_slip_model_to_island(int nic, int nib) {       // returns t
   const double qi = (lane < n) ? gd[D_NSQ + lane] : 0.0;
   double zi = (lane < MH_NOSLIP_MAX) ? gd[D_VNS + lane] : 0.0;
   if (lane >= n) zi = 0.0;
-  const ChainOut co = world_lcp_chain(2, nic, n, qi, zi, zsize);   // lcp_fast(_MM, _qq, _v), then the Lemke ladder (ICH:1239, 1281)
+  const ChainOut co = world_lcp_chain(2, nic, n, qi, zi, zsize, 0.0, PolyIndex());   // lcp_fast(_MM, _qq, _v), then the Lemke ladder (ICH:1239, 1281)
   account(n, uni(co.piv));
   tock(PH_LCP, t0);
   if (!uni(co.ok)) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_LCP_FAILED); wave_sync(); return true; }
@@ -1544,31 +1598,33 @@ MH_DEV bool apply_no_slip_model_to_island(int nic, int nib) {       // returns t
 // current_time (TSS:215), the step does not stabilise, and a world that carries MH_WORLD_LCP_FAILED is not stepped again (oracle World::handle_impacts / step).
 // The throw travels up as a return value (a uniform register): only world_step's entry test reads the status word from LDS.
 MH_DEV bool thrown() { return (uni(geti(I_STATUS)) & MH_WORLD_LCP_FAILED) != 0; }
-MH_DEV bool handle_impacts() {                                      // returns true when the handler threw
+MH_DEV bool handle_impacts(int nc) {                                // nc: the contacts of the constraint list; returns true when the handler threw
+  nc = uni(nc);
   const int lane = lane_id();
-  const int nc = geti(I_NC);
   if (nc == 0) return false;
-  if (ballot(lane < nc && contact_vn(lane) < -MH_NEAR_ZERO) == 0ull) return false;
-  islands_begin();
+  const uint64_t impacting = ballot(lane < nc && contact_vn(lane) < -MH_NEAR_ZERO);
+  if (impacting == 0ull) return false;
+  IslandSearch search = islands_begin(nc);
   // islands share no enabled body, so applying the model island by island equals the
-  // reference's "filter inactive groups first, then apply" (UC:1197-1225, ICH:107-151)
+  // reference's "filter inactive groups first, then apply" (UC:1197-1225, ICH:107-151).  For the same reason the bodies of an island still have the
+  // velocities `impacting` was taken at when the island's turn comes: its contacts' normal velocities are those of that ballot, not computed again.
   uint64_t active_contacts = 0;
   while (true) {
     const unsigned long long ti = tick();
-    const int isl = next_island();
+    Island isl;
+    const bool more = next_island(nc, search, isl);
     tock(PH_ISLANDS, ti);
-    if (isl < 0) break;
-    const int nic = isl & 0xff, nib = isl >> 8;
-    const uint64_t act = ballot(lane < nic && contact_vn(gi[I_ISLC + (lane < nic ? lane : 0)]) < -MH_NEAR_ZERO);
-    if (act == 0ull) continue;                                      // remove_inactive_groups
+    if (!more) break;
+    const int nic = isl.nic;
+    if ((impacting & isl.contacts) == 0ull) continue;               // remove_inactive_groups
     const bool all_inf = ballot(lane < nic && gd[D_CMU + gi[I_ISLC + (lane < nic ? lane : 0)]] < 1e2) == 0ull;
-    for (int i = 0; i < nic; i++) active_contacts |= 1ull << geti(I_ISLC + i);
+    active_contacts |= isl.contacts;
 #if MHW_NOSLIP
-    if (all_inf) { if (apply_no_slip_model_to_island(nic, nib)) return true; continue; }    // ICH:134-135
+    if (all_inf) { if (apply_no_slip_model_to_island(isl)) return true; continue; }    // ICH:134-135
 #else
     if (all_inf) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); continue; }   // variant built without the no-slip model
 #endif
-    if (apply_model(nic, nib)) return true;
+    if (apply_model(isl)) return true;
   }
   if (ballot(lane < nc && ((active_contacts >> lane) & 1ull) && contact_vn(lane) < -MH_NEAR_ZERO) != 0ull) {
     seti(I_STATUS, geti(I_STATUS) | MH_WORLD_IMPACT_TOL); wave_sync();
@@ -1578,9 +1634,9 @@ MH_DEV bool handle_impacts() {                                      // returns t
 
 // ---- time stepping ----------------------------------------------------------------------------------
 // fills the constraint list from the sim pair list (CSim:488-537)
-MH_DEV void find_unilateral_constraints() {
+MH_DEV int find_unilateral_constraints(int npairs) {               // npairs: the length of the pair list; returns the number of contacts
+  npairs = uni(npairs);
   const int lane = lane_id();
-  const int npairs = geti(I_NPAIRS);
 #if MHW_REPORT
   for (int e = lane; e < 3 * MHW_MAX_CONTACTS; e += 64) g_racc[e] = 0.0;    // a new constraint list: no contact has received an impulse yet
 #endif
@@ -1613,8 +1669,8 @@ MH_DEV void find_unilateral_constraints() {
   { uint64_t sm = ballot(spk);                                      // spokes pairs come last in the pair list
     while (sm) { const int k = ctz(sm); sm &= sm - 1; nc = spoke_contacts(geti(I_PAIRS + k), nc); } }
 #endif
-  seti(I_NC, nc);
   wave_sync();
+  return nc;
 }
 #if MHW_NOSLIP
 // The conservative-advancement loop of do_mini_step for a world that is ONE spokes body over the plane
@@ -1699,7 +1755,7 @@ MH_DEV double wheel_ca_loop(double dt) {
   if (lane_id() == 0) {
 #pragma unroll
     for (int k = 0; k < 7; k++) gd[D_ST + k] = q[k];
-    gi[I_PAIRS] = 0; gi[I_NPAIRS] = 1;                               // the (wheel, ground) pair, as broad_phase leaves it
+    gi[I_PAIRS] = 0;                                                 // the (wheel, ground) pair, as broad_phase leaves it (do_mini_step: its length, 1)
   }
   wave_sync();
   return h;
@@ -1710,10 +1766,9 @@ MH_DEV double wheel_ca_loop(double dt) {
 // Folds the mini-step's contacts into the step's rows, where ConstraintSimulator::constraint_post_callback_fn sees them (CSim:353): after handle_impacts
 // returned without a throw, also when it returned early (the contacts then count with zero impulse).  Lane p owns pair slot p and walks the constraint
 // list in its order, so the order of a row's additions is fixed and no two lanes share a row.
-MH_DEV void report_fold() {
+MH_DEV void report_fold(int nc) {                                  // nc: the contacts of the constraint list
   const int lane = lane_id();
   double* rep = g_rep;
-  const int nc = geti(I_NC);
   wave_sync();
   if (!rep || lane >= gi[I_NPT]) return;
   int a, b; pair_bodies(lane, a, b);                                // a < b: the row holds the impulse on body a
@@ -1732,6 +1787,15 @@ MH_DEV void report_fold() {
 }
 #endif
 
+// a world that is ONE spokes body over the plane: wheel_ca_loop's case.  (Read from the image where it is needed: found once in the kernel entry and handed
+// down as a value, it made the wheel leg 1.2 % slower than this form, ranges apart -- DESIGN.md 4.1.)
+MH_DEV bool lone_wheel() {
+#if MHW_NOSLIP
+  return geti(I_NB) == 1 && geti(I_NTOT) == 2 && geti(I_GEOM) == MH_GEOM_SPOKES;
+#else
+  return false;
+#endif
+}
 MH_DEV double do_mini_step(double dt, bool& threw) {               // TSS:114-222; threw: the impact handler's exception left the mini-step before TSS:215
   const int lane = lane_id();
   wave_sync();
@@ -1739,17 +1803,17 @@ MH_DEV double do_mini_step(double dt, bool& threw) {               // TSS:114-22
   wave_sync();
   double h = 0.0;
   const double min_step = gd[D_MINSTEP];
+  // the length of the pair list travels as a value to the constraint list and the impact handler; gi[I_NPAIRS] is written once, below, for the
+  // stabiliser, which reads it after the step's last mini-step
+  int npairs = 0;
 #if MHW_NOSLIP
-  const bool lone_wheel = geti(I_NB) == 1 && geti(I_NTOT) == 2 && geti(I_GEOM) == MH_GEOM_SPOKES;
-  if (lone_wheel) { const unsigned long long tw = tick(); h = uni(wheel_ca_loop(dt)); tock(PH_BROAD_CA, tw); }
+  if (lone_wheel()) { const unsigned long long tw = tick(); h = uni(wheel_ca_loop(dt)); tock(PH_BROAD_CA, tw); npairs = 1; }   // (the loop leaves the one-pair list)
   else
 #endif
   for (unsigned guard = 0; h < dt; ) {
     if (++guard > MH_CA_HARD_CAP) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_STALLED); wave_sync(); break; }
     unsigned long long t0 = tick();
-    const int npairs = broad_phase(dt - h, I_PAIRS);
-    seti(I_NPAIRS, npairs);
-    wave_sync();
+    npairs = broad_phase(dt - h, I_PAIRS);
     const double e = (lane < npairs) ? ca_step(gi[I_PAIRS + lane]) : MHW_INF;   // TSS:272-331
     const double CA = wave_min(e);
     tock(PH_BROAD_CA, t0);
@@ -1761,18 +1825,20 @@ MH_DEV double do_mini_step(double dt, bool& threw) {               // TSS:114-22
     h += tc;
     tock(PH_INTEGRATE, t0);
   }
+  seti(I_NPAIRS, npairs);
   unsigned long long t1 = tick();
   integrate_velocities(h);
   tock(PH_FWDDYN, t1);
   t1 = tick();
-  find_unilateral_constraints();
+  const int nc = find_unilateral_constraints(npairs);
   tock(PH_CONTACTS, t1);
-  threw = handle_impacts();
+  threw = handle_impacts(nc);
   if (threw) return h;
 #if MHW_REPORT
-  report_fold();
+  report_fold(nc);
 #endif
-  if (lane == 0) { gd[D_TIME] = gd[D_TIME] + h; g_cnt[CN_MINI]++; }
+  if (lane == 0) gd[D_TIME] = gd[D_TIME] + h;
+  count(CN_MINI, 1ull);
   wave_sync();
   return h;
 }
@@ -1879,7 +1945,7 @@ MHW_FN void stabilize_work(double max_uvio) {
     PairGeom g; g.dist = 0.0; g.a = 0; g.b = 0; g.pa = v3(0, 0, 0); g.pb = v3(0, 0, 0);
 #if MHW_BOX
     int nc = gen_contacts(I_SCR, ncp, 1);
-    if (nc < 0) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); seti(I_NC, 0); wave_sync(); break; }
+    if (nc < 0) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); break; }
     if (lane < ncp) { p = gi[I_SCR + lane]; int a, b; pair_bodies(p, a, b); spk = is_spokes(a); if (spk) g = pair_geom(p); }
     (void)c;
 #else
@@ -1896,7 +1962,7 @@ MHW_FN void stabilize_work(double max_uvio) {
     const uint64_t m = ballot(c.has != 0);
     int nc = popc(m);
     wave_sync();
-    if (nc > MHW_MAX_CONTACTS) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); seti(I_NC, 0); wave_sync(); break; }
+    if (nc > MHW_MAX_CONTACTS) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); break; }
     if (c.has) store_contact(popc(m & lanes_below(lane)), p, c.g1, c.g2, c.pt, c.n, c.dist);
 #endif
 #if MHW_NOSLIP
@@ -1913,26 +1979,25 @@ MHW_FN void stabilize_work(double max_uvio) {
           nc++;
         } else nc = spoke_contacts(geti(I_SCR + k), nc);
       }
-      if (over) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); seti(I_NC, 0); wave_sync(); break; } }
+      if (over) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); break; } }
 #endif
-    seti(I_NC, nc);
     wave_sync();
-    islands_begin();
+    IslandSearch search = islands_begin(nc);
     while (true) {
-      const int isl = next_island();
-      if (isl < 0) break;
-      const int nic = isl & 0xff, nib = isl >> 8;
+      Island isl;
+      if (!next_island(nc, search, isl)) break;
+      const int nic = isl.nic, nib = isl.nib;
       const int n_ = nic;
       if (n_ > MHW_MAX_ROWS) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); continue; }
-      compute_problem_data(nic, nib, 1, 1);
+      compute_problem_data(nic, isl.bodies, 1, 1, false);
       if (n_ > geti(I_NMAX)) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_UNSUPPORTED); wave_sync(); continue; }
       // determine_dq (CStab:932-970): MM = Cn X Cn', qq = dist - |eps| - NEAR_ZERO; cold lcp_fast, then Lemke ladder
       double qi = 0.0;
       if (lane < n_) qi = gd[D_CDIST + gi[I_ISLC + lane]] - fabs(cstab_eps) - MH_NEAR_ZERO;
       wave_sync();
-      const ChainOut co = world_lcp_chain(1, nic, n_, qi, 0.0, 0);   // fresh local z: cold start
+      const ChainOut co = world_lcp_chain(1, nic, n_, qi, 0.0, 0, 0.0, PolyIndex());   // fresh local z: cold start
       const double zi = co.zi; const int zsize = uni(co.zsize);
-      account(n_, uni(co.piv)); if (lane_id() == 0) g_cnt[CN_SROWS] += (unsigned long long)n_;
+      account(n_, uni(co.piv)); count(CN_SROWS, (unsigned long long)n_);
       // update_from_stacked(pd, z): cn = z[0..nc) (zeros where z is shorter)
       wave_sync();
       if (lane < n_) gd[D_IMP + lane] = (lane < zsize) ? zi : 0.0;
@@ -1945,7 +2010,7 @@ MHW_FN void stabilize_work(double max_uvio) {
     if (!update_q()) { seti(I_STATUS, geti(I_STATUS) | MH_WORLD_STAB_FAILED); wave_sync(); break; }
     max_uvio = eval_unilateral().vmin;
     iterations++;
-    if (lane == 0) g_cnt[CN_STAB]++;
+    count(CN_STAB, 1ull);
   }
   wave_sync();
   if (lane < nb) for (int k = 0; k < 6; k++) gd[D_ST + 13*lane + 7 + k] = gd[D_VSAVE + 6*lane + k];
@@ -1960,8 +2025,14 @@ MH_DEV void stabilize() {                                          // CStab:167-
 }
 
 MH_DEV bool world_step(double dt) {                                // TSS:52-111; returns true when the impact handler threw (the world's run is over)
-  seti(I_NPAIRS, broad_phase(dt, I_PAIRS));
-  wave_sync();
+  // TSS:60 runs the broad phase at the step's start.  The first pass of do_mini_step's advancement loop runs it again with dt - 0.0 on the same state and
+  // overwrites the same list, so the call is made in two cases only:
+  //   * a step without a mini-step, !(0.0 < dt): stabilize() is the reader -- eval_unilateral measures the pairs of this list, gi[I_NPAIRS] of them;
+  //   * the lone wheel, whose wheel_ca_loop takes the place of the advancement loop and runs no broad phase.  NOTHING reads this list there either:
+  //     wheel_ca_loop leaves the same one-pair list when it ends (gi[I_PAIRS] = 0, length 1: the (wheel, ground) pair is appended unconditionally) and
+  //     broad_phase has no other effect.  The call stays so that the wheel's step makes the calls the parent's made, no more and no fewer; whoever
+  //     removes it has the wheel objects' timing to show for it, not a result to fear for.
+  if (lone_wheel() || !(0.0 < dt)) { seti(I_NPAIRS, broad_phase(dt, I_PAIRS)); wave_sync(); }
   double h = 0.0;
   unsigned guard = 0;
   while (h < dt) {
@@ -1973,7 +2044,7 @@ MH_DEV bool world_step(double dt) {                                // TSS:52-111
   const unsigned long long ts = tick();
   stabilize();
   tock(PH_STAB, ts);
-  if (lane_id() == 0) g_cnt[CN_STEPS]++;
+  count(CN_STEPS, 1ull);
   return false;
 }
 
@@ -2069,9 +2140,9 @@ void mh_k_world_step(const mh_scene* __restrict__ scp, int B, double dt, int nst
   mh_world_aux* a = aux + w;
   if (lane == 0) {
     gd[D_MINSTEP] = sc.min_step_size; gd[D_THRESH] = sc.contact_dist_thresh; gd[D_CSTABEPS] = sc.cstab_eps; gd[D_TIME] = a->time;
-    gi[I_NB] = nb; gi[I_NTOT] = ntot; gi[I_NPT] = npt; gi[I_NMAX] = nmax; gi[I_KA] = (ka < MHW_KA_V) ? ka : MHW_KA_V; gi[I_NPAIRS] = 0; gi[I_NC] = 0;
+    gi[I_NB] = nb; gi[I_NTOT] = ntot; gi[I_NPT] = npt; gi[I_NMAX] = nmax; gi[I_KA] = (ka < MHW_KA_V) ? ka : MHW_KA_V; gi[I_NPAIRS] = 0;
     gi[I_STATUS] = a->status; gi[I_ZLAST_SIZE] = a->zlast_size; gi[I_ZBUF_SIZE] = a->zbuf_size; gi[I_ZBUF_CAP] = a->zbuf_cap;
-    gi[I_NODEMASK] = 0; gi[I_DONEMASK] = 0; gi[I_DONEMASK_HI] = 0; gi[I_CSTAB_MAXIT] = (int)sc.cstab_max_iterations;
+    gi[I_CSTAB_MAXIT] = (int)sc.cstab_max_iterations;
     gi[I_NSPOKES] = 0; gi[I_VNS_SIZE] = a->vns_size; gi[I_NSM] = 0; gi[I_NSNS] = 0;
     for (int b = 0; b < nb; b++) if (sc.geom_type[b] == MH_GEOM_SPOKES) gi[I_NSPOKES] = (int)sc.geom_dim[b][1];
     g_lu_ws = lu_ws + (size_t)w * nmax * nmax;
