@@ -339,7 +339,7 @@ MH_DEV bool collinear(V3 a, V3 b, V3 c) {                           // CompGeom.
 #endif
 #if MHW_BSP
 // ---- box-sphere pairs of two free bodies (include/moby_hip.h).  The box is the reference's geometry A whichever body has the lower id; the frames are
-// the bodies' own (box centre = COM, box axes = rot(box)), a static box's its table row (box_frame).  Operation order = tests/native/world_boxsphere_ref.cpp (= artic_boxsphere_ref.cpp):
+// the bodies' own (box centre = COM, box axes = rot(box)), a static box's its table row (box_frame).  Operation order = tests/native/world_ref.cpp (= artic_boxsphere_ref.cpp):
 // three-term sums as (a + b) + c.  Each function forms the box rotation once. ----
 MH_DEV bool is_sphere(int b) { return b < gi[I_NB] && gi[I_GEOM + b] == MH_GEOM_SPHERE; }
 #if MHW_STATICS

@@ -1,14 +1,11 @@
 """The box reference's ctypes face (tests/native/artic_box_ref.cpp), shared by the CPU and the GPU tests of box primitives on links."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 
 from moby_amd import artic as A
+from tests import native_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class BoxRef:
@@ -33,10 +30,5 @@ class BoxRef:
         del keep
 
 
-def build_box_ref(tmpdir):
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = str(tmpdir / "libartic_box_ref.so")
-    nat = os.path.join(ROOT, "tests", "native")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle")]
-                          + [os.path.join(nat, f) for f in ("artic_box_ref.cpp", "artic_drive_ref.cpp", "artic_pose_ref.cpp")] + ["-o", so])
-    return BoxRef(so)
+def build_box_ref():
+    return BoxRef(native_build.build(("artic_box_ref.cpp", "artic_drive_ref.cpp", "artic_pose_ref.cpp"), "artic_box_ref"))

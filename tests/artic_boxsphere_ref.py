@@ -1,17 +1,13 @@
 """The box-sphere reference's ctypes face (tests/native/artic_boxsphere_ref.cpp) and the scenes shared by the CPU tests, the GPU tests, the fuzz
 tool and the bench of box-sphere contacts between links and static boxes."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 
 from moby_amd import artic as A
-
+from tests import native_build
 from tests.artic_pair_ref import G, UP, _hinge, slider
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FACE, EDGE, VERTEX, INSIDE = 0, 1, 2, 3
 
 
@@ -75,13 +71,9 @@ class BoxSphereRef:
         return reg, dist
 
 
-def build_boxsphere_ref(tmpdir):
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = str(tmpdir / "libartic_boxsphere_ref.so")
-    nat = os.path.join(ROOT, "tests", "native")
+def build_boxsphere_ref():
     srcs = ("artic_boxsphere_ref.cpp", "artic_pair_ref.cpp", "artic_box_ref.cpp", "artic_drive_ref.cpp", "artic_pose_ref.cpp")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle")] + [os.path.join(nat, f) for f in srcs] + ["-o", so])
-    return BoxSphereRef(so)
+    return BoxSphereRef(native_build.build(srcs, "artic_boxsphere_ref"))
 
 
 def track(ref, model, q, qd, dt, nsteps, pose=None):

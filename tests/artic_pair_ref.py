@@ -1,15 +1,12 @@
 """The pair reference's ctypes face (tests/native/artic_pair_ref.cpp), shared by the CPU and the GPU tests of sphere contacts between links."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 
 from moby_amd import artic as A
 from moby_amd import scene as S
+from tests import native_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class PairRef:
@@ -53,13 +50,8 @@ class PairRef:
         return out[:, :model.npairs]
 
 
-def build_pair_ref(tmpdir):
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = str(tmpdir / "libartic_pair_ref.so")
-    nat = os.path.join(ROOT, "tests", "native")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle")]
-                          + [os.path.join(nat, f) for f in ("artic_pair_ref.cpp", "artic_box_ref.cpp", "artic_drive_ref.cpp", "artic_pose_ref.cpp")] + ["-o", so])
-    return PairRef(so)
+def build_pair_ref():
+    return PairRef(native_build.build(("artic_pair_ref.cpp", "artic_box_ref.cpp", "artic_drive_ref.cpp", "artic_pose_ref.cpp"), "artic_pair_ref"))
 
 
 # ---- scenes shared by the CPU and the GPU tests (gravity along -y, the plane y = 0 unless stated) ----

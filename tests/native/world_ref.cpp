@@ -1,24 +1,40 @@
-// TEST INFRASTRUCTURE: the world step with several static bodies -- planes and boxes, each with a frame of its own -- beside the free ones, which the GPU
-// kernels are held to (include/moby_hip.h, "Static bodies").
+// TEST INFRASTRUCTURE: the one statement of the free-body world step beyond the oracle, which the GPU world kernels are held to bit for bit
+// (include/moby_hip.h: "Box-sphere pairs", "Static bodies", mh_world_forces / mh_world_batch_step_wrench, "Contact report").
 //
-// oracle::World (oracle/world.hpp) knows one static object, the scene's plane, and oracle/ is not edited for a feature; World is all-public and does not
-// care about the index of a body that is not enabled (islands, problem data, impulses and point velocities only ask enabled(b)), so this file restates
-// ONLY what several statics change:
-//   * the scene view: the pair arrays run triangularly over ntot = nb + has_ground + n bodies (an explicit pair list handed to World);
+// oracle::World (oracle/world.hpp) knows one static object (the scene's plane), gravity alone, and refuses an enabled box-sphere pair in its broad phase.
+// World is all-public and does not care about the index of a body that is not enabled (islands, problem data, impulses and point velocities only ask
+// enabled(b)), so this file restates ONLY what those features change, each function once:
+//   * the scene view: the pair arrays run triangularly over ntot = nb + has_ground + n bodies (an explicit pair list handed to World; with no statics
+//     that is the scene's own numbering);
 //   * the plane frame: to_plane / from_plane / plane_n take the plane's body index (the scene's ground is nb, static k is nb + has_ground + k), and with
 //     them the plane cases of signed_dist and find_contacts (PlanePrimitive.cpp:338-411, CCD.inl:804-886) and the box-plane rule of conservative
 //     advancement (CCD.cpp:238-468), whose polyhedron-plane tail is World's own;
-//   * the box of a box-sphere pair may be a static: its axes, centre and edge lengths come from the record instead of a body's quaternion and COM
-//     (find_contacts_box_sphere CCD.inl:1208-1259, BoxPrimitive::calc_signed_dist BoxPrimitive.cpp:256-276, 788-836); the sphere rule of
-//     conservative advancement gets calc_max_dist = 0 for it from World (CCD.cpp:585-609);
-//   * broad_phase: a static box's bounding sphere (centre, half diagonal) does not move (CCD.cpp:735-768), a plane's bound is infinite, pairs of two
-//     disabled bodies are dropped (CCD.cpp:864-866), a box body against a static box is box-box;
-//   * the callers that reach those through non-virtual calls, as tests/native/world_boxsphere_ref.cpp restates them (that file stays as it is; its
-//     box-sphere geometry, forcing, mini-step and stabiliser statements are repeated here over the functions above).
+//   * box-sphere pairs, the box a body (centre = COM, axes = World::rot) or a static (its record): signed_dist is BoxPrimitive::calc_signed_dist for a
+//     sphere (BoxPrimitive.cpp:256-276, 788-836; with the sphere as A, SpherePrimitive.cpp:282-290 forwards with the point arguments swapped: the points
+//     stay with their bodies); find_contacts is BoxPrimitive::calc_closest_points as its clamp fixed point + find_contacts_box_sphere
+//     (CCD.inl:1208-1259), created as (box, sphere); the sphere rule of conservative advancement (CCD.cpp:121-235) gets calc_max_dist = 0 for a static
+//     box from World (CCD.cpp:585-609).  The geometry is the text of tests/native/artic_boxsphere_ref.cpp (bsp_contact / bsp_sdist); three-term sums as
+//     (a + b) + c;
+//   * broad_phase: the refusal names box-box alone (a box body against a static box included), a box-sphere pair takes the swept-bounds test; a static
+//     box's bounding sphere (centre, half diagonal) does not move (CCD.cpp:735-768), a plane's bound is infinite, pairs of two disabled bodies are
+//     dropped (CCD.cpp:864-866);
+//   * forcing: World::fwd_dyn and the joint-free branch of fwd_dyn_and_integrate with the terms evaluated where the reference runs its recurrent forces
+//     and controllers -- once per mini-step, after the position update and before calc_fwd_dyn (precalc_fwd_dyn: TimeSteppingSimulator.cpp:173 ->
+//     Simulator.cpp:319-350; StokesDragForce.cpp:39-44, DampingForce.cpp:32-51).  Taken whenever the caller hands over forces (even with no terms) or a
+//     wrench; with neither the step runs the oracle's own fwd_dyn_and_integrate;
+//   * the callers that reach those through non-virtual calls: calc_pairwise_distances, CA_step / next_CA_step, do_mini_step, the stabiliser
+//     (eval_unilateral, eval_at, ridders, update_q, stabilize -- the joint-free statements: the scenes of the many-worlds stepper have no joints), step;
+//   * the contact report, which adds no physics: it is what ConstraintSimulator::constraint_post_callback_fn (ConstraintSimulator.cpp:353) would see --
+//     the mini-step's contact constraints with the contact_impulse that update_from_stacked accumulated (ImpactConstraintHandler.cpp:298-327) -- summed
+//     per pair.  The oracle carries that quantity: Contact::imp (oracle/world.hpp:65), zeroed when the contact is made, added to by
+//     World::apply_impulses; do_mini_step folds it behind handle_impacts when it is given a sink.
 // Everything else is the oracle's own: sphere pairs, spokes (scene ground only), islands, the impact handler, the LCP chain, the dynamics.
-// Pins (tests/test_world_statics.py): a scene with has_ground = 1 and no statics, and the same scene with has_ground = 0 and one static plane carrying
-// plane_R / plane_o, both equal oracle_world_step_batch bit for bit; the static-box geometry equals numpy written out by hand on dyadic inputs, and
-// artic_boxsphere_ref's static box on identical poses.
+// Pins: with forces of no terms, and with none at all, it equals oracle_world_step_batch bit for bit, and so it does with every coefficient zero
+// (tests/test_world_forces.py, on the stack, wheel, box and ball scenes); a lone body under Stokes drag and a wrench follows the recurrence written out
+// in numpy (same file); with no box-sphere pair enabled it equals the oracle (tests/test_world_boxsphere.py); a scene with has_ground = 1 and no
+// statics, and the same scene with has_ground = 0 and one static plane carrying plane_R / plane_o, both equal the oracle, and statics = NULL equals an
+// empty record (tests/test_world_statics.py); the box geometry equals numpy written out by hand on dyadic inputs, over a quaternion and over a matrix,
+// and artic_boxsphere_ref's static box on identical poses (both files); the report sink changes no step (tests/test_world_report.py).
 // Built by the tests with g++ and oracle/Makefile's CXXFLAGS (-ffp-contract=off: every operation rounds on its own).
 #include <cstring>
 #include "lcp.hpp"
@@ -314,13 +330,13 @@ double next_CA_step(const World& w)
   return t;
 }
 
-// the scene's recurrent forces and the caller's wrench (include/moby_hip.h: mh_world_forces, mh_world_batch_step_wrench), evaluated as
-// tests/native/world_force_ref.cpp does -- its fwd_dyn, restated: once per mini-step, terms in the order gravity, Stokes drag, damping, wrench
+// the scene's recurrent forces and the caller's wrench (include/moby_hip.h: mh_world_forces, mh_world_batch_step_wrench)
 struct Forcing {
   const mh_world_forces* F;    // stored terms, or NULL
   const double* wrench;        // rows x B x nb x 6, or NULL
   int rows, B, world, step;
 };
+// World::fwd_dyn with the terms in their canonical order: gravity, Stokes drag, damping, the caller's wrench; an absent term is left out
 void fwd_dyn(const World& w, const Forcing& fo, int b, V3& xdd, V3& wd)
 {
   const SceneView* sc = w.sc;
@@ -362,7 +378,43 @@ void fwd_dyn(const World& w, const Forcing& fo, int b, V3& xdd, V3& wd)
 // under the threshold test whose contact query found nothing
 struct Census { int* counts; };
 
-double do_mini_step(World& w, double dt, Census* cen, const Forcing* fo)
+// what a step's contacts were like, for the conditions the tests assert on their inputs (per world and step, 6 ints):
+//   [0] mini-steps folded with at least one contact; [1] most contacts of one pair in one mini-step; [2] most pairs with cn > 0 in one mini-step;
+//   [3] contacts with epsilon > 0 whose restitution pass added a second impulse; [4] contacts counted with zero impulse; [5] contacts with sign = -1
+enum { SH_MINI = 0, SH_PAIR_CONTACTS, SH_PAIRS_LOADED, SH_RESTITUTION, SH_ZERO, SH_NEG_SIGN, SH_COUNT };
+
+// the report of one mini-step, summed into rows: npt x MH_REPORT_PAIR of this step; the contacts in constraint-list order
+void fold(const World& w, const std::vector<Contact>& cs, double* rows, int* shape)
+{
+  const int npt = w.sc->npairs;
+  std::vector<int> per_pair(npt, 0); std::vector<double> cn_pair(npt, 0.0);
+  for (const Contact& c : cs) {
+    int i, j; w.pair_bodies(c.pair, i, j);                           // i < j
+    const double cn = c.imp[0], cs_ = c.imp[1], ct = c.imp[2];
+    const double sign = (c.g1 == i) ? 1.0 : -1.0;
+    const V3 jv = (c.n * cn + c.s * cs_) + c.t * ct;
+    double* r = rows + (size_t)MH_REPORT_PAIR * c.pair;
+    r[0] += 1.0;
+    r[1] += cn;
+    r[2] += sign * jv.x; r[3] += sign * jv.y; r[4] += sign * jv.z;
+    r[5] += c.p.x * cn; r[6] += c.p.y * cn; r[7] += c.p.z * cn;
+    if (!shape) continue;
+    per_pair[c.pair]++; cn_pair[c.pair] += cn;
+    // the restitution pass (ICH:470-491, 581) adds eps * cn to every contact of an island once one of them has eps * cn > NEAR_ZERO.  Without it
+    // imp[0] = cn and eps * cn <= NEAR_ZERO, so imp[0] eps / (1 + eps) > NEAR_ZERO can only be seen after a second impulse
+    if (c.eps > 0.0 && cn * c.eps / (1.0 + c.eps) > NEAR_ZERO) shape[SH_RESTITUTION]++;
+    if (cn == 0.0 && cs_ == 0.0 && ct == 0.0) shape[SH_ZERO]++;
+    if (sign < 0.0) shape[SH_NEG_SIGN]++;
+  }
+  if (!shape) return;
+  if (!cs.empty()) shape[SH_MINI]++;
+  int loaded = 0;
+  for (int p = 0; p < npt; p++) { if (per_pair[p] > shape[SH_PAIR_CONTACTS]) shape[SH_PAIR_CONTACTS] = per_pair[p]; if (cn_pair[p] > 0.0) loaded++; }
+  if (loaded > shape[SH_PAIRS_LOADED]) shape[SH_PAIRS_LOADED] = loaded;
+}
+
+// World::do_mini_step over the functions above.  fo: NULL = the oracle's own forward dynamics; rows: this step's report rows, or NULL (shape with them)
+double do_mini_step(World& w, double dt, Census* cen, const Forcing* fo, double* rows, int* shape)
 {
   const SceneView* sc = w.sc;
   const int nb = sc->nb;
@@ -405,7 +457,8 @@ double do_mini_step(World& w, double dt, Census* cen, const Forcing* fo)
     }
   }
   w.handle_impacts(cs);
-  if (w.thrown_) return h;
+  if (w.thrown_) return h;                                           // (the exception leaves before CSim:353: nothing is folded)
+  if (rows) fold(w, cs, rows, shape);                                // constraint_post_callback_fn (CSim:353)
   w.aux->time += h;
   w.aux->mini_steps++;
   return h;
@@ -550,15 +603,15 @@ void stabilize(World& w)
   for (int b = 0; b < nb; b++) for (int k = 0; k < 6; k++) st[13*b + 7 + k] = vsave[b][k];
 }
 
-void step(World& w, double dt, Census* cen, const Forcing* fo)
+void step(World& w, double dt, Census* cen, const Forcing* fo, double* rows, int* shape)
 {
-  if (w.aux->status & MH_WORLD_LCP_FAILED) return;
+  if (w.aux->status & MH_WORLD_LCP_FAILED) return;                   // passed over: the rows stay zero
   broad_phase(w, dt, w.pairs_to_check);
   calc_pairwise_distances(w, w.pairs_to_check, w.pairwise);
   double h = 0.0;
   unsigned guard = 0;
   while (h < dt) {
-    h += do_mini_step(w, dt - h, cen, fo);
+    h += do_mini_step(w, dt - h, cen, fo, rows, shape);
     if (w.thrown_) return;
     if (++guard > 100000u) { w.aux->status |= MH_WORLD_STALLED; break; }
   }
@@ -586,20 +639,26 @@ const mh_world_statics g_none = {};
 extern "C" {
 
 // B worlds x nsteps steps, in place.  statics: NULL = none.  traj: B x nsteps x nb x 7 or NULL; census: B x nsteps x 5 ints (face, edge, vertex,
-// penetrating, none) or NULL; forces: NULL or terms == 0 = none; wrench: HOST array rows x B x nb x 6 or NULL
-void world_statics_ref_step(const mh_scene* sc, const mh_world_statics* statics, int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj,
-                            int* census, const mh_world_forces* forces, const double* wrench, int rows)
+// penetrating, none) or NULL; forces, wrench (HOST array rows x B x nb x 6): both NULL = the oracle's own forward dynamics, otherwise the restated one
+// (forces with terms == 0 included); report: B x nsteps x npt x MH_REPORT_PAIR (written whole: zero rows first) or NULL; shape: B x nsteps x 6 ints
+// (zeroed here; filled only beside a report) or NULL
+void world_ref_step(const mh_scene* sc, const mh_world_statics* statics, int B, double dt, int nsteps, double* state, mh_world_aux* aux, double* traj,
+                    int* census, const mh_world_forces* forces, const double* wrench, int rows, double* report, int* shape)
 {
   g_st = statics ? statics : &g_none; g_hg = sc->has_ground ? 1 : 0;
   const View view(sc, g_st);
-  const bool forced = (forces && forces->terms) || wrench;
+  const int npt = view.v.npairs;
+  const bool forced = forces || wrench;
+  if (report) for (size_t i = 0; i < (size_t)B * nsteps * npt * MH_REPORT_PAIR; i++) report[i] = 0.0;
+  if (shape) for (size_t i = 0; i < (size_t)B * nsteps * SH_COUNT; i++) shape[i] = 0;
   for (int b = 0; b < B; b++) {
     double* st = state + (size_t)b * sc->nb * MH_BODY_STATE;
     World w(view.v, st, aux + b, aux[b].zlast, aux[b].zbuf, MH_LCP_MAX_N_WAVE);
     for (int s = 0; s < nsteps; s++) {
       Census cen = { census ? census + ((size_t)b * nsteps + s) * 5 : nullptr };
       const Forcing fo = { forces, wrench, rows, B, b, s };
-      step(w, dt, census ? &cen : nullptr, forced ? &fo : nullptr);
+      step(w, dt, census ? &cen : nullptr, forced ? &fo : nullptr, report ? report + ((size_t)b * nsteps + s) * npt * MH_REPORT_PAIR : nullptr,
+           shape ? shape + ((size_t)b * nsteps + s) * SH_COUNT : nullptr);
       if (traj) for (int k = 0; k < sc->nb; k++) for (int i = 0; i < 7; i++) traj[(((size_t)b * nsteps + s) * sc->nb + k) * 7 + i] = st[13*k + i];
     }
   }
@@ -607,22 +666,42 @@ void world_statics_ref_step(const mh_scene* sc, const mh_world_statics* statics,
 
 // probe: the contact of a box (centre cb, axes R row-major, edge lengths len) and a sphere (centre cS, radius Rs) within TOL.
 // out[0] = has, out[1] = dist (set either way), out[2..4] = point, out[5..7] = normal, out[8] = region (0 face, 1 edge, 2 vertex, 3 centre inside)
-void world_statics_ref_box_contact(const double* cb, const double* R, const double* len, const double* cS, double Rs, double TOL, double* out)
+void world_ref_box_contact(const double* cb, const double* R, const double* len, const double* cS, double Rs, double TOL, double* out)
 {
   const BspContact c = bsp_contact(R, v3(cb[0], cb[1], cb[2]), len, v3(cS[0], cS[1], cS[2]), Rs, TOL);
   out[0] = c.has; out[1] = c.dist; out[2] = c.p.x; out[3] = c.p.y; out[4] = c.p.z; out[5] = c.n.x; out[6] = c.n.y; out[7] = c.n.z; out[8] = c.region;
 }
 // probe: the signed distance with both points.  out[0] = dist, out[1..3] = the box point, out[4..6] = the sphere point
-void world_statics_ref_box_dist(const double* cb, const double* R, const double* len, const double* cS, double Rs, double* out)
+void world_ref_box_dist(const double* cb, const double* R, const double* len, const double* cS, double Rs, double* out)
 {
   V3 pA, pB;
   out[0] = bsp_sdist(R, v3(cb[0], cb[1], cb[2]), len, v3(cS[0], cS[1], cS[2]), Rs, pA, pB);
   out[1] = pA.x; out[2] = pA.y; out[3] = pA.z; out[4] = pB.x; out[5] = pB.y; out[6] = pB.z;
 }
+// the axes of a free box body with quaternion xyzw q, as the stepper forms them: World::rot
+static void body_axes(const double* cb, const double* q, double R[9])
+{
+  mh_scene sc; std::memset(&sc, 0, sizeof(sc)); sc.nb = 1;
+  double st[13] = { cb[0], cb[1], cb[2], q[0], q[1], q[2], q[3], 0, 0, 0, 0, 0, 0 };
+  mh_world_aux aux; std::memset(&aux, 0, sizeof(aux));
+  World w(&sc, st, &aux);
+  w.rot(0, R);
+}
+// the two probes above over a box body's pose (centre cb, quaternion xyzw q)
+void world_ref_contact(const double* cb, const double* q, const double* len, const double* cS, double Rs, double TOL, double* out)
+{
+  double R[9]; body_axes(cb, q, R);
+  world_ref_box_contact(cb, R, len, cS, Rs, TOL, out);
+}
+void world_ref_dist(const double* cb, const double* q, const double* len, const double* cS, double Rs, double* out)
+{
+  double R[9]; body_axes(cb, q, R);
+  world_ref_box_dist(cb, R, len, cS, Rs, out);
+}
 // probe: pair p of a scene with statics in a given state, as the stepper reads it.  out[0] = dist, out[1..3] = pa (body a = the lower index),
 // out[4..6] = pb, out[7] = a, out[8] = b; contacts (TOL): out[9] = their number, then of the first out[10] = g1, out[11] = g2, out[12] = dist,
 // out[13..15] = point, out[16..18] = normal; out[19] = 1 if the broad phase (dt = 0) keeps the pair
-void world_statics_ref_pair(const mh_scene* sc, const mh_world_statics* statics, const double* state, int p, double TOL, double* out)
+void world_ref_pair(const mh_scene* sc, const mh_world_statics* statics, const double* state, int p, double TOL, double* out)
 {
   g_st = statics ? statics : &g_none; g_hg = sc->has_ground ? 1 : 0;
   const View view(sc, g_st);

@@ -20,8 +20,8 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.fixture(scope="module")
-def box_ref(tmp_path_factory):
-    return build_box_ref(tmp_path_factory.mktemp("box_ref"))
+def box_ref():
+    return build_box_ref()
 
 
 def Ry(a):

@@ -18,8 +18,8 @@ SCENES = os.path.join(ROOT, "tests", "scenes")
 
 
 @pytest.fixture(scope="module")
-def box_ref(tmp_path_factory):
-    return build_box_ref(tmp_path_factory.mktemp("box_ref_gpu"))
+def box_ref():
+    return build_box_ref()
 
 
 def same(got, ref, B):

@@ -17,8 +17,8 @@ SCENES = os.path.join(ROOT, "tests", "scenes")
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return BS.build_boxsphere_ref(tmp_path_factory.mktemp("boxsphere_ref"))
+def ref():
+    return BS.build_boxsphere_ref()
 
 
 # ---- readers ----

@@ -21,8 +21,8 @@ B = 64
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return BS.build_boxsphere_ref(tmp_path_factory.mktemp("boxsphere_ref_gpu"))
+def ref():
+    return BS.build_boxsphere_ref()
 
 
 SCENES = {  # name -> (steps per launch, has a floating base)

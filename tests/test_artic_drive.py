@@ -4,7 +4,6 @@ oracle_artic_step, driven it is the oracle's own forward dynamics composed with 
 where the servo balances gravity, and the ctypes mirror of the new struct."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 from moby_amd import artic as A
 from moby_amd import scene as S
+from tests import native_build
 from tests.test_artic_gpu import ur10_states
 from tests.test_oracle_artic_contacts import tip_model
 
@@ -45,12 +45,8 @@ class DriveRef:
 
 
 @pytest.fixture(scope="session")
-def drive_ref(tmp_path_factory):
-    """the driven reference, built with g++ and oracle/Makefile's CXXFLAGS (the oracle's floating-point contract: no FMA)"""
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = str(tmp_path_factory.mktemp("drive_ref") / "libartic_drive_ref.so")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "artic_drive_ref.cpp"), "-o", so])
-    return DriveRef(so)
+def drive_ref():
+    return DriveRef(native_build.build(("artic_drive_ref.cpp",), "artic_drive_ref"))
 
 
 def random_drive(rng, B, nj, rows=1, terms=A.MH_DRIVE_PD | A.MH_DRIVE_FORCE, kp=(0.0, 40.0), kv=(0.0, 4.0), qspan=0.5, tau=5.0):

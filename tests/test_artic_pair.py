@@ -19,13 +19,13 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.fixture(scope="module")
-def pair_ref(tmp_path_factory):
-    return P.build_pair_ref(tmp_path_factory.mktemp("pair_ref"))
+def pair_ref():
+    return P.build_pair_ref()
 
 
 @pytest.fixture(scope="module")
-def box_ref(tmp_path_factory):
-    return build_box_ref(tmp_path_factory.mktemp("pair_box_ref"))
+def box_ref():
+    return build_box_ref()
 
 
 def assert_same(a, b):

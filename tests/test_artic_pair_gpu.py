@@ -16,8 +16,8 @@ B = 64
 
 
 @pytest.fixture(scope="module")
-def pair_ref(tmp_path_factory):
-    return P.build_pair_ref(tmp_path_factory.mktemp("pair_ref_gpu"))
+def pair_ref():
+    return P.build_pair_ref()
 
 
 SCENES = {  # name -> (builder, steps per launch, has a floating base)

@@ -4,7 +4,6 @@ the fold changes coordinates only, a free ball turned through a quarter turn of 
 body keeps |Q| = 1 and its angular momentum -- and the ctypes mirrors of the new entry points."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ from moby_amd import _lib
 from moby_amd import artic as A
 from moby_amd import io as mio
 from moby_amd import scene as S
+from tests import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = os.path.join(ROOT, "tests", "scenes")
@@ -60,14 +60,9 @@ class PoseRef:
 
 
 @pytest.fixture(scope="session")
-def pose_ref(tmp_path_factory):
-    """the pose-coordinate reference and the driven one it steps with, one library, g++ with oracle/Makefile's CXXFLAGS"""
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = str(tmp_path_factory.mktemp("pose_ref") / "libartic_pose_ref.so")
-    nat = os.path.join(ROOT, "tests", "native")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(nat, "artic_pose_ref.cpp"),
-                                             os.path.join(nat, "artic_drive_ref.cpp"), "-o", so])
-    return PoseRef(so)
+def pose_ref():
+    """the pose-coordinate reference and the driven one it steps with, one library"""
+    return PoseRef(native_build.build(("artic_pose_ref.cpp", "artic_drive_ref.cpp"), "artic_pose_ref"))
 
 
 def quat_of_R(R):

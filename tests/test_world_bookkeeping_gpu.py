@@ -10,7 +10,7 @@ from moby_amd import _lib
 from moby_amd import scene as S
 from moby_amd.world import WorldBatchDevice
 from tests.world_bookkeeping_ref import cases, reference_run
-from tests.world_force_ref import assert_aux_equal, reference as force_reference
+from tests.world_ref import assert_aux_equal, reference as force_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -109,11 +109,11 @@ def test_impact_lcp_whose_attempt_zero_fails():
 
 
 def test_forces_object_with_a_stored_drag_term():
-    """the _forces object: the stack batch under Stokes drag against the forced reference (tests/native/world_force_ref.cpp)"""
+    """the _forces object: the stack batch under Stokes drag against the forced reference (tests/native/world_ref.cpp)"""
     c = cases()["stack"]
     forces = S.make_forces(3, stokes=(0.3, 0.05))
     st_r, aux_r = c["state"].copy(), S.new_aux(c["state"].shape[0])
-    force_reference().step(c["scene"], st_r, aux_r, c["dt"], c["nsteps"], forces, None)
+    force_reference().step(c["scene"], st_r, aux_r, c["dt"], c["nsteps"], forces=forces)
     assert ((aux_r["status"] & ~S.MH_WORLD_IMPACT_TOL) == 0).all() and (aux_r["lcp_solves"] > 0).all()
     st, aux = run_device(c, forces=forces)
     np.testing.assert_array_equal(st, st_r)

@@ -1,8 +1,8 @@
 """Box-sphere contacts between free bodies (include/moby_hip.h, "Box-sphere pairs") without a GPU: the reference the kernels are held to
-(tests/native/world_boxsphere_ref.cpp, a restatement of what the pair changes in oracle::World) pinned to the oracle -- with no box-sphere pair
+(tests/native/world_ref.cpp, a restatement of what the pair changes in oracle::World) pinned to the oracle -- with no box-sphere pair
 enabled it IS oracle_world_step_batch -- and to the geometry written out by hand in numpy on dyadic inputs; both id orders of the pair; what a
-contact must do physically (a head-on hit, a ball resting on a crate); the scene file and the scene check.  The reference's ctypes face and the
-batches shared with the GPU tests live in tests/world_boxsphere_ref.py."""
+contact must do physically (a head-on hit, a ball resting on a crate); the scene file and the scene check.  The reference's ctypes face lives in
+tests/world_ref.py, the batches shared with the GPU tests in tests/world_boxsphere_ref.py."""
 import ctypes
 
 import numpy as np
@@ -10,8 +10,8 @@ import pytest
 
 from moby_amd import io as mio
 from moby_amd import scene as S
-from tests.world_force_ref import assert_aux_equal
-from tests.world_boxsphere_ref import BOX_DIMS, RADIUS, SCENE_XML, disabled_mixed_batch, mixed_scene, reference
+from tests.world_ref import assert_aux_equal, reference
+from tests.world_boxsphere_ref import BOX_DIMS, RADIUS, SCENE_XML, disabled_mixed_batch, mixed_scene
 
 
 
@@ -123,13 +123,13 @@ def test_contact_and_signed_distance_are_different_functions(ref):
     assert ref.contact(P[0], P[1], DIMS, c, 0.5, 0.0)["dist"] == 0.0 and ref.dist(P[0], P[1], DIMS, c, 0.5)[0] == -0.25
 
 
-def test_geometry_equals_the_articulated_reference_on_bit_identical_poses(ref, tmp_path_factory):
+def test_geometry_equals_the_articulated_reference_on_bit_identical_poses(ref):
     """tests/native/artic_boxsphere_ref.cpp with a static axis-aligned box at the origin and the sphere on three sliders with zero offsets (q = its
     centre): the same contact (found, point, normal, distance, region) and the same signed distance, bit for bit, on every case of the tables"""
     from moby_amd import artic as A
     from tests import artic_boxsphere_ref as BS
     from tests import artic_pair_ref as APR
-    aref = BS.build_boxsphere_ref(tmp_path_factory.mktemp("artic_boxsphere_ref"))
+    aref = BS.build_boxsphere_ref()
     cb, quat, _ = POSES[0]
 
     def model(radius):
@@ -185,7 +185,7 @@ def test_head_on_hit_conserves_momentum_and_restitutes(ref):
     st[0, 1, 0] = 0.5 * BOX_DIMS[0] + RADIUS + 2.5e-3; st[0, 1, 7] = -1.0
     p0 = mb * st[0, 0, 7:10] + ms * st[0, 1, 7:10]
     st = st.reshape(1, -1); aux = S.new_aux(1)
-    _, census = ref.step(sc, st, aux, 1e-3, 10, want_census=True)
+    census = ref.step(sc, st, aux, 1e-3, 10, want_census=True).census
     assert aux["status"][0] == 0 and aux["lcp_solves"][0] > 0 and census[0, :, 0].sum() > 0
     v = st.reshape(2, 13)[:, 7:10]; w = st.reshape(2, 13)[:, 10:13]
     print("momentum error", mb * v[0] + ms * v[1] - p0, "separating speed", v[1, 0] - v[0, 0])
@@ -199,7 +199,7 @@ def test_ball_rests_on_a_crate_on_the_plane(ref):
     contact_dist_thresh + cstab_eps of their start"""
     sc = S.ball_on_crate_scene(epsilon=0.0)
     st = S.ball_on_crate_state(1, gap=0.0, speed=0.0); aux = S.new_aux(1)
-    traj, census = ref.step(sc, st, aux, 1e-3, 200, want_traj=True, want_census=True)
+    traj, census = ref.step(sc, st, aux, 1e-3, 200, want_traj=True, want_census=True)[:2]
     assert (aux["status"][0] & ~(S.MH_WORLD_IMPACT_TOL | S.MH_WORLD_STAB_FAILED)) == 0
     assert aux["lcp_solves"][0] > 0 and census[0, :, 0].sum() > 0
     y0 = np.array([0.5 * BOX_DIMS[1], BOX_DIMS[1] + RADIUS])
@@ -237,7 +237,7 @@ def test_scene_file_loads_with_its_three_pairs(ref):
     np.testing.assert_array_equal(st.reshape(2, 13)[:, :3], [[0.0, 0.752, 0.0], [0.0, 0.25, 0.0]])
     # the reference steps it: the scene is in scope (no MH_WORLD_UNSUPPORTED from the broad phase) and the ball lands on the crate
     aux = S.new_aux(1); s = st.copy()
-    _, census = ref.step(sc, s, aux, dt, 30, want_census=True)
+    census = ref.step(sc, s, aux, dt, 30, want_census=True).census
     assert (aux["status"][0] & ~S.MH_WORLD_IMPACT_TOL) == 0 and census[0, :, 0].sum() > 0
 
 

@@ -1,5 +1,5 @@
 """Box-sphere contacts between free bodies in the many-worlds stepper (include/moby_hip.h, "Box-sphere pairs"; mh_world_large_bsp*.hip) against
-tests/native/world_boxsphere_ref.cpp, bit for bit: states, trajectories and complete aux records, no tolerance anywhere.  The batches and their
+tests/native/world_ref.cpp, bit for bit: states, trajectories and complete aux records, no tolerance anywhere.  The batches and their
 reference results live in tests/world_boxsphere_ref.py (computed once per process); the conditions on the inputs are asserted there and here."""
 
 import numpy as np
@@ -9,8 +9,8 @@ from moby_amd import _lib
 from moby_amd import io as mio
 from moby_amd import scene as S
 from moby_amd.world import WorldBatch, WorldBatchDevice
-from tests.world_force_ref import assert_aux_equal
-from tests.world_boxsphere_ref import (EDGE, FACE, PENETRATING, SCENE_XML, VERTEX, centre_inside_box, gpu_cases, reference, reference_run)
+from tests.world_ref import assert_aux_equal, reference
+from tests.world_boxsphere_ref import (EDGE, FACE, PENETRATING, SCENE_XML, VERTEX, centre_inside_box, gpu_cases, reference_run)
 
 pytestmark = pytest.mark.gpu
 
@@ -181,7 +181,7 @@ def test_scene_file():
     assert ids == ["ball", "crate", "ground"] and dt == 1e-3
     assert not centre_inside_box(sc, st0)
     st_r, aux_r = st0.copy(), S.new_aux(1)
-    traj_r, census = reference().step(sc, st_r, aux_r, dt, 30, want_traj=True, want_census=True)
+    traj_r, census = reference().step(sc, st_r, aux_r, dt, 30, want_traj=True, want_census=True)[:2]
     assert (aux_r["status"] & ~S.MH_WORLD_IMPACT_TOL) == 0 and aux_r["lcp_solves"][0] > 0 and census[:, :, FACE].sum() > 0
     wb = WorldBatch(sc, st0.copy())
     traj = wb.step(dt, 30, want_traj=True)

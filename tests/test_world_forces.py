@@ -1,8 +1,9 @@
 """Recurrent forces and per-world body wrenches of the many-worlds stepper (include/moby_hip.h: mh_world_forces, mh_world_batch_set_forces,
-mh_world_batch_step_wrench) without a GPU: the forced reference (tests/native/world_force_ref.cpp, a restatement of oracle::World::fwd_dyn /
+mh_world_batch_step_wrench) without a GPU: the reference's forcing (tests/native/world_ref.cpp, a restatement of oracle::World::fwd_dyn /
 do_mini_step / step with the terms) pinned to the oracle -- with no terms it IS oracle_world_step_batch -- and to the recurrence written out in
 numpy; what the terms must do physically (hover, terminal velocity, the friction cone); the ctypes mirror and the argument checks of the new entry
-points.  The reference's ctypes face and the batches shared with the GPU tests live in tests/world_force_ref.py."""
+points.  The reference's ctypes face lives in tests/world_ref.py, the batches shared with the GPU tests in
+tests/world_force_ref.py."""
 import ctypes
 import os
 import subprocess
@@ -11,7 +12,8 @@ import numpy as np
 import pytest
 
 from moby_amd import scene as S
-from tests.world_force_ref import G, assert_aux_equal, cone_batch, hover_batch, reference
+from tests.world_force_ref import G, cone_batch, hover_batch
+from tests.world_ref import assert_aux_equal, reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,7 +34,8 @@ PIN_A = {
 
 @pytest.mark.parametrize("name", sorted(PIN_A))
 def test_reference_without_terms_is_the_oracle(oracle, force_ref, name):
-    """pin A: no forces, terms == 0 and a NULL wrench step exactly as oracle_world_step_batch: states and whole aux records"""
+    """pin A: no forces (the oracle's own forward dynamics) and forces with terms == 0 (the restated one, with nothing to add), both with a NULL wrench,
+    step exactly as oracle_world_step_batch: states and whole aux records"""
     sc, st0, dt, n = PIN_A[name]()
     B = st0.shape[0]
     st_o, aux_o = st0.copy(), S.new_aux(B)
@@ -40,19 +43,22 @@ def test_reference_without_terms_is_the_oracle(oracle, force_ref, name):
     assert (aux_o["lcp_solves"] > 0).all()
     for forces in (None, S.mh_world_forces()):
         st_r, aux_r = st0.copy(), S.new_aux(B)
-        force_ref.step(sc, st_r, aux_r, dt, n, forces)
+        force_ref.step(sc, st_r, aux_r, dt, n, forces=forces)
         np.testing.assert_array_equal(st_r, st_o)
         assert_aux_equal(aux_r, aux_o)
         assert aux_r.tobytes() == aux_o.tobytes()
 
 
-def test_zero_coefficients_change_nothing_on_the_sphere_stack(oracle, force_ref):
-    """both terms present with all coefficients zero: v (-0) and R (R' v (-0)) add signed zeros only"""
-    sc, st0, dt, n = PIN_A["stack"]()
-    st_o, aux_o = st0.copy(), S.new_aux(5)
+@pytest.mark.parametrize("name", sorted(PIN_A))
+def test_zero_coefficients_change_nothing(oracle, force_ref, name):
+    """both terms present with all coefficients zero equal oracle_world_step_batch on every pin A scene (stack, wheel, box, ball): v (-0) and
+    R (R' v (-0)) add signed zeros only.  With pin A this is what holds the restated forward dynamics to the oracle on every scene family"""
+    sc, st0, dt, n = PIN_A[name]()
+    B = st0.shape[0]
+    st_o, aux_o = st0.copy(), S.new_aux(B)
     oracle.world_step_batch(sc, st_o, aux_o, dt, n)
-    st_r, aux_r = st0.copy(), S.new_aux(5)
-    force_ref.step(sc, st_r, aux_r, dt, n, S.make_forces(3, stokes=(0.0, 0.0), damping=(0.0, 0.0, 0.0, 0.0)))
+    st_r, aux_r = st0.copy(), S.new_aux(B)
+    force_ref.step(sc, st_r, aux_r, dt, n, forces=S.make_forces(sc.nb, stokes=(0.0, 0.0), damping=(0.0, 0.0, 0.0, 0.0)))
     np.testing.assert_array_equal(st_r, st_o)
     assert_aux_equal(aux_r, aux_o)
 
@@ -69,7 +75,7 @@ def test_stokes_and_wrench_follow_the_recurrence_bit_for_bit(force_ref):
     aux = S.new_aux(1)
     forces = S.make_forces(1, stokes=(b, 0.0))
     for _ in range(20):
-        force_ref.step(sc, st, aux, dt, 1, forces, wrench)
+        force_ref.step(sc, st, aux, dt, 1, forces=forces, wrench=wrench)
         F = g * m
         F = F + v * (-b)
         F = F + f
@@ -82,7 +88,7 @@ def test_a_wrench_that_cancels_gravity_leaves_the_velocities_untouched(force_ref
     """hover: f_y = -(g_y m_b) makes F_y = g m + (-(g m)) = 0 exactly, for every mass: 50 steps change no linear velocity by a bit"""
     sc, st0, wrench = hover_batch()
     st, aux = st0.copy(), S.new_aux(st0.shape[0])
-    force_ref.step(sc, st, aux, 0.01, 50, None, wrench)
+    force_ref.step(sc, st, aux, 0.01, 50, wrench=wrench)
     v0 = st0.reshape(-1, sc.nb, 13)[:, :, 7:10]; v1 = st.reshape(-1, sc.nb, 13)[:, :, 7:10]
     np.testing.assert_array_equal(v1, v0)
     assert (aux["status"] == 0).all() and (aux["lcp_solves"] == 0).all()
@@ -96,7 +102,7 @@ def test_terminal_velocity_under_stokes_drag(force_ref):
     sc = S.make_scene([0.5], [m], (0.0, -G, 0.0))
     st = np.zeros((1, 13)); st[0, 6] = 1.0
     aux = S.new_aux(1)
-    force_ref.step(sc, st, aux, 0.01, 400, S.make_forces(1, stokes=(b, 0.0)))
+    force_ref.step(sc, st, aux, 0.01, 400, forces=S.make_forces(1, stokes=(b, 0.0)))
     want = -G * m / b
     rel = abs(st[0, 8] - want) / abs(want)
     print("terminal velocity: relative error %.3g" % rel)
@@ -108,7 +114,7 @@ def test_a_push_inside_the_friction_cone_does_not_move_the_box(force_ref):
     """mu m g = 4.905 N: pushes of 0, 2 and 4 N leave the box where it is, 8 N slides it past x = 1 in a second"""
     sc, st0, wrench = cone_batch()
     st, aux = st0.copy(), S.new_aux(4)
-    force_ref.step(sc, st, aux, 0.01, 100, None, wrench)
+    force_ref.step(sc, st, aux, 0.01, 100, wrench=wrench)
     print("friction cone: x =", st[:, 0])
     assert np.abs(st[:3, 0]).max() < 1e-9
     assert st[3, 0] > 1.0

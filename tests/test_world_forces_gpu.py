@@ -1,5 +1,5 @@
 """Recurrent forces and per-world body wrenches in the one-wavefront world kernels (mh_world_{small,wheel,large}_forces.hip) on the GPU: every
-variant bit for bit against the forced reference (tests/native/world_force_ref.cpp) -- states and complete aux records, no tolerance anywhere --
+variant bit for bit against the forced reference (tests/native/world_ref.cpp) -- states and complete aux records, no tolerance anywhere --
 schedules, split launches, id lists, dead worlds, trajectories, residency, the unforced paths through the new entry points, and a scene file."""
 import ctypes
 import os
@@ -9,7 +9,8 @@ import pytest
 
 from moby_amd import scene as S
 from moby_amd.world import WorldBatch, WorldBatchDevice
-from tests.world_force_ref import assert_aux_equal, reference, reference_run
+from tests.world_force_ref import reference_run
+from tests.world_ref import assert_aux_equal, reference
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -243,7 +244,7 @@ def test_drag_scene_file_runs_as_the_reference(force_ref):
     sc, st0, ids, dt, forces = mio.load_xml_forces(os.path.join(ROOT, "tests", "scenes", "ball_in_syrup.xml"))
     assert forces.terms == S.MH_FORCE_STOKES and dt == 0.01
     st_r, aux_r = st0.copy(), S.new_aux(1)
-    force_ref.step(sc, st_r, aux_r, dt, 150, forces)
+    force_ref.step(sc, st_r, aux_r, dt, 150, forces=forces)
     assert aux_r["status"][0] == 0 and aux_r["lcp_solves"][0] > 0
     host = WorldBatch(sc, st0.copy(), forces=forces)
     host.step(dt, 150)

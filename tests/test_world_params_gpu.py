@@ -7,7 +7,7 @@ import pytest
 from moby_amd import _lib
 from moby_amd import scene as S
 from moby_amd.world import WorldBatch, WorldBatchDevice
-from tests.world_force_ref import assert_aux_equal
+from tests.world_ref import assert_aux_equal
 from tests import world_params_ref as P
 from tests import world_statics_ref as W
 

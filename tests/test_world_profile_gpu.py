@@ -9,7 +9,7 @@ from moby_amd import _lib
 from moby_amd import scene as S
 from moby_amd.synth import world_uniforms
 from moby_amd.world import WorldBatchDevice
-from tests.world_force_ref import assert_aux_equal
+from tests.world_ref import assert_aux_equal
 
 pytestmark = pytest.mark.gpu
 

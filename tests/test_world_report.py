@@ -1,5 +1,5 @@
 """The per-pair contact impulse report of the many-worlds stepper (include/moby_hip.h, "Contact report") without a GPU: the report reference
-(tests/native/world_report_ref.cpp) pinned to the statics reference and to the momentum balance, the conditions on the GPU cases, the refusals (they run
+(tests/native/world_ref.cpp with a report sink) pinned to the step without one and to the momentum balance, the conditions on the GPU cases, the refusals (they run
 before the device is looked for), debug key 18 and moby_amd.world.body_impulses."""
 import ctypes
 import functools
@@ -12,6 +12,7 @@ import pytest
 from moby_amd import _lib
 from moby_amd import scene as S
 from moby_amd import world as MW
+from tests import world_ref
 from tests import world_report_ref as R
 from tests import world_statics_ref as W
 
@@ -35,7 +36,7 @@ def stepwise(name):
     st, aux = st0.copy(), S.new_aux(B)
     states, times, rows = [st.copy()], [aux["time"].copy()], []
     for _ in range(nsteps):
-        _, rep, _ = R.reference().step(sc, stt, st, aux, dt, 1)
+        rep = world_ref.reference().step(sc, st, aux, dt, 1, statics=stt, want_report=True).report
         states.append(st.copy()); times.append(aux["time"].copy()); rows.append(rep[:, 0])
     report = np.stack(rows, axis=1)
     _, st1, aux1, rep1, _ = R.reference_run(name)
@@ -46,10 +47,12 @@ def stepwise(name):
 
 
 @pytest.mark.parametrize("name", sorted(PIN))
-def test_report_reference_is_the_statics_reference(name):
-    """the restated mini-step changes nothing: state, trajectory and the complete aux record bit-equal to world_statics_ref's step"""
+def test_the_report_sink_changes_no_step(name):
+    """the same entry (world_ref_step) without and with a report sink: state, trajectory and the complete aux record are bit-equal, so the fold behind
+    handle_impacts only reads"""
     sc, stt, st0, dt, nsteps = PIN[name]()
-    st_w, aux_w, traj_w, _ = W.run_ref(sc, stt, st0, dt, nsteps, want_traj=True)
+    st_w, aux_w, (traj_w, _, no_rep, no_shape) = world_ref.run_ref(sc, st0, dt, nsteps, statics=stt, want_traj=True)
+    assert no_rep is None and no_shape is None
     st_r, aux_r, traj_r, rep, _ = R.run_ref(sc, stt, st0, dt, nsteps, want_traj=True)
     np.testing.assert_array_equal(st_r, st_w)
     np.testing.assert_array_equal(traj_r, traj_w)
@@ -86,7 +89,7 @@ def test_resting_ball():
     st, aux = st0.copy(), S.new_aux(1)
     for s in range(nsteps):
         before = st[0].copy()
-        _, rep, _ = R.reference().step(sc, stt, st, aux, dt, 1)
+        rep = world_ref.reference().step(sc, st, aux, dt, 1, statics=stt, want_report=True).report
         assert aux["status"][0] == 0 and rep.shape == (1, 1, 1, 8)
         row = rep[0, 0, 0]
         assert row[0] >= 1.0 and row[1] > 0.0

@@ -1,5 +1,5 @@
 """The per-pair contact impulse report of the many-worlds stepper (include/moby_hip.h, "Contact report"; mh_world_large_rp*.hip) against the report
-reference (tests/native/world_report_ref.cpp): states, complete aux records and EVERY report row bit for bit, no tolerance anywhere.  What each case is
+reference (tests/native/world_ref.cpp): states, complete aux records and EVERY report row bit for bit, no tolerance anywhere.  What each case is
 there for is asserted on the reference in tests/test_world_report.py (tests/world_report_ref.py shape_conditions)."""
 import numpy as np
 import pytest
@@ -7,7 +7,7 @@ import pytest
 from moby_amd import _lib
 from moby_amd import scene as S
 from moby_amd.world import WorldBatch, WorldBatchDevice, report_npt
-from tests.world_force_ref import assert_aux_equal
+from tests.world_ref import assert_aux_equal
 from tests import world_params_ref as P
 from tests import world_report_ref as R
 

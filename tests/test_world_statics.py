@@ -1,9 +1,9 @@
 """Static planes and boxes among the free bodies of the many-worlds stepper (include/moby_hip.h, "Static bodies") without a GPU: the reference the
-kernels are held to (tests/native/world_statics_ref.cpp, a restatement of what several statics change in oracle::World) pinned to the oracle -- the
+kernels are held to (tests/native/world_ref.cpp, a restatement of what several statics change in oracle::World) pinned to the oracle -- the
 scene's ground, and the same plane handed over as a static, both ARE oracle_world_step_batch --, to the box geometry written out by hand on dyadic
 inputs and to the articulated reference's static box; a mirror property of two opposed walls; the refusals of the new entry; the ctypes mirror; the
-exported symbols; the scene reader.  All comparisons are bit for bit.  The reference's ctypes face and the scenes shared with the GPU tests live in
-tests/world_statics_ref.py."""
+exported symbols; the scene reader.  All comparisons are bit for bit.  The reference's ctypes face lives in tests/world_ref.py, the scenes shared with the
+GPU tests in tests/world_statics_ref.py."""
 import ctypes
 import os
 import subprocess
@@ -14,7 +14,7 @@ import pytest
 from moby_amd import _lib
 from moby_amd import io as mio
 from moby_amd import scene as S
-from tests.world_force_ref import assert_aux_equal
+from tests.world_ref import assert_aux_equal, run_ref
 from tests import world_statics_ref as W
 # the hand-written values of the box-sphere geometry (box frame, half lengths (1, 0.5, 0.75), dyadic throughout): the same tables, other box poses
 from tests.test_world_boxsphere import CONTACTS, DIMS, DISTS
@@ -81,10 +81,26 @@ def test_reference_is_the_oracle(ref, pinned, name, as_static):
         assert aux_o["stab_iters"].sum() > 0
     sc2, stt = ground_as_static(sc) if as_static else (sc, None)
     st_r, aux_r = st0.copy(), S.new_aux(st0.shape[0])
-    ref.step(sc2, stt, st_r, aux_r, dt, 40)
+    ref.step(sc2, st_r, aux_r, dt, 40, statics=stt)
     np.testing.assert_array_equal(st_r, st_o)
     assert_aux_equal(aux_r, aux_o)
     assert aux_r.tobytes() == aux_o.tobytes()
+
+
+@pytest.mark.parametrize("name", ["face", "full"])
+def test_no_statics_is_an_empty_record(name):
+    """statics = None steps exactly as an empty mh_world_statics (n = 0) on box-sphere batches: state, trajectory, census and whole aux records"""
+    from tests.world_boxsphere_ref import gpu_cases
+    c = gpu_cases()[name]
+    empty = S.mh_world_statics()
+    assert empty.n == 0
+    st_n, aux_n, r_n = run_ref(c["scene"], c["state"], c["dt"], c["nsteps"], want_traj=True, want_census=True)
+    st_e, aux_e, r_e = run_ref(c["scene"], c["state"], c["dt"], c["nsteps"], statics=empty, want_traj=True, want_census=True)
+    assert (aux_n["lcp_solves"] > 0).all() and r_n.census[:, :, :W.PENETRATING + 1].sum() > 0
+    np.testing.assert_array_equal(st_e, st_n)
+    np.testing.assert_array_equal(r_e.traj, r_n.traj)
+    np.testing.assert_array_equal(r_e.census, r_n.census)
+    assert aux_e.tobytes() == aux_n.tobytes()
 
 
 # ---- 2. static-box geometry ----------------------------------------------------------------------------------------------------------------------
@@ -131,7 +147,7 @@ def test_static_box_through_the_pair_probe(ref):
     stt = S.make_statics([dict(box=DIMS, R=P[1], o=tuple(P[0])), dict(plane=True, R=W.R_UP, o=(0.0, -10.0, 0.0))])
     c = CONTACTS["edge_separated"][0]
     st = np.zeros(13); st[:3] = to_world(P, c); st[6] = 1.0
-    got = ref.pair(sc, stt, st, 0, 0.25)
+    got = ref.pair(sc, st, 0, 0.25, statics=stt)
     want = ref.box_contact(P[0], P[1], DIMS, st[:3], 0.5, 0.25)
     assert (got["a"], got["b"], got["ncontacts"], got["g1"], got["g2"], got["kept"]) == (0, 1, 1, 1, 0, 1)
     assert got["cdist"] == want["dist"]
@@ -139,18 +155,18 @@ def test_static_box_through_the_pair_probe(ref):
     d, pbox, psph = ref.box_dist(P[0], P[1], DIMS, st[:3], 0.5)
     assert got["dist"] == d
     np.testing.assert_array_equal(got["pa"], psph); np.testing.assert_array_equal(got["pb"], pbox)
-    assert ref.pair(sc, stt, st, 2, 0.25)["kept"] == 0                     # (static box, static plane)
+    assert ref.pair(sc, st, 2, 0.25, statics=stt)["kept"] == 0                     # (static box, static plane)
     far = st.copy(); far[:3] = (100.0, 100.0, 100.0)
-    assert ref.pair(sc, stt, far, 0, 0.25)["kept"] == 0 and ref.pair(sc, stt, far, 1, 0.25)["kept"] == 1   # a box's bound is finite, a plane's is not
+    assert ref.pair(sc, far, 0, 0.25, statics=stt)["kept"] == 0 and ref.pair(sc, far, 1, 0.25, statics=stt)["kept"] == 1   # a box's bound is finite, a plane's is not
 
 
-def test_static_box_equals_the_articulated_reference(ref, tmp_path_factory):
+def test_static_box_equals_the_articulated_reference(ref):
     """tests/native/artic_boxsphere_ref.cpp with a static axis-aligned box at the origin and the sphere on three sliders with zero offsets (q = its
     centre): the same contact and the same signed distance, bit for bit, on every case of the tables"""
     from moby_amd import artic as A
     from tests import artic_boxsphere_ref as BS
     from tests import artic_pair_ref as APR
-    aref = BS.build_boxsphere_ref(tmp_path_factory.mktemp("artic_boxsphere_ref"))
+    aref = BS.build_boxsphere_ref()
 
     def model(radius):
         links = [dict(parent=k - 1, type=A.MH_JOINT_PRISMATIC, R0=np.eye(3), x0=(0.0, 0.0, 0.0), axis=np.eye(3)[k], com=(0.0, 0.0, 0.0),
@@ -182,7 +198,7 @@ def test_two_opposed_walls_mirror(ref):
     st = W.sphere_state(2, 1)
     W.set_body(st, 0, 0, (0.125, 0.5, -0.25), v=(3.0, 0.0, 0.0))
     W.set_body(st, 1, 0, (-0.125, 0.5, -0.25), v=(-3.0, 0.0, 0.0))
-    s, aux, traj, _ = W.run_ref(sc, stt, st.reshape(2, -1), 0.01, 120, want_traj=True)
+    s, aux, (traj, *_) = run_ref(sc, st.reshape(2, -1), 0.01, 120, statics=stt, want_traj=True)
     assert (aux["status"] & W.FATAL == 0).all() and (aux["lcp_solves"] >= 2).all()      # 3.6 m at 0.75 m between the turning points: several bounces
     mirror = traj[1].copy(); mirror[..., 0] = -mirror[..., 0]
     np.testing.assert_array_equal(traj[0], mirror)
@@ -223,7 +239,7 @@ def test_mixed_scene_equals_its_ground_as_static_twin_on_the_reference(ref, name
     c, st, aux, traj, _ = W.reference_run(name)
     sc2, stt2 = W.ground_to_static(c["scene"], c["statics"])
     assert (sc2.has_ground, stt2.n) == (0, 3) and bytes(sc2)[8:] == bytes(c["scene"])[8:]
-    st2, aux2, traj2, _ = W.run_ref(sc2, stt2, c["state"], c["dt"], c["nsteps"], want_traj=True, forces=c.get("forces"), wrench=c.get("wrench"))
+    st2, aux2, (traj2, *_) = run_ref(sc2, c["state"], c["dt"], c["nsteps"], statics=stt2, want_traj=True, forces=c.get("forces"), wrench=c.get("wrench"))
     np.testing.assert_array_equal(traj2, traj)
     np.testing.assert_array_equal(st2, st)
     assert aux2.tobytes() == aux.tobytes()

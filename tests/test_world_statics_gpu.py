@@ -1,5 +1,5 @@
 """Static planes and boxes among the free bodies of the many-worlds stepper (include/moby_hip.h, "Static bodies"; mh_world_large_st*.hip) against
-tests/native/world_statics_ref.cpp, bit for bit: states, trajectories and complete aux records, no tolerance anywhere.  The batches and their
+tests/native/world_ref.cpp, bit for bit: states, trajectories and complete aux records, no tolerance anywhere.  The batches and their
 reference results live in tests/world_statics_ref.py (computed once per process); worlds differ through world_uniforms."""
 import numpy as np
 import pytest
@@ -9,9 +9,9 @@ from moby_amd import io as mio
 from moby_amd import scene as S
 from moby_amd.synth import world_uniforms
 from moby_amd.world import WorldBatch, WorldBatchDevice
-from tests.world_force_ref import assert_aux_equal
+from tests.world_ref import assert_aux_equal, reference
 from tests import world_statics_ref as W
-from tests.world_statics_ref import EDGE, FACE, PENETRATING, VERTEX, gpu_cases, reference, reference_run
+from tests.world_statics_ref import EDGE, FACE, PENETRATING, VERTEX, gpu_cases, reference_run
 
 pytestmark = pytest.mark.gpu
 
@@ -60,9 +60,9 @@ def test_ball_in_a_corner():
     (worlds start a fraction of a micrometre inside or outside each of the three)"""
     case = gpu_cases()["corner"]
     for w in range(case["state"].shape[0]):
-        got = [reference().pair(case["scene"], case["statics"], case["state"][w], p, 1e-6) for p in range(3)]
+        got = [reference().pair(case["scene"], case["state"][w], p, 1e-6, statics=case["statics"]) for p in range(3)]
         assert [g["b"] for g in got] == [1, 2, 3]
-    d = np.array([[reference().pair(case["scene"], case["statics"], case["state"][w], p, 1e-6)["dist"] for p in range(3)] for w in range(case["state"].shape[0])])
+    d = np.array([[reference().pair(case["scene"], case["state"][w], p, 1e-6, statics=case["statics"])["dist"] for p in range(3)] for w in range(case["state"].shape[0])])
     assert (np.abs(d) < 1e-6).all() and (d < 0).any() and (d > 1.5e-8).any()
     _, aux, _ = check_case("corner")
     assert (aux["stab_iters"] > 0).all() and (aux["lcp_rows"] >= 3 * 20).all()
@@ -93,7 +93,7 @@ def test_capacity_is_flagged_in_the_step_of_the_reference():
     try:
         for s in range(case["nsteps"]):                            # one step per launch, until both sides have flagged every world
             dev.step(case["dt"], 1)
-            reference().step(case["scene"], case["statics"], st, aux, case["dt"], 1)
+            reference().step(case["scene"], st, aux, case["dt"], 1, statics=case["statics"])
             st_g, aux_g = dev.download()
             got[(got < 0) & ((aux_g["status"] & S.MH_WORLD_UNSUPPORTED) != 0)] = s
             want[(want < 0) & ((aux["status"] & S.MH_WORLD_UNSUPPORTED) != 0)] = s
@@ -216,7 +216,7 @@ def test_key_16_changes_no_result():
     from tests.world_boxsphere_ref import face_batch
     sc, st0 = face_batch(8)
     st_r, aux_r = st0.copy(), S.new_aux(8)
-    reference().step(sc, None, st_r, aux_r, 1e-3, 30)
+    reference().step(sc, st_r, aux_r, 1e-3, 30)
     lib = _lib.load()
     out = []
     try:
@@ -263,7 +263,7 @@ def test_scene_file():
         u = world_uniforms(1100 + w, 2)
         st0[w, 0] += 0.05 * (u[0] - 0.5); st0[w, 1] += 1e-3 * u[1]
     st_r, aux_r = st0.copy(), S.new_aux(4)
-    traj_r, census = reference().step(sc, stt, st_r, aux_r, dt, 30, want_traj=True, want_census=True)
+    traj_r, census = reference().step(sc, st_r, aux_r, dt, 30, statics=stt, want_traj=True, want_census=True)[:2]
     assert ((aux_r["status"] & ~S.MH_WORLD_IMPACT_TOL) == 0).all() and (aux_r["lcp_solves"] > 0).all() and census[:, :, :PENETRATING].sum() > 0
     wb = WorldBatch(sc, st0.copy(), statics=stt)
     traj = wb.step(dt, 30, want_traj=True)

@@ -6,9 +6,7 @@ bases), random states and random drives changed every launch of 10 steps; q, qd,
 bit for bit.     python tests/tools/fuzz_artic_box.py [seed0] [cases]"""
 import os
 import sys
-import tempfile
 import time
-from pathlib import Path
 
 import numpy as np
 
@@ -67,7 +65,7 @@ def make_case(seed):
 if __name__ == "__main__":
     seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 6100
     cases = int(sys.argv[2]) if len(sys.argv) > 2 else 300
-    ref = build_box_ref(Path(tempfile.mkdtemp()))
+    ref = build_box_ref()
     SKIP_AFTER = 5.0
     bad = skipped = solves = failed = unsup = rows16 = 0
     for case in range(cases):

@@ -9,9 +9,7 @@ well above a step's travel and starts every box-sphere pair apart.
 python tests/tools/fuzz_artic_boxsphere.py [seed0] [cases] [list: no GPU, the reference alone]"""
 import os
 import sys
-import tempfile
 import time
-from pathlib import Path
 
 import numpy as np
 
@@ -121,7 +119,7 @@ def make_case(seed):
 if __name__ == "__main__":
     seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 7100
     cases = int(sys.argv[2]) if len(sys.argv) > 2 else 300
-    ref = build_boxsphere_ref(Path(tempfile.mkdtemp()))
+    ref = build_boxsphere_ref()
     REF = ref
     SKIP_AFTER = 5.0
     bad = skipped = solves = failed = unsup = rows16 = inside = 0

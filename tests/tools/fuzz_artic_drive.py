@@ -4,10 +4,7 @@ plane, limits, restitution, both impact models, both dynamics algorithms; `float
 and forces, PD and feed-forward terms apart and together, held rows and per-step schedules, a new drive every launch of 10 steps; q, qd, the rand()
 stream, the warm starts and the counters bit for bit.     python tests/tools/fuzz_artic_drive.py [seed0] [cases] [floating]"""
 import os
-import re
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -15,6 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from moby_amd import artic as A, scene as S  # noqa: E402
+from tests import native_build               # noqa: E402
 from tests.oracle_api import Oracle          # noqa: E402
 from tests.test_artic_drive import DriveRef, random_drive  # noqa: E402
 from tests.tools import fuzz_artic as F      # noqa: E402
@@ -27,11 +25,7 @@ if __name__ == "__main__":
     seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 1900
     cases = int(sys.argv[2]) if len(sys.argv) > 2 else 40
     F.FLOATING = len(sys.argv) > 3 and sys.argv[3] == "floating"
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    tmp = tempfile.mkdtemp()
-    so = os.path.join(tmp, "libartic_drive_ref.so")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "artic_drive_ref.cpp"), "-o", so])
-    ref = DriveRef(so)
+    ref = DriveRef(native_build.build(("artic_drive_ref.cpp",), "artic_drive_ref"))
     SKIP_AFTER = 5.0
     bad = skipped = solves = 0
     for case in range(cases):

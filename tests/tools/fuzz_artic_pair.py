@@ -8,9 +8,7 @@ steps; q, qd, the poses, the rand() stream, the warm starts and the counters bit
 python tests/tools/fuzz_artic_pair.py [seed0] [cases]"""
 import os
 import sys
-import tempfile
 import time
-from pathlib import Path
 
 import numpy as np
 
@@ -92,7 +90,7 @@ def make_case(seed):
 if __name__ == "__main__":
     seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 6100
     cases = int(sys.argv[2]) if len(sys.argv) > 2 else 300
-    ref = build_pair_ref(Path(tempfile.mkdtemp()))
+    ref = build_pair_ref()
     SKIP_AFTER = 5.0
     bad = skipped = solves = failed = unsup = rows16 = 0
     if len(sys.argv) > 3:                                                     # (no GPU: list what the cases hold and what the reference makes of them)

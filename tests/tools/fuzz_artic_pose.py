@@ -5,10 +5,7 @@ against a floor under the no-slip or the Drumwright-Shell model, the stabiliser 
 middle hinge's quarter turn, and random drives (tau_ff on every column, PD on the body's joints) changed every launch of 10 steps; q, qd, the
 poses, the rand() stream, the warm starts and the counters bit for bit.     python tests/tools/fuzz_artic_pose.py [seed0] [cases]"""
 import os
-import re
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -16,6 +13,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from moby_amd import artic as A, scene as S  # noqa: E402
+from tests import native_build               # noqa: E402
 from tests.test_artic_drive import FIELDS    # noqa: E402
 from tests.test_artic_pose import PoseRef, random_floating  # noqa: E402
 
@@ -56,13 +54,7 @@ def make_case(seed):
 if __name__ == "__main__":
     seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 4100
     cases = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    tmp = tempfile.mkdtemp()
-    so = os.path.join(tmp, "libartic_pose_ref.so")
-    nat = os.path.join(ROOT, "tests", "native")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(nat, "artic_pose_ref.cpp"),
-                                             os.path.join(nat, "artic_drive_ref.cpp"), "-o", so])
-    ref = PoseRef(so)
+    ref = PoseRef(native_build.build(("artic_pose_ref.cpp", "artic_drive_ref.cpp"), "artic_pose_ref"))
     SKIP_AFTER = 5.0
     bad = skipped = solves = failed = 0
     for case in range(cases):

@@ -1,16 +1,13 @@
-"""TEST INFRASTRUCTURE shared by tests/test_world_boxsphere.py and tests/test_world_boxsphere_gpu.py: the ctypes face of the box-sphere reference
-(tests/native/world_boxsphere_ref.cpp), built once per process, the batches the tests run and their reference results, computed once and read-only."""
-import ctypes
+"""TEST INFRASTRUCTURE shared by tests/test_world_boxsphere.py and tests/test_world_boxsphere_gpu.py: the batches the box-sphere world step is tested
+on and their reference results (tests/world_ref.py), computed once and read-only."""
 import functools
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from moby_amd import scene as S
 from moby_amd.synth import world_uniforms
+from tests.world_ref import reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENE_XML = os.path.join(ROOT, "tests", "scenes", "ball_on_crate.xml")
@@ -18,70 +15,6 @@ FACE, EDGE, VERTEX, PENETRATING, NONE = range(5)     # columns of the region cen
 FATAL = S.MH_WORLD_LCP_FAILED | S.MH_WORLD_UNSUPPORTED | S.MH_WORLD_STALLED
 BOX_DIMS = (1.0, 0.5, 0.8)
 RADIUS = 0.25
-
-
-class BoxSphereRef:
-    """ctypes face of tests/native/world_boxsphere_ref.cpp"""
-
-    def __init__(self, path):
-        self.lib = ctypes.CDLL(path)
-        for f in ("world_boxsphere_ref_step", "world_boxsphere_ref_contact", "world_boxsphere_ref_dist", "world_boxsphere_ref_pair"):
-            getattr(self.lib, f).restype = None
-
-    def step(self, sc, state, aux, dt, nsteps, want_traj=False, want_census=False, forces=None, wrench=None):
-        """B worlds x nsteps in place -> (trajectory (B, nsteps, nb, 7) or None, census (B, nsteps, 5) or None); forces: S.mh_world_forces or None,
-        wrench: (B, nb, 6) or (rows, B, nb, 6) host array or None"""
-        B = state.shape[0]
-        P = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-        traj = np.zeros((B, nsteps, sc.nb, 7)) if want_traj else None
-        census = np.zeros((B, nsteps, 5), dtype=np.int32) if want_census else None
-        w, rows = None, 1
-        if wrench is not None:
-            w = np.ascontiguousarray(wrench, dtype=np.float64)
-            rows = 1 if w.ndim == 3 else w.shape[0]
-            assert w.shape[-3:] == (B, sc.nb, 6)
-        self.lib.world_boxsphere_ref_step(ctypes.byref(sc), int(B), ctypes.c_double(dt), int(nsteps), P(state), P(aux), P(traj), P(census),
-                                          None if forces is None else ctypes.byref(forces), P(w), int(rows))
-        return traj, census
-
-    @staticmethod
-    def _v(a, n):
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        assert a.shape == (n,)
-        return a
-
-    def contact(self, cb, quat, dims, cS, radius, TOL):
-        """-> dict(has, dist, point, normal, region) of a box pose (centre, quaternion xyzw, edge lengths) and a sphere"""
-        out = np.zeros(9)
-        a = [self._v(cb, 3), self._v(quat, 4), self._v(dims, 3), self._v(cS, 3)]
-        self.lib.world_boxsphere_ref_contact(*[x.ctypes.data_as(ctypes.c_void_p) for x in a], ctypes.c_double(radius), ctypes.c_double(TOL),
-                                             out.ctypes.data_as(ctypes.c_void_p))
-        return dict(has=int(out[0]), dist=out[1], point=out[2:5].copy(), normal=out[5:8].copy(), region=int(out[8]))
-
-    def dist(self, cb, quat, dims, cS, radius):
-        """-> (signed distance, box point, sphere point)"""
-        out = np.zeros(7)
-        a = [self._v(cb, 3), self._v(quat, 4), self._v(dims, 3), self._v(cS, 3)]
-        self.lib.world_boxsphere_ref_dist(*[x.ctypes.data_as(ctypes.c_void_p) for x in a], ctypes.c_double(radius), out.ctypes.data_as(ctypes.c_void_p))
-        return out[0], out[1:4].copy(), out[4:7].copy()
-
-    def pair(self, sc, state, p, TOL):
-        """pair p of a scene in one world's state, as the stepper reads it -> dict(dist, pa, pb, a, b, ncontacts, g1, g2, cdist, point, normal)"""
-        out = np.zeros(19)
-        st = np.ascontiguousarray(state, dtype=np.float64).ravel()
-        assert st.size == sc.nb * S.MH_BODY_STATE
-        self.lib.world_boxsphere_ref_pair(ctypes.byref(sc), st.ctypes.data_as(ctypes.c_void_p), int(p), ctypes.c_double(TOL), out.ctypes.data_as(ctypes.c_void_p))
-        return dict(dist=out[0], pa=out[1:4].copy(), pb=out[4:7].copy(), a=int(out[7]), b=int(out[8]), ncontacts=int(out[9]), g1=int(out[10]), g2=int(out[11]),
-                    cdist=out[12], point=out[13:16].copy(), normal=out[16:19].copy())
-
-
-@functools.lru_cache(maxsize=None)
-def reference():
-    """the box-sphere reference, built once per process with g++ and oracle/Makefile's CXXFLAGS (the oracle's floating-point contract: no FMA)"""
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = os.path.join(tempfile.mkdtemp(prefix="world_boxsphere_ref_"), "libworld_boxsphere_ref.so")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "world_boxsphere_ref.cpp"), "-o", so])
-    return BoxSphereRef(so)
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------------------------------
@@ -301,7 +234,7 @@ def reference_run(name):
     enabled box-sphere pair has solved LCPs and produced box-sphere contacts"""
     c = gpu_cases()[name]
     st, aux = c["state"].copy(), S.new_aux(c["state"].shape[0])
-    traj, census = reference().step(c["scene"], st, aux, c["dt"], c["nsteps"], want_traj=True, want_census=True, forces=c.get("forces"), wrench=c.get("wrench"))
+    traj, census = reference().step(c["scene"], st, aux, c["dt"], c["nsteps"], want_traj=True, want_census=True, forces=c.get("forces"), wrench=c.get("wrench"))[:2]
     if name != "noslip_capacity":
         assert 8 * int(((aux["status"] & FATAL) != 0).sum()) <= len(aux), (name, aux["status"])
     if name != "disabled":

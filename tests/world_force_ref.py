@@ -1,49 +1,13 @@
-"""TEST INFRASTRUCTURE shared by tests/test_world_forces.py and tests/test_world_forces_gpu.py: the ctypes face of the forced reference
-(tests/native/world_force_ref.cpp), built once per process, the batches the tests run and their reference results, computed once and read-only."""
-import ctypes
+"""TEST INFRASTRUCTURE shared by tests/test_world_forces.py and tests/test_world_forces_gpu.py: the batches the forced world step is tested on and their
+reference results (tests/world_ref.py), computed once and read-only."""
 import functools
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from moby_amd import scene as S
+from tests.world_ref import reference
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = 9.81
-
-
-class ForceRef:
-    """ctypes face of tests/native/world_force_ref.cpp"""
-
-    def __init__(self, path):
-        self.lib = ctypes.CDLL(path)
-        self.lib.world_force_ref_step.restype = None
-
-    def step(self, sc, state, aux, dt, nsteps, forces=None, wrench=None, want_traj=False):
-        """B worlds x nsteps in place; wrench: (B, nb, 6) or (rows, B, nb, 6) host array; -> trajectory (B, nsteps, nb, 7) or None"""
-        B = state.shape[0]
-        P = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-        w, rows = None, 1
-        if wrench is not None:
-            w = np.ascontiguousarray(wrench, dtype=np.float64)
-            rows = 1 if w.ndim == 3 else w.shape[0]
-            assert w.shape[-3:] == (B, sc.nb, 6)
-        traj = np.zeros((B, nsteps, sc.nb, 7)) if want_traj else None
-        self.lib.world_force_ref_step(ctypes.byref(sc), int(B), ctypes.c_double(dt), int(nsteps), P(state), P(aux),
-                                      None if forces is None else ctypes.byref(forces), P(w), int(rows), P(traj))
-        return traj
-
-
-@functools.lru_cache(maxsize=None)
-def reference():
-    """the forced reference, built once per process with g++ and oracle/Makefile's CXXFLAGS (the oracle's floating-point contract: no FMA)"""
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = os.path.join(tempfile.mkdtemp(prefix="world_force_ref_"), "libworld_force_ref.so")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "world_force_ref.cpp"), "-o", so])
-    return ForceRef(so)
 
 
 # ---- the batches ------------------------------------------------------------------------------------------------------------------------------
@@ -109,21 +73,10 @@ def reference_run(name):
     """(case, final state, final aux, trajectory) of the reference for gpu_cases()[name], computed once per process and handed out read-only"""
     c = gpu_cases()[name]
     st, aux = c["state"].copy(), S.new_aux(c["state"].shape[0])
-    traj = reference().step(c["scene"], st, aux, c["dt"], c["nsteps"], c["forces"], c["wrench"], want_traj=True)
+    traj = reference().step(c["scene"], st, aux, c["dt"], c["nsteps"], forces=c["forces"], wrench=c["wrench"], want_traj=True).traj
     # a world that ends with an error bit makes the INPUT wrong for a comparison (MH_WORLD_IMPACT_TOL is a warning)
     assert ((aux["status"] & ~S.MH_WORLD_IMPACT_TOL) == 0).all(), (name, aux["status"])
     for a in (st, aux, traj):
         a.setflags(write=False)
     return c, st, aux, traj
 
-
-def assert_aux_equal(a, b):
-    """complete records: rand ring, time, status, every counter, zlast / zbuf / vns with their sizes"""
-    for f in S.AUX_DTYPE.names:
-        if f in ("zlast", "zbuf", "vns", "pad0"):
-            continue
-        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
-    for w in range(len(b)):
-        for arr, n in (("zlast", "zlast_size"), ("zbuf", "zbuf_cap"), ("vns", "vns_size")):
-            k = int(b[n][w])
-            np.testing.assert_array_equal(a[arr][w, :k], b[arr][w, :k], err_msg="%s of world %d" % (arr, w))

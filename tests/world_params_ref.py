@@ -27,7 +27,7 @@ def world_scene(sc, stt, params, w):
 
 
 def step_ref_params(sc, stt, params, st, aux, dt, nsteps, want_traj=False, forces=None, wrench=None):
-    """the statics reference on the worlds of a varied batch IN PLACE (st (B, nb * 13), aux B records), one run per world -> trajectory or None.
+    """the reference on the worlds of a varied batch IN PLACE (st (B, nb * 13), aux B records), one run per world -> trajectory or None.
     wrench: (B, nb, 6) or (rows, B, nb, 6), as the batch takes it; world w reads its own entries"""
     B = st.shape[0]
     traj = np.zeros((B, nsteps, sc.nb, 7)) if want_traj else None
@@ -35,7 +35,7 @@ def step_ref_params(sc, stt, params, st, aux, dt, nsteps, want_traj=False, force
         s2, t2 = world_scene(sc, stt, params, w)
         sw, aw = st[w:w + 1].copy(), aux[w:w + 1].copy()
         ww = None if wrench is None else np.ascontiguousarray(np.asarray(wrench)[..., w:w + 1, :, :])
-        tr, _ = W.reference().step(s2, t2, sw, aw, dt, nsteps, want_traj=want_traj, forces=forces, wrench=ww)
+        tr = W.reference().step(s2, sw, aw, dt, nsteps, statics=t2, want_traj=want_traj, forces=forces, wrench=ww).traj
         st[w], aux[w] = sw[0], aw[0]
         if want_traj:
             traj[w] = tr[0]

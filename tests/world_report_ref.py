@@ -1,69 +1,25 @@
-"""TEST INFRASTRUCTURE shared by tests/test_world_report.py and tests/test_world_report_gpu.py: the ctypes face of the contact-report reference
-(tests/native/world_report_ref.cpp), built once per process, the cases the tests run and their reference results, computed once and read-only."""
-import ctypes
+"""TEST INFRASTRUCTURE shared by tests/test_world_report.py and tests/test_world_report_gpu.py: the cases the contact report is tested on and their
+reference results (tests/world_ref.py, the step with a report sink), computed once and read-only."""
 import functools
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from moby_amd import scene as S
 from tests import world_force_ref as F
 from tests import world_params_ref as P
+from tests import world_ref
 from tests import world_statics_ref as W
+from tests.world_ref import REPORT_PAIR, npt_of
 
 ROOT = W.ROOT
 FATAL = W.FATAL
-REPORT_PAIR = 8
-SH_MINI, SH_PAIR_CONTACTS, SH_PAIRS_LOADED, SH_RESTITUTION, SH_ZERO, SH_NEG_SIGN = range(6)    # columns of the shape census (world_report_ref.cpp)
-
-
-def npt_of(sc, stt):
-    ntot = sc.nb + sc.has_ground + (stt.n if stt is not None else 0)
-    return ntot * (ntot - 1) // 2
-
-
-class ReportRef:
-    """ctypes face of tests/native/world_report_ref.cpp"""
-
-    def __init__(self, path):
-        self.lib = ctypes.CDLL(path)
-        self.lib.world_report_ref_step.restype = None
-
-    def step(self, sc, statics, state, aux, dt, nsteps, want_traj=False, forces=None, wrench=None):
-        """B worlds x nsteps in place -> (trajectory (B, nsteps, nb, 7) or None, report (B, nsteps, npt, 8), shape census (B, nsteps, 6))"""
-        B = state.shape[0]
-        Pp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-        traj = np.zeros((B, nsteps, sc.nb, 7)) if want_traj else None
-        report = np.full((B, nsteps, npt_of(sc, statics), REPORT_PAIR), np.nan)
-        shape = np.zeros((B, nsteps, 6), dtype=np.int32)
-        w, rows = None, 1
-        if wrench is not None:
-            w = np.ascontiguousarray(wrench, dtype=np.float64)
-            rows = 1 if w.ndim == 3 else w.shape[0]
-            assert w.shape[-3:] == (B, sc.nb, 6)
-        self.lib.world_report_ref_step(ctypes.byref(sc), None if statics is None else ctypes.byref(statics), int(B), ctypes.c_double(dt), int(nsteps),
-                                       Pp(state), Pp(aux), Pp(traj), None if forces is None else ctypes.byref(forces), Pp(w), int(rows), Pp(report), Pp(shape))
-        return traj, report, shape
-
-
-@functools.lru_cache(maxsize=None)
-def reference():
-    """the report reference, built once per process with g++ and oracle/Makefile's CXXFLAGS (the oracle's floating-point contract: no FMA)"""
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = os.path.join(tempfile.mkdtemp(prefix="world_report_ref_"), "libworld_report_ref.so")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "world_report_ref.cpp"), "-o", so])
-    return ReportRef(so)
+SH_MINI, SH_PAIR_CONTACTS, SH_PAIRS_LOADED, SH_RESTITUTION, SH_ZERO, SH_NEG_SIGN = range(6)    # columns of the shape census (tests/native/world_ref.cpp)
 
 
 def run_ref(sc, stt, st, dt, nsteps, seed=1, aux=None, **kw):
-    """the reference on copies -> (state, aux, trajectory or None, report, shape census)"""
-    s2 = np.array(st, dtype=np.float64, copy=True)
-    a2 = S.new_aux(s2.shape[0], seed) if aux is None else aux.copy()
-    traj, report, shape = reference().step(sc, stt, s2, a2, dt, nsteps, **kw)
-    return s2, a2, traj, report, shape
+    """the reference with the report on copies -> (state, aux, trajectory or None, report, shape census)"""
+    s2, a2, r = world_ref.run_ref(sc, st, dt, nsteps, seed=seed, aux=aux, statics=stt, want_report=True, want_shape=True, **kw)
+    return s2, a2, r.traj, r.report, r.shape
 
 
 def run_ref_params(sc, stt, params, st, dt, nsteps, forces=None, wrench=None):
@@ -152,7 +108,7 @@ def reference_run(name):
 
 
 def shape_conditions():
-    """what the cases are there for, asserted on the reference runs alone (the numbers are those of tests/native/world_report_ref.cpp's census)"""
+    """what the cases are there for, asserted on the reference runs alone (the numbers are those of tests/native/world_ref.cpp's census)"""
     sh = {n: reference_run(n)[4] for n in ("corner", "box_ball", "mixed", "noslip_table")}
     assert (sh["box_ball"][..., SH_PAIR_CONTACTS] >= 2).any() and (sh["mixed"][..., SH_PAIR_CONTACTS] >= 2).any()       # 1: several contacts of one pair
     assert (sh["corner"][..., SH_PAIRS_LOADED] >= 3).any()                                                                      # 2: three loaded pairs at once

@@ -1,16 +1,13 @@
-"""TEST INFRASTRUCTURE shared by tests/test_world_statics.py and tests/test_world_statics_gpu.py: the ctypes face of the statics reference
-(tests/native/world_statics_ref.cpp), built once per process, and the scenes and batches the tests run."""
-import ctypes
+"""TEST INFRASTRUCTURE shared by tests/test_world_statics.py and tests/test_world_statics_gpu.py: the scenes and batches the world step with statics is
+tested on and their reference results (tests/world_ref.py), computed once and read-only."""
 import functools
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from moby_amd import scene as S
 from moby_amd.synth import world_uniforms
+from tests.world_ref import reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENE_XML = os.path.join(ROOT, "tests", "scenes", "ball_in_corner.xml")
@@ -31,70 +28,6 @@ def rot_y(c, s):
 
 def rot_z(c, s):
     return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-
-
-class StaticsRef:
-    """ctypes face of tests/native/world_statics_ref.cpp"""
-
-    def __init__(self, path):
-        self.lib = ctypes.CDLL(path)
-        for f in ("world_statics_ref_step", "world_statics_ref_box_contact", "world_statics_ref_box_dist", "world_statics_ref_pair"):
-            getattr(self.lib, f).restype = None
-
-    def step(self, sc, statics, state, aux, dt, nsteps, want_traj=False, want_census=False, forces=None, wrench=None):
-        """B worlds x nsteps in place -> (trajectory (B, nsteps, nb, 7) or None, census (B, nsteps, 5) or None)"""
-        B = state.shape[0]
-        P = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-        traj = np.zeros((B, nsteps, sc.nb, 7)) if want_traj else None
-        census = np.zeros((B, nsteps, 5), dtype=np.int32) if want_census else None
-        w, rows = None, 1
-        if wrench is not None:
-            w = np.ascontiguousarray(wrench, dtype=np.float64)
-            rows = 1 if w.ndim == 3 else w.shape[0]
-            assert w.shape[-3:] == (B, sc.nb, 6)
-        self.lib.world_statics_ref_step(ctypes.byref(sc), None if statics is None else ctypes.byref(statics), int(B), ctypes.c_double(dt), int(nsteps),
-                                        P(state), P(aux), P(traj), P(census), None if forces is None else ctypes.byref(forces), P(w), int(rows))
-        return traj, census
-
-    @staticmethod
-    def _v(a, n):
-        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
-        assert a.shape == (n,)
-        return a
-
-    def box_contact(self, cb, R, dims, cS, radius, TOL):
-        """-> dict(has, dist, point, normal, region) of a box (centre, axes R row-major, edge lengths) and a sphere"""
-        out = np.zeros(9)
-        a = [self._v(cb, 3), self._v(R, 9), self._v(dims, 3), self._v(cS, 3)]
-        self.lib.world_statics_ref_box_contact(*[x.ctypes.data_as(ctypes.c_void_p) for x in a], ctypes.c_double(radius), ctypes.c_double(TOL),
-                                               out.ctypes.data_as(ctypes.c_void_p))
-        return dict(has=int(out[0]), dist=out[1], point=out[2:5].copy(), normal=out[5:8].copy(), region=int(out[8]))
-
-    def box_dist(self, cb, R, dims, cS, radius):
-        """-> (signed distance, box point, sphere point)"""
-        out = np.zeros(7)
-        a = [self._v(cb, 3), self._v(R, 9), self._v(dims, 3), self._v(cS, 3)]
-        self.lib.world_statics_ref_box_dist(*[x.ctypes.data_as(ctypes.c_void_p) for x in a], ctypes.c_double(radius), out.ctypes.data_as(ctypes.c_void_p))
-        return out[0], out[1:4].copy(), out[4:7].copy()
-
-    def pair(self, sc, statics, state, p, TOL):
-        """pair p of a scene with statics in one world's state -> dict(dist, pa, pb, a, b, ncontacts, g1, g2, cdist, point, normal, kept)"""
-        out = np.zeros(20)
-        st = np.ascontiguousarray(state, dtype=np.float64).ravel()
-        assert st.size == sc.nb * S.MH_BODY_STATE
-        self.lib.world_statics_ref_pair(ctypes.byref(sc), None if statics is None else ctypes.byref(statics), st.ctypes.data_as(ctypes.c_void_p), int(p),
-                                        ctypes.c_double(TOL), out.ctypes.data_as(ctypes.c_void_p))
-        return dict(dist=out[0], pa=out[1:4].copy(), pb=out[4:7].copy(), a=int(out[7]), b=int(out[8]), ncontacts=int(out[9]), g1=int(out[10]), g2=int(out[11]),
-                    cdist=out[12], point=out[13:16].copy(), normal=out[16:19].copy(), kept=int(out[19]))
-
-
-@functools.lru_cache(maxsize=None)
-def reference():
-    """the statics reference, built once per process with g++ and oracle/Makefile's CXXFLAGS (the oracle's floating-point contract: no FMA)"""
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1).split()
-    so = os.path.join(tempfile.mkdtemp(prefix="world_statics_ref_"), "libworld_statics_ref.so")
-    subprocess.check_call(["g++"] + flags + ["-shared", "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "native", "world_statics_ref.cpp"), "-o", so])
-    return StaticsRef(so)
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------------------------------
@@ -384,10 +317,10 @@ def contact_worlds(case):
     st, aux = case["state"].copy(), S.new_aux(B)
     seen = {p: set() for p in slots}
     for _ in range(case["nsteps"]):
-        reference().step(sc, stt, st, aux, case["dt"], 1)
+        reference().step(sc, st, aux, case["dt"], 1, statics=stt)
         for w in range(B):
             for p in slots:
-                g = reference().pair(sc, stt, st[w], p, sc.contact_dist_thresh)
+                g = reference().pair(sc, st[w], p, sc.contact_dist_thresh, statics=stt)
                 if g["kept"] and g["ncontacts"] > 0:
                     seen[p].add(w)
     return seen, st, aux
@@ -453,7 +386,8 @@ def reference_run(name):
     assert name != "box_corner_capacity"      # a flagged world stalls in every later step (100000 empty mini-steps each): its test stops at the flag
     c = gpu_cases()[name]
     st, aux = c["state"].copy(), S.new_aux(c["state"].shape[0])
-    traj, census = reference().step(c["scene"], c["statics"], st, aux, c["dt"], c["nsteps"], want_traj=True, want_census=True, forces=c.get("forces"), wrench=c.get("wrench"))
+    traj, census = reference().step(c["scene"], st, aux, c["dt"], c["nsteps"], statics=c["statics"], want_traj=True, want_census=True, forces=c.get("forces"),
+                                    wrench=c.get("wrench"))[:2]
     assert ((aux["status"] & FATAL) == 0).all(), (name, aux["status"])
     assert (aux["lcp_solves"] > 0).all(), (name, aux["lcp_solves"])
     if name.startswith("mixed"):
@@ -464,10 +398,3 @@ def reference_run(name):
         a.setflags(write=False)
     return c, st, aux, traj, census
 
-
-def run_ref(sc, stt, st, dt, nsteps, seed=1, **kw):
-    """the reference on copies -> (state, aux, trajectory, census)"""
-    s2 = np.array(st, dtype=np.float64, copy=True)
-    aux = S.new_aux(s2.shape[0], seed)
-    traj, census = reference().step(sc, stt, s2, aux, dt, nsteps, **kw)
-    return s2, aux, traj, census
