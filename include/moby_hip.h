@@ -311,6 +311,9 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                                    record filled from the scene (1, for batches created after it; default 0: only batches created with records; for A/B runs).
                                             key 18: world batches that would take the per-world-parameters build stepped by the contact-report build, mh_world_large_rp*.hip, with
                                                    a NULL report (1, for batches created after it; default 0: only batches created for the report; for A/B runs).
+                                            key 19: articulated batches that would take the box-sphere kernels stepped by the contact-report kernels, mh_artic_rp*.hip, with a
+                                                   NULL report (1, for batches created after it; default 0: only batches of mh_artic_batch_create_report; for A/B runs;
+                                                   include/moby_hip_artic.h, "Contact report").
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);
@@ -515,8 +518,8 @@ int mh_world_step_batch_params(const mh_scene* scene, const mh_world_forces* for
  * Key 18 of mh_debug_set sends batches that would take the per-world-parameters build through these objects with a NULL report (A/B runs; no result
  * changes).
  * NOT built: the report inside the small and wheel variants (such batches take the objects above, as batches with records take theirs); per-contact
- * lists (the row is per pair); the angular impulse about the centre of mass ([5..7] gives the lever); the report in the large-world (moby_hip_stack.h)
- * and articulated steppers; the stabiliser's corrections (they move positions and carry no impulse in the reference either,
+ * lists (the row is per pair); the angular impulse about the centre of mass ([5..7] gives the lever); the report in the large-world stepper
+ * (moby_hip_stack.h; the articulated stepper has its own, per slot: moby_hip_artic.h, "Contact report"); the stabiliser's corrections (they move positions and carry no impulse in the reference either,
  * ConstraintStabilization.cpp:457). */
 /* (no existing layout changes, so MH_VERSION stays 102; a caller that needs to know tests this macro) */
 #define MH_WORLD_REPORT 1

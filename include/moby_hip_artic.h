@@ -282,6 +282,47 @@ int mh_artic_batch_set_base_pose(mh_artic_batch* ab, const double* pose);
 /* the poses into a caller DEVICE buffer (B x 7), stream-ordered: the pose counterpart of mh_artic_batch_state_dev */
 int mh_artic_batch_base_pose_dev(mh_artic_batch* ab, void* stream, double* dst);
 
+/* Contact report.  What the reference hands to ConstraintSimulator::constraint_post_callback_fn (ConstraintSimulator.cpp:353) -- the mini-step's contact
+ * constraints, each with the contact_impulse that ImpactConstraintHandler::update_from_stacked accumulated (ImpactConstraintHandler.cpp:298-327) --
+ * reduced per SLOT inside the step and left in device memory: the contact half of a GPU-resident control loop's observation (is the foot down, how
+ * hard does the tip press on the crate, where is the centre of pressure under a box foot), beside mh_artic_batch_state_dev.
+ * Slots: nslots = nspheres + nboxes + npairs (mh_artic_report_slots).  Slot s < nspheres is sphere s against the plane; slot nspheres + b is box b
+ * against the plane, all of its vertex contacts; slot nspheres + nboxes + k is pair k, of either kind.  A sphere masked off the plane and a static box
+ * keep their slot: its rows stay zero.  For world w, step s of the launch and a slot there is one row of MH_REPORT_PAIR (moby_hip.h: 8) doubles at
+ * report_dev[((w * nsteps + s) * nslots + slot) * MH_REPORT_PAIR].  The rows of a step start at zero and accumulate over the step's mini-steps, in
+ * mini-step order; within a mini-step in constraint-list order (canonical: spheres, then boxes with their vertices in get_vertices order, then pairs).
+ * A mini-step's contacts are folded once handle_impacts has returned without a throw (the point of CSim:353) -- also when the handler returned early
+ * because nothing was impacting, or because there was neither a contact nor a limit: its contacts then count, with zero impulse.  A mini-step that threw
+ * (the forward dynamics failed before the contacts were generated, or the handler set MH_WORLD_LCP_FAILED) is not folded: the step's rows keep what
+ * earlier mini-steps left.  Every step of a world that is passed over (MH_WORLD_LCP_FAILED) writes zero rows.  A world with MH_WORLD_UNSUPPORTED or
+ * MH_WORLD_STALLED has undefined rows from then on, as its state is; they are still written inside the world's own rows only.
+ * Contact c carries accumulated (cn, cs, ct): zeroed when the contact list is built; every application of impulses by the impact handler adds what it
+ * applied (the no-slip solve and its restitution pass; the Drumwright-Shell solve, its restitution pass with the tangential impulses applied again in
+ * full, and the second solve); the stabiliser's corrections add nothing.  The handler refuses more than MH_NOSLIP_MAX contacts, so a contact beyond
+ * them folds with zero impulse.  With p the stored contact point, n the normal and s, t the tangents, contact c adds to its slot's row:
+ *   [0]     += 1.0                  contacts, summed over mini-steps
+ *   [1]     += cn
+ *   [2..4]  += jv                   jv = (n cn + s cs) + t ct componentwise, every product and sum rounded on its own, model-frame axes: the impulse ON
+ *                                   THE REFERENCE'S GEOMETRY A.  For a plane contact A is the link that carries the sphere or box; for a pair A is
+ *                                   pair_a's link, and pair_b's link received -jv.  With a static box as A only -jv on the sphere's link is physical.
+ *   [5..7]  += p * cn               the contact point weighted by its normal impulse: the centre of pressure is [5..7] / [1]
+ * Such a batch steps through code objects of its own (mh_artic_rp.hip, mh_artic_rp_pose.hip: the box-sphere kernels with MH_ARTIC_REPORT_TU) whatever
+ * its geometry -- sphere-only, box, pair and box-sphere models alike; every batch of mh_artic_batch_create launches what it launched.  Pose coordinates
+ * work as for every family.  Key 19 of mh_debug_set sends batches that would take the box-sphere kernels through these objects with a NULL report (A/B
+ * runs; no result changes).
+ * NOT built: joint-limit impulses (the rows hold contacts only); per-contact lists (the row is per slot); angular impulses ([5..7] gives the lever);
+ * the report in the large-world stepper (moby_hip_stack.h); a host convenience entry. */
+/* (no existing layout changes, so MH_VERSION stays as it is; a caller that needs to know tests this macro) */
+#define MH_ARTIC_REPORT 1
+/* host only: nspheres + nboxes + npairs, or a negative MH_ERR_* for a NULL model or one whose counts lie outside their ranges */
+int mh_artic_report_slots(const mh_artic_model* model);
+/* mh_artic_batch_create with the report kernels: every check of mh_artic_batch_create, and MH_ERR_INVALID_ARG for a model without a slot. */
+int mh_artic_batch_create_report(const mh_artic_model* model, int B, mh_artic_batch** out);
+/* mh_artic_batch_step_driven plus the report (drive == NULL: the stored drive, or none): report_dev is a DEVICE array B x nsteps x nslots x
+ * MH_REPORT_PAIR doubles, written in stream order.  report_dev == NULL: the same kernels with nothing written.  MH_ERR_INVALID_ARG if
+ * report_dev != NULL on a batch not created by mh_artic_batch_create_report.  mh_artic_batch_step and _step_driven take such a batch and write no report. */
+int mh_artic_batch_step_report(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* drive, double* report_dev);
+
 #ifdef __cplusplus
 }
 #endif

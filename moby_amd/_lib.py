@@ -123,6 +123,9 @@ SYMBOLS = {
     "mh_artic_batch_base_pose": (_i, [_vp, _vp]),
     "mh_artic_batch_set_base_pose": (_i, [_vp, _vp]),
     "mh_artic_batch_base_pose_dev": (_i, [_vp, _vp, _vp]),
+    "mh_artic_report_slots": (_i, [_vp]),
+    "mh_artic_batch_create_report": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
+    "mh_artic_batch_step_report": (_i, [_vp, _vp, _d, _i, _vp, _vp]),
 }
 
 _lib = None

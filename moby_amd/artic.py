@@ -47,6 +47,35 @@ MH_ARTIC_CRB, MH_ARTIC_FSAB = 0, 1      # moby_hip_artic.h: RCArticulatedBody::a
 MH_DRIVE_FORCE, MH_DRIVE_PD = 1, 2       # moby_hip_artic.h: mh_artic_drive.terms
 MH_ARTIC_BASE_ANGLES, MH_ARTIC_BASE_POSE = 0, 1     # moby_hip_artic.h: mh_artic_batch_set_base_coords
 _BASE_COORDS = {"angles": MH_ARTIC_BASE_ANGLES, "pose": MH_ARTIC_BASE_POSE}
+REPORT_PAIR = 8      # MH_REPORT_PAIR: doubles per (world, step, slot) row of the contact report (include/moby_hip_artic.h, "Contact report")
+
+
+def report_slots(model):
+    """nspheres + nboxes + npairs: the slots of the model's contact report (mh_artic_report_slots; host only)"""
+    n = _lib.load().mh_artic_report_slots(ctypes.byref(model))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
+def link_impulses(report, model):
+    """The net linear contact impulse on every link from rows of the contact report: (..., nslots, 8) -> (..., nj, 3), model-frame axes.  Entries
+    [2..4] of a slot's row are the impulse on the reference's geometry A: the link of a sphere or box on the plane, pair_a's link for a pair, whose
+    other link (pair_b's sphere) received the negative.  A static box (link -1) is skipped.  numpy arrays and torch tensors alike."""
+    ns, nb = model.nspheres, model.nboxes
+    assert report.shape[-2:] == (ns + nb + model.npairs, REPORT_PAIR), report.shape
+    out = (report.new_zeros if _is_tensor(report) else lambda sh: np.zeros(sh, dtype=report.dtype))(tuple(report.shape[:-2]) + (model.nj, 3))
+    terms = [(s, model.sphere_link[s], None) for s in range(ns)] + [(ns + b, model.box_link[b], None) for b in range(nb)]
+    for k in range(model.npairs):
+        a = model.box_link[model.pair_a[k]] if model.pair_kind[k] == MH_ARTIC_PAIR_BOX_SPHERE else model.sphere_link[model.pair_a[k]]
+        terms.append((ns + nb + k, a, model.sphere_link[model.pair_b[k]]))
+    for slot, la, lb in terms:
+        jv = report[..., slot, 2:5]
+        if la >= 0:
+            out[..., la, :] += jv
+        if lb is not None:
+            out[..., lb, :] -= jv
+    return out
 
 
 class mh_artic_drive(ctypes.Structure):
@@ -292,7 +321,9 @@ class ArticBatch:
     carried -- three Euler-like angles in the virtual joints, or a per-world pose (p, Q) the virtual joints are folded into after every step
     (include/moby_hip_artic.h, MH_ARTIC_BASE_POSE: no singularity at a quarter turn of the middle hinge).  "pose" folds q / qd as given."""
 
-    def __init__(self, model, q, qd, aux=None, base_coords="angles"):
+    def __init__(self, model, q, qd, aux=None, base_coords="angles", report=False):
+        """report=True: a batch of mh_artic_batch_create_report -- it steps through the report kernels and step(..., report=tensor) fills the
+        per-slot contact impulse report (include/moby_hip_artic.h, "Contact report")"""
         lib = _lib.load()
         self.model = model
         self.nj = model.nj
@@ -301,7 +332,9 @@ class ArticBatch:
         assert q.shape == (self.B, self.nj) and qd.shape == q.shape
         self.handle = ctypes.c_void_p()
         self._staged = None
-        _lib.check(lib.mh_artic_batch_create(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
+        self.report = bool(report)
+        _lib.check((lib.mh_artic_batch_create_report if report else lib.mh_artic_batch_create)(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
+        self.report_slots = report_slots(model)
         self.upload(q, qd, aux)
         if base_coords != "angles":
             self.set_base_coords(base_coords)
@@ -348,11 +381,18 @@ class ArticBatch:
             raise ValueError("expected a contiguous float64 tensor of shape %r on %s, got %s %r on %s" % (tuple(shape), self._device(), t.dtype, tuple(t.shape), t.device))
         return t.data_ptr()
 
-    def step(self, dt, nsteps=1, stream=None, drive=None):
+    def step(self, dt, nsteps=1, stream=None, drive=None, report=None):
         """nsteps x TimeSteppingSimulator::step(dt) in one launch on `stream` (a raw HIP stream handle; None = the null stream).
         drive: a Drive for this launch; None = the drive stored by set_drive (none: undriven).  A torch loop passes
-        torch.cuda.current_stream().cuda_stream here and to state_into, so that both run in order with its own kernels."""
+        torch.cuda.current_stream().cuda_stream here and to state_into, so that both run in order with its own kernels.
+        report: a float64 contiguous (B, nsteps, report_slots, 8) torch tensor on the batch's device that receives the launch's contact report
+        (a batch created with report=True only); None = nothing is written."""
         lib = _lib.load()
+        rp = None
+        if report is not None:
+            if not self.report:
+                raise ValueError("a report needs a batch created with report=True")
+            rp = self._tensor_ptr(report, (self.B, int(nsteps), self.report_slots, REPORT_PAIR))
         if self._staged is not None:               # numpy arrays staged by the previous launch: free them once it has read them
             import torch
             torch.cuda.synchronize(self._device())
@@ -371,7 +411,10 @@ class ArticBatch:
                     staged.append(a)
                 setattr(d, k, self._tensor_ptr(a, a.shape))
             self._staged = staged or None
-        _lib.check(lib.mh_artic_batch_step_driven(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d)))
+        if self.report:
+            _lib.check(lib.mh_artic_batch_step_report(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d), rp))
+        else:
+            _lib.check(lib.mh_artic_batch_step_driven(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d)))
 
     def set_drive(self, drive=None):
         """Store a Drive (host copies of its arrays on the device) for every later step(..., drive=None); None clears it."""

@@ -21,6 +21,12 @@
 //   MobyHip::set_ground_plane(io.model, normal, point_on_plane, /*epsilon*/ 0.0, /*mu_coulomb*/ 100.0);
 // step() then runs TimeSteppingSimulator::step in full: conservative advancement, mini-steps, contact + limit rows in one LCP.
 //
+// The contact report (include/moby_hip_artic.h, "Contact report": what ConstraintSimulator::constraint_post_callback_fn would see, reduced per
+// slot -- sphere on the plane, box on the plane, pair -- inside the step):
+//   MobyHip::BatchedArticulatedBody* r = MobyHip::BatchedArticulatedBody::with_report(model, B, q, qd);
+//   double* rows_dev;  hipMalloc(&rows_dev, sizeof(double) * B * n * r->report_slots() * MH_REPORT_PAIR);   // the caller owns the device array
+//   r->step_report(1e-3, n, rows_dev);             // row of world w, step s, slot k at rows_dev + ((w * n + s) * report_slots() + k) * MH_REPORT_PAIR
+//
 // Generalized coordinates / velocities are the joint positions / velocities in the model's joint order (parents first),
 // as get_generalized_coordinates_euler / get_generalized_velocity return them for a fixed-base RCArticulatedBody.
 #ifndef MOBY_HIP_ARTICULATED_ADAPTER_H
@@ -94,11 +100,20 @@ inline void set_ground_plane(mh_artic_model& m, const double normal[3], const do
 
 class BatchedArticulatedBody {
  public:
-  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd) : _nj(model.nj), _B(B), _ab(NULL), _dirty(false)
-  {
-    if (mh_artic_batch_create(&model, B, &_ab) != MH_OK) throw std::runtime_error(mh_last_error());
-    _q.assign(q, q + (size_t)B * _nj); _qd.assign(qd, qd + (size_t)B * _nj); _aux.resize((size_t)B);
-    if (mh_artic_batch_upload(_ab, _q.data(), _qd.data(), NULL) != MH_OK) throw std::runtime_error(mh_last_error());
+  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd) : _nj(model.nj), _B(B), _ab(NULL), _dirty(false), _nslots(-1)
+  { init(model, q, qd, false); }
+  /// A batch whose steps can report contact impulses (mh_artic_batch_create_report: it steps through the report kernels, whatever its geometry;
+  /// step() writes no rows).  The model needs at least one sphere, box or pair.
+  static BatchedArticulatedBody* with_report(const mh_artic_model& model, int B, const double* q, const double* qd)
+  { return new BatchedArticulatedBody(model, B, q, qd, true); }
+  /// nspheres + nboxes + npairs of a batch made by with_report: the rows per world and step
+  int report_slots() const { return _nslots; }
+  /// step(dt, nsteps) with the launch's rows written to report_dev, a DEVICE array of B x nsteps x report_slots() x MH_REPORT_PAIR doubles that the
+  /// caller owns (this header knows no HIP); the rows are written in the order of the null stream.  With the drive of set_drive when one is set.
+  double step_report(double dt, int nsteps, double* report_dev) {
+    if (_nslots < 0) throw std::runtime_error("step_report: the batch was not made by with_report");
+    if (mh_artic_batch_step_report(_ab, NULL, dt, nsteps, NULL, report_dev) != MH_OK) throw std::runtime_error(mh_last_error());
+    _dirty = true; return dt;
   }
   ~BatchedArticulatedBody() { if (_ab) mh_artic_batch_destroy(_ab); }
   void set_generalized_coordinates_euler(const double* q) { _q.assign(q, q + _q.size()); if (mh_artic_batch_upload(_ab, _q.data(), NULL, NULL) != MH_OK) throw std::runtime_error(mh_last_error()); }
@@ -122,8 +137,17 @@ class BatchedArticulatedBody {
  private:
   BatchedArticulatedBody(const BatchedArticulatedBody&);
   BatchedArticulatedBody& operator=(const BatchedArticulatedBody&);
+  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd, bool report) : _nj(model.nj), _B(B), _ab(NULL), _dirty(false), _nslots(-1)
+  { init(model, q, qd, report); }
+  void init(const mh_artic_model& model, const double* q, const double* qd, bool report)
+  {
+    if ((report ? mh_artic_batch_create_report(&model, _B, &_ab) : mh_artic_batch_create(&model, _B, &_ab)) != MH_OK) throw std::runtime_error(mh_last_error());
+    if (report) _nslots = mh_artic_report_slots(&model);
+    _q.assign(q, q + (size_t)_B * _nj); _qd.assign(qd, qd + (size_t)_B * _nj); _aux.resize((size_t)_B);
+    if (mh_artic_batch_upload(_ab, _q.data(), _qd.data(), NULL) != MH_OK) { mh_artic_batch_destroy(_ab); _ab = NULL; throw std::runtime_error(mh_last_error()); }
+  }
   void sync() { if (!_dirty) return; if (mh_artic_batch_download(_ab, _q.data(), _qd.data(), _aux.data()) != MH_OK) throw std::runtime_error(mh_last_error()); _dirty = false; }
-  int _nj, _B; mh_artic_batch* _ab; bool _dirty;
+  int _nj, _B; mh_artic_batch* _ab; bool _dirty; int _nslots;
   std::vector<double> _q, _qd; std::vector<mh_world_aux> _aux;
 };
 

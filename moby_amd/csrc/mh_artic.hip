@@ -2,18 +2,24 @@
 // kernels without link geometry beyond spheres (mh_artic_dev.h with no switch set).
 //
 // mh_artic_batch_step launches those kernels itself, hands a batch in pose coordinates to mh_artic_pose.hip and one whose step goes through a
-// geometry family to artic_geom_step below, the one router to the six geometry code objects (mh_artic_{box,pair,bsp}[_pose].hip);
-// mh_artic_batch_step_driven (mh_artic_drive.hip) calls the same router.
+// geometry family to artic_geom_step below, the one router to the eight geometry code objects (mh_artic_{box,pair,bsp,rp}[_pose].hip);
+// mh_artic_batch_step_driven (mh_artic_drive.hip) calls the same router, and so does mh_artic_batch_step_report, with the rows.
 #include "mh_artic_dev.h"
 
 // Every step of a batch whose family (artic_geom_family) is box, pair or box-sphere, undriven and driven: the family's checks, then the launcher
 // of that family in the batch's coordinates.  To add a family: its switch and token in two wrapper files, an enumerator, its precedence in
 // mh_artic_batch_create, and a case here.
-int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D)
+int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report)
 {
   namespace ar = mh::artic;
   const bool pose = ab->base_coords == MH_ARTIC_BASE_POSE;
   const mh_artic_family fam = artic_geom_family(ab);
+  if (fam == MH_ARTIC_FAM_RP) {                                    // the report kernels: the pair workspace, an LDS image of their own
+    if (!ab->d_ws || ab->ws_stride < ar::WS_PAIR) return fail(MH_ERR_INVALID_ARG, "the batch's workspace is not sized for the report kernels");
+    const size_t lds = pose ? artic_rp_pose_lds_bytes(ab->nj) : artic_rp_lds_bytes(ab->nj);
+    if (lds > 65536) return fail(MH_ERR_INVALID_ARG, "the report kernels' LDS image (%zu bytes) exceeds a workgroup's 64 KB", lds);
+    return pose ? artic_rp_pose_launch(ab, stream, dt, nsteps, D, report) : artic_rp_launch(ab, stream, dt, nsteps, D, report);
+  }
   if (fam == MH_ARTIC_FAM_BOX) {
     if (ab->d_ws && ab->ws_stride < ar::WS_BOX)                  // a sphere batch created before mh_debug_set(12, 1): its workspace has the sphere kernels' layout
       return fail(MH_ERR_INVALID_ARG, "mh_debug_set(12, 1) applies to batches created after it (their workspace is sized for the box kernels at create)");
@@ -44,7 +50,17 @@ int mh_artic_batch_destroy(mh_artic_batch* ab)
   return MH_OK;
 }
 
-int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out)
+int mh_artic_report_slots(const mh_artic_model* model)
+{
+  if (!model) return fail(MH_ERR_INVALID_ARG, "null model");
+  if (model->nspheres < 0 || model->nspheres > MH_ARTIC_MAX_SPHERES || model->nboxes < 0 || model->nboxes > MH_ARTIC_MAX_BOXES || model->npairs < 0 || model->npairs > MH_ARTIC_MAX_PAIRS)
+    return fail(MH_ERR_INVALID_ARG, "nspheres = %d, nboxes = %d, npairs = %d outside [0, %d], [0, %d], [0, %d]", model->nspheres, model->nboxes, model->npairs,
+                MH_ARTIC_MAX_SPHERES, MH_ARTIC_MAX_BOXES, MH_ARTIC_MAX_PAIRS);
+  return model->nspheres + model->nboxes + model->npairs;
+}
+
+// mh_artic_batch_create (report false) and mh_artic_batch_create_report (true): one text, the report only decides the family
+static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out, bool report)
 {
   namespace ar = mh::artic;
   if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
@@ -134,8 +150,14 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   for (int k = 0; k < model->npairs; k++) has_bsp = has_bsp || model->pair_kind[k] == MH_ARTIC_PAIR_BOX_SPHERE;
   const bool has_geom = model->nspheres > 0 || model->nboxes > 0;
   const bool use_bsp = has_bsp || nstatic > 0 || (has_geom && mh_g_debug_artic_bsp != 0);
-  const bool use_pair = use_bsp || model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
-  if (use_pair && artic_pair_lds_bytes(nj) > 65536) return fail(MH_ERR_INVALID_ARG, "the pair kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, artic_pair_lds_bytes(nj));
+  const bool use_rp = report || (use_bsp && mh_g_debug_artic_rp != 0);          // the report kernels hold all the work of the box-sphere kernels
+  if (report && model->nspheres + model->nboxes + model->npairs == 0) return fail(MH_ERR_INVALID_ARG, "a contact report needs geometry: the model has no sphere, box or pair (no slot)");
+  const bool use_pair = use_rp || use_bsp || model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
+  if (use_pair && !use_rp && artic_pair_lds_bytes(nj) > 65536) return fail(MH_ERR_INVALID_ARG, "the pair kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, artic_pair_lds_bytes(nj));
+  if (use_rp) {                                                     // this family's own image, in either coordinates (the batch may be switched to poses later)
+    const size_t lds = artic_rp_pose_lds_bytes(nj) > artic_rp_lds_bytes(nj) ? artic_rp_pose_lds_bytes(nj) : artic_rp_lds_bytes(nj);
+    if (lds > 65536) return fail(MH_ERR_INVALID_ARG, "the report kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, lds);
+  }
   if (model->cstab_max_iterations < 0) return fail(MH_ERR_INVALID_ARG, "cstab_max_iterations = %d < 0", model->cstab_max_iterations);
   if (model->nspheres > 0 || model->nboxes > 0) {
     const double* Rp = model->plane_R; const double nn = Rp[1]*Rp[1] + Rp[4]*Rp[4] + Rp[7]*Rp[7];
@@ -154,7 +176,8 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   { const int rc = init_pow10(); if (rc != MH_OK) return rc; }             // this code object's powers of ten, before its first launch on the device
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
-  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->family = use_bsp ? MH_ARTIC_FAM_BSP : use_pair ? MH_ARTIC_FAM_PAIR : model->nboxes > 0 ? MH_ARTIC_FAM_BOX : MH_ARTIC_FAM_NONE; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->family = use_rp ? MH_ARTIC_FAM_RP : use_bsp ? MH_ARTIC_FAM_BSP : use_pair ? MH_ARTIC_FAM_PAIR : model->nboxes > 0 ? MH_ARTIC_FAM_BOX : MH_ARTIC_FAM_NONE; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->report = report ? 1 : 0;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;
@@ -177,6 +200,9 @@ int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** o
   *out = ab;
   return MH_OK;
 }
+
+int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out) { return artic_batch_create(model, B, out, false); }
+int mh_artic_batch_create_report(const mh_artic_model* model, int B, mh_artic_batch** out) { return artic_batch_create(model, B, out, true); }
 
 int mh_artic_batch_upload(mh_artic_batch* ab, const double* q, const double* qd, const mh_world_aux* aux)
 {
@@ -227,6 +253,20 @@ int mh_artic_batch_step(mh_artic_batch* ab, void* stream, double dt, int nsteps)
                      (const ar::Model*)ab->d_model, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux);
   MH_HIP(hipGetLastError());
   return MH_OK;
+}
+
+int mh_artic_batch_step_report(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* drive, double* report_dev)
+{
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  if (!report_dev) return mh_artic_batch_step_driven(ab, stream, dt, nsteps, drive);   // (a report batch launches its kernels with nothing to write)
+  if (!ab->report) return fail(MH_ERR_INVALID_ARG, "a report needs a batch created by mh_artic_batch_create_report");
+  MH_ON_DEVICE(ab);
+  const mh_artic_drive& D = drive ? *drive : ab->drive;
+  if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
+  if (D.terms != 0) { const int rc = check_drive(&D, nsteps); if (rc != MH_OK) return rc; }
+  if (nsteps == 0) return MH_OK;
+  if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
+  return artic_geom_step(ab, stream, dt, nsteps, D.terms != 0 ? &D : nullptr, report_dev);
 }
 
 int mh_artic_batch_set_drive(mh_artic_batch* ab, const mh_artic_drive* host_drive)

@@ -41,6 +41,9 @@ constexpr int NINTS = 24;
 #endif
 struct LayC {
   int qsave, V, cp, C, XC, G, CL, Cv, Lv, MM, qq, QX, W, Yy, YXv, t2, imp, l, A, art, ints, total;
+#ifdef MH_ARTIC_REPORT_TU
+  int racc, rslot;      // the contact report (mh_artic_rp.hip): the contacts' accumulated (cn, cs, ct), laid out as imp; the contacts' slots, NCL ints beside clink
+#endif
   // The arrays that live across calls (qsave, V, the contact list, ints) and most temporaries sit behind the config-5 image; the
   // three largest temporaries (MM, the LU scratch A, the C X C' blocks G) go into the forward-dynamics arrays that are dead while
   // the impact handler runs (I6 .. Iv of mh_artic_dev.h's Lay: composite inertias, RNEA velocities / accelerations / forces --
@@ -53,6 +56,9 @@ struct LayC {
     Lv = o; o += NR; qq = o; o += NR;
     QX = o; o += NR * MT; W = o; o += MT * NR; Yy = o; o += MT * MT; YXv = o; o += MT; t2 = o; o += MT;
     imp = o; o += 3 * NS; l = o; o += NR; art = o; o += MH_LCP_MAX_N_WAVE /* Lemke's artificial column: up to 64 rows in the Drumwright-Shell LCP */; ints = o; o += NINTS;
+#ifdef MH_ARTIC_REPORT_TU
+    racc = o; o += 3 * NS; rslot = o; o += (NCL + 1) / 2;           // (in front of the rule below that moves G to the workspace: it counts them)
+#endif
     if (a + NR * NR <= a_end) { MM = a; a += NR * NR; } else { MM = o; o += NR * NR; }
     if (a + NR * NR <= a_end) { A = a; a += NR * NR; } else { A = o; o += NR * NR; }
 #ifdef MH_ARTIC_PAIR_TU
@@ -778,6 +784,9 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
       double acc = 0.0; for (int k = 0; k < nl; k++) acc = acc + CL[a * NS * NR + i * nl + k] * ll[k];
       cv = cv + acc;
       g[Z.W + lane] = cv;                                         // staged: W is dead
+#ifdef MH_ARTIC_REPORT_TU
+      g[Z.racc + a * NS + i] = g[Z.racc + a * NS + i] + imp[a * NS + i];   // contact_impulse += (cn, cs, ct) (ICH:298-327): every application adds what it applied
+#endif
     }
     if (lane >= LOFF && lane < LOFF + nl) {                           // L_v rows
       const int k = lane - LOFF;
@@ -933,6 +942,32 @@ MH_DEV void handle_impacts(const Model& M, const Lay& Y, const LayC& Z, double* 
   if (ballot(tol) != 0ull) status |= MH_WORLD_IMPACT_TOL;
 }
 
+#ifdef MH_ARTIC_REPORT_TU
+// The contact report (include/moby_hip_artic.h, "Contact report").  Folds the mini-step's contacts into the step's rows, where
+// ConstraintSimulator::constraint_post_callback_fn sees them (CSim:353): after handle_impacts returned without a throw, also when it returned early
+// (the contacts then count with zero impulse).  Lane k owns slot k (sphere, box or pair: at most 18) and walks the contact list in its order, so the
+// order of a row's additions is fixed and no lane reads what another wrote; the rows stay in global memory.  A contact the handler has no room for
+// (list index >= NS) has no accumulator and folds with zero impulse.
+MH_DEV void report_fold(const Model& M, const LayC& Z, const double* g, int nc, double* rep)
+{
+  const int lane = lane_id();
+  if (!rep || lane >= M.m.nspheres + M.bx.n + M.pr.n) return;
+  const int* rslot = reinterpret_cast<const int*>(g + Z.rslot);
+  const double* racc = g + Z.racc;
+  double* row = rep + MH_REPORT_PAIR * lane;
+  for (int c = 0; c < nc; c++) {
+    if (rslot[c] != lane) continue;
+    const bool has = c < NS;
+    const double cn = has ? racc[c] : 0.0, cs = has ? racc[NS + c] : 0.0, ct = has ? racc[2 * NS + c] : 0.0;
+    const double* p = g + Z.cp + 12 * c;
+    row[0] = row[0] + 1.0;
+    row[1] = row[1] + cn;
+    for (int k = 0; k < 3; k++) { const double jv = (p[3 + k] * cn + p[6 + k] * cs) + p[9 + k] * ct; row[2 + k] = row[2 + k] + jv; }
+    for (int k = 0; k < 3; k++) row[5 + k] = row[5 + k] + p[k] * cn;
+  }
+}
+#endif
+
 // TimeSteppingSimulator::do_mini_step (TSS:114-222); returns h (uniform).  MH_ARTIC_DRIVE_TU: the drive's row of step s (world b of B) is
 // evaluated after the position update, before the forward dynamics (precalc_fwd_dyn, Simulator.cpp:319-350)
 MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* g, double* ws, mh_world_aux* aux, WaveRand& rng, double dt, bool& kin_ok, int& status,
@@ -942,6 +977,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #endif
 #if defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
                            , const mh_artic_drive* Dp, int B, int b, int s
+#endif
+#ifdef MH_ARTIC_REPORT_TU
+                           , double* rep                        // this world's rows of step s in the caller's report, or NULL
 #endif
                            )
 {
@@ -995,6 +1033,10 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
   // find_unilateral_constraints (CSim:488-537): R, x, S of the current q are in LDS (kin_inertia inside the dynamics call)
   int* ints = reinterpret_cast<int*>(g + Z.ints);
   int nc = 0;
+#ifdef MH_ARTIC_REPORT_TU
+  int* rslot = reinterpret_cast<int*>(g + Z.rslot);
+  for (int e = lane; e < 3 * NS; e += 64) g[Z.racc + e] = 0.0;     // a new constraint list: no contact has received an impulse yet
+#endif
   for (int s = 0; s < m.nspheres; s++) {
     MH_SKIP_MASKED(M, s)
     double cp[3]; sphere_in_plane(m, Y, g, s, cp);
@@ -1007,6 +1049,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
         for (int k = 0; k < 3; k++) { c[k] = p[k]; c[3 + k] = n[k]; c[6 + k] = sv[k]; c[9 + k] = tv[k]; }
         ints[I_LINK + nc] = m.sphere_link[s];
         MH_SET_LINKB(nc, -1)
+#ifdef MH_ARTIC_REPORT_TU
+        rslot[nc] = s;
+#endif
       }
       nc++;
     }
@@ -1025,6 +1070,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
         for (int c2 = 0; c2 < 3; c2++) { c[c2] = v[c2]; c[3 + c2] = n[c2]; c[6 + c2] = sv[c2]; c[9 + c2] = tv[c2]; }
         ints[I_LINK + nc] = M.bx.link[k];
         MH_SET_LINKB(nc, -1)
+#ifdef MH_ARTIC_REPORT_TU
+        rslot[nc] = m.nspheres + k;
+#endif
       }
       nc++;
     }
@@ -1049,6 +1097,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
       ints[I_LINK + nc] = m.sphere_link[M.pr.a[k]];
 #endif
       ints[I_LINKB + nc] = m.sphere_link[M.pr.b[k]];
+#ifdef MH_ARTIC_REPORT_TU
+      rslot[nc] = m.nspheres + M.bx.n + k;
+#endif
     }
     nc++;
   }
@@ -1057,6 +1108,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
   wave_sync();
   handle_impacts(M, Y, Z, g, ws, aux, rng, nc, status, solves, rows, pivs, bytes);
   wave_sync();
+#ifdef MH_ARTIC_REPORT_TU
+  if (!(status & MH_WORLD_LCP_FAILED)) report_fold(M, Z, g, nc, rep);   // a handler that threw leaves the step's rows as the earlier mini-steps left them
+#endif
   return h;
 }
 
@@ -1405,6 +1459,9 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #ifdef MH_ARTIC_POSE_TU
                                 , double* __restrict__ poseg
 #endif
+#ifdef MH_ARTIC_REPORT_TU
+                                , double* __restrict__ report   // B x nsteps x nslots x MH_REPORT_PAIR rows, or NULL: nothing is written, the steps are the same
+#endif
                                 )
 {
   extern __shared__ double g[];
@@ -1432,14 +1489,30 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   const int FROZEN = MH_WORLD_UNSUPPORTED | MH_WORLD_STALLED;
   bool kin_ok = false;
   wave_sync();
+#ifdef MH_ARTIC_REPORT_TU
+  // this world's rows: lane k owns slot k's row of every step and zeroes it before the step folds into it; the rows of steps that a world passed over
+  // or frozen never reaches are zeroed behind the loop
+  const int nslots = M.m.nspheres + M.bx.n + M.pr.n;
+  double* const rep0 = report ? report + (size_t)b * nsteps * nslots * MH_REPORT_PAIR : nullptr;
+  auto rep_zero = [&](int s) { if (rep0 && lane < nslots) for (int k = 0; k < MH_REPORT_PAIR; k++) rep0[((size_t)s * nslots + lane) * MH_REPORT_PAIR + k] = 0.0; };
+  int rep_done = 0;
+#endif
   for (int s = 0; s < nsteps; s++) {
+#ifdef MH_ARTIC_REPORT_TU
+    rep_zero(s); rep_done = s + 1;
+    double* const rep = rep0 ? rep0 + (size_t)s * nslots * MH_REPORT_PAIR : nullptr;
+#endif
     if (status & (FROZEN | MH_WORLD_LCP_FAILED)) break;           // as in the oracle: the reference would have thrown out of step() / never returned from it
     double h = 0.0; unsigned guard = 0;
     while (h < dt) {
 #ifdef MH_ARTIC_DRIVE_TU
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, D, B, b, s));
 #elif defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
+#ifdef MH_ARTIC_REPORT_TU
+      const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s, rep));
+#else
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s));
+#endif
 #else
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes));
 #endif
@@ -1466,6 +1539,9 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
     kin_ok = false;
 #endif
   }
+#ifdef MH_ARTIC_REPORT_TU
+  for (int s = rep_done; s < nsteps; s++) rep_zero(s);
+#endif
   if (lane < nj) { qg[(size_t)b * nj + lane] = g[Y.q + lane]; qdg[(size_t)b * nj + lane] = g[Y.qd + lane]; }
 #ifdef MH_ARTIC_POSE_TU
   pose_store(Y, g, poseg + 7 * (size_t)b);
@@ -1496,17 +1572,24 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #define MH_GEOM_POSE_PARAM
 #define MH_GEOM_POSE_ARG
 #endif
+#ifdef MH_ARTIC_REPORT_TU
+#define MH_GEOM_REPORT_PARAM , double* __restrict__ report
+#define MH_GEOM_REPORT_ARG , report
+#else
+#define MH_GEOM_REPORT_PARAM
+#define MH_GEOM_REPORT_ARG
+#endif
 #define MH_GEOM_KERNEL_X(fam, stab, drive) MH_GEOM_KERNEL_(fam, stab, drive)      // (the token is expanded before it is pasted)
 #define MH_GEOM_KERNEL(stab, drive) MH_GEOM_KERNEL_X(MH_ARTIC_GEOM, stab, drive)
 #define MH_GEOM_STAMP(STAB, stab) \
 __global__ __launch_bounds__(64) \
 void MH_GEOM_KERNEL(stab, )(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg, \
-                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg MH_GEOM_POSE_PARAM) \
-{ artic_contacts_body<STAB>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr MH_GEOM_POSE_ARG); } \
+                            mh_world_aux* __restrict__ auxg, double* __restrict__ wsg MH_GEOM_POSE_PARAM MH_GEOM_REPORT_PARAM) \
+{ artic_contacts_body<STAB>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, nullptr MH_GEOM_POSE_ARG MH_GEOM_REPORT_ARG); } \
 __global__ __launch_bounds__(64) \
 void MH_GEOM_KERNEL(stab, _drive)(const Model* __restrict__ Mg, int B, double dt, int nsteps, double* __restrict__ qg, double* __restrict__ qdg, \
-                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg MH_GEOM_POSE_PARAM, mh_artic_drive D) \
-{ artic_contacts_body<STAB>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D MH_GEOM_POSE_ARG); }
+                                  mh_world_aux* __restrict__ auxg, double* __restrict__ wsg MH_GEOM_POSE_PARAM, mh_artic_drive D MH_GEOM_REPORT_PARAM) \
+{ artic_contacts_body<STAB>(Mg, B, dt, nsteps, qg, qdg, auxg, wsg, &D MH_GEOM_POSE_ARG MH_GEOM_REPORT_ARG); }
 MH_GEOM_STAMP(false, )
 MH_GEOM_STAMP(true, _stab)
 #elif !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_POSE_TU)

@@ -1,10 +1,10 @@
 // mh_artic_dev.h -- many-worlds stepper for fixed-base articulated bodies (include/moby_hip_artic.h; BASELINE config 5): the device code and
 // the host declarations every articulated translation unit shares.
 //
-// Each of the nine articulated .hip files sets its switches (MH_ARTIC_DRIVE_TU, MH_ARTIC_POSE_TU, MH_ARTIC_BOX_TU, MH_ARTIC_PAIR_TU,
-// MH_ARTIC_BSP_TU; a geometry file also its family token MH_ARTIC_GEOM) and includes this header once: the switches pick the kernels of that
-// code object.  mh_artic.hip (no switch) holds the C entry points and the router to the geometry kernels, mh_artic_drive.hip and
-// mh_artic_pose.hip their own entry points; a geometry file (mh_artic_{box,pair,bsp}[_pose].hip) holds nothing else: its launcher is stamped at
+// Each of the eleven articulated .hip files sets its switches (MH_ARTIC_DRIVE_TU, MH_ARTIC_POSE_TU, MH_ARTIC_BOX_TU, MH_ARTIC_PAIR_TU,
+// MH_ARTIC_BSP_TU, MH_ARTIC_REPORT_TU; a geometry file also its family token MH_ARTIC_GEOM) and includes this header once: the switches pick the
+// kernels of that code object.  mh_artic.hip (no switch) holds the C entry points and the router to the geometry kernels, mh_artic_drive.hip and
+// mh_artic_pose.hip their own entry points; a geometry file (mh_artic_{box,pair,bsp,rp}[_pose].hip) holds nothing else: its launcher is stamped at
 // the end of this header.
 //
 // One wavefront per world. Per step (TimeSteppingSimulator::do_mini_step with no collision geometry, TSS:114-222):
@@ -1046,12 +1046,14 @@ void k_artic_pose_fold(int B, int nj, double* __restrict__ qg, double* __restric
 enum mh_artic_family { MH_ARTIC_FAM_NONE = 0,  // no geometry, or spheres against the plane: the kernels of mh_artic.hip / mh_artic_drive.hip / mh_artic_pose.hip
                        MH_ARTIC_FAM_BOX,       // box primitives (mh_artic_box.hip)
                        MH_ARTIC_FAM_PAIR,      // sphere pairs between links or a plane mask (mh_artic_pair.hip), and every model with geometry created under mh_debug_set(13, 1)
-                       MH_ARTIC_FAM_BSP };     // a box-sphere pair or a static box (mh_artic_bsp.hip), and every model with geometry created under mh_debug_set(14, 1)
+                       MH_ARTIC_FAM_BSP,       // a box-sphere pair or a static box (mh_artic_bsp.hip), and every model with geometry created under mh_debug_set(14, 1)
+                       MH_ARTIC_FAM_RP };      // the contact report (mh_artic_rp.hip): every batch of mh_artic_batch_create_report, and one that would take BSP created under mh_debug_set(19, 1)
 
 struct mh_artic_batch {
   int device;                // the HIP device the batch lives on (current at create); every entry point runs there (MH_ON_DEVICE)
   int B, nj, nspheres, cstab, algorithm;
   mh_artic_family family;    // fixed at create, and with it the workspace layout (artic_geom_family: what a step goes through)
+  int report;                // created by mh_artic_batch_create_report: mh_artic_batch_step_report may hand it rows to write
   mh::artic::Model* d_model;
   double* d_q; double* d_qd; mh_world_aux* d_aux;
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
@@ -1076,7 +1078,8 @@ static inline mh_artic_family artic_geom_family(const mh_artic_batch* ab)
 }
 // the router (mh_artic.hip): every step of a batch whose family is not MH_ARTIC_FAM_NONE -- the family's workspace and LDS checks, then the
 // launcher of that family and of the batch's coordinates; D as artic_pose_step's
-int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
+// report: the rows a batch of the report family writes (NULL: none; every other family ignores it)
+int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report = nullptr);
 // the launchers, one per geometry code object (stamped at the end of this header): nothing but the launch of one of its four kernels
 #define MH_ARTIC_LAUNCHER(name) int name(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D)
 MH_ARTIC_LAUNCHER(artic_box_launch);  MH_ARTIC_LAUNCHER(artic_box_pose_launch);
@@ -1085,6 +1088,12 @@ MH_ARTIC_LAUNCHER(artic_bsp_launch);  MH_ARTIC_LAUNCHER(artic_bsp_pose_launch);
 // the LDS image of the pair layout at nj joints in angle coordinates, in bytes (mh_artic_pair.hip: the contact list's length differs per code object;
 // the box-sphere kernels' image is the same).  mh_artic_batch_create and the router refuse a model whose image would not fit a workgroup
 size_t artic_pair_lds_bytes(int nj);
+// the report family's launchers take the rows too, and its LDS image is its own (the pair layout plus the accumulators and the slot table), per
+// coordinate kind: mh_artic_rp.hip and mh_artic_rp_pose.hip each export theirs
+#define MH_ARTIC_REPORT_LAUNCHER(name) int name(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report)
+MH_ARTIC_REPORT_LAUNCHER(artic_rp_launch); MH_ARTIC_REPORT_LAUNCHER(artic_rp_pose_launch);
+size_t artic_rp_lds_bytes(int nj);
+size_t artic_rp_pose_lds_bytes(int nj);
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
 static int check_drive(const mh_artic_drive* d, int nsteps)
@@ -1125,7 +1134,13 @@ static int init_pow10()
 #define MH_GEOM_POSE_PTR
 #endif
 #define MH_GEOM_LAUNCHER(fam) MH_GEOM_LAUNCHER_(fam)
+#ifdef MH_ARTIC_REPORT_TU
+#define MH_GEOM_REPORT_PTR , report
+MH_ARTIC_REPORT_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
+#else
+#define MH_GEOM_REPORT_PTR
 MH_ARTIC_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
+#endif
 {
   namespace ar = mh::artic;
   if (init_pow10() != MH_OK) return MH_ERR_HIP;
@@ -1133,13 +1148,18 @@ MH_ARTIC_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
   const size_t lds = ar::lds_bytes_contacts(ab->nj);
   const hipStream_t st = (hipStream_t)stream;
   if (D && D->terms != 0) hipLaunchKernelGGL(ab->cstab ? ar::MH_GEOM_KERNEL(_stab, _drive) : ar::MH_GEOM_KERNEL(, _drive), dim3(ab->B), dim3(64), lds, st,
-                                             M, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws MH_GEOM_POSE_PTR, *D);
+                                             M, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws MH_GEOM_POSE_PTR, *D MH_GEOM_REPORT_PTR);
   else hipLaunchKernelGGL(ab->cstab ? ar::MH_GEOM_KERNEL(_stab, ) : ar::MH_GEOM_KERNEL(, ), dim3(ab->B), dim3(64), lds, st,
-                          M, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws MH_GEOM_POSE_PTR);
+                          M, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws MH_GEOM_POSE_PTR MH_GEOM_REPORT_PTR);
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
 #if defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_BSP_TU) && !defined(MH_ARTIC_POSE_TU)
 size_t artic_pair_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
+#endif
+#if defined(MH_ARTIC_REPORT_TU) && defined(MH_ARTIC_POSE_TU)
+size_t artic_rp_pose_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
+#elif defined(MH_ARTIC_REPORT_TU)
+size_t artic_rp_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
 #endif
 #endif

@@ -1,6 +1,7 @@
 """Same-instructions check of the world code objects: compiles every moby_amd/csrc/mh_world_*.hip of two source trees to gfx950 assembly with the
 Makefile's HIPFLAGS (+ --cuda-device-only -S) and reports, per object and per function, identical or different with both code lengths.  No GPU needed.
-usage: python tools/world_asm_diff.py OLD_TREE NEW_TREE [--out DIR] [--jobs N]     (e.g. OLD_TREE from `git worktree add` or `git archive` of the parent)
+usage: python tools/world_asm_diff.py OLD_TREE NEW_TREE [--out DIR] [--jobs N] [--glob PATTERN]     (e.g. OLD_TREE from `git worktree add` or `git archive` of the parent)
+--glob picks other code objects of moby_amd/csrc by file name (default mh_world_*.hip; 'mh_artic*.hip' for the articulated stepper's).
 --out keeps the .s files (DIR/old, DIR/new; an existing .s is reused, so delete it after editing its tree).  Exit status 1 if any object differs."""
 import argparse, concurrent.futures, glob, os, re, subprocess, sys, tempfile
 
@@ -8,10 +9,10 @@ def flags(tree):
     mk = open(os.path.join(tree, "moby_amd", "csrc", "Makefile")).read()
     return re.search(r"^HIPFLAGS \?= (.*)$", mk, re.M).group(1).split(), re.search(r"^HIPCC \?= (.*)$", mk, re.M).group(1)
 
-def assemble(tree, out):
+def assemble(tree, out, pattern):
     os.makedirs(out, exist_ok=True)
     fl, hipcc = flags(tree)
-    src = sorted(glob.glob(os.path.join(tree, "moby_amd", "csrc", "mh_world_*.hip")))
+    src = sorted(glob.glob(os.path.join(tree, "moby_amd", "csrc", pattern)))
     return [(s, os.path.join(out, os.path.basename(s)[:-4] + ".s"), [hipcc] + fl + ["--cuda-device-only", "-S"]) for s in src]
 
 def functions(path):
@@ -32,9 +33,10 @@ def functions(path):
 
 ap = argparse.ArgumentParser()
 ap.add_argument("old"); ap.add_argument("new"); ap.add_argument("--out"); ap.add_argument("--jobs", type=int, default=8)
+ap.add_argument("--glob", default="mh_world_*.hip")
 a = ap.parse_args()
 out = a.out or tempfile.mkdtemp(prefix="world_asm_")
-jobs = assemble(a.old, os.path.join(out, "old")) + assemble(a.new, os.path.join(out, "new"))
+jobs = assemble(a.old, os.path.join(out, "old"), a.glob) + assemble(a.new, os.path.join(out, "new"), a.glob)
 with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
     list(ex.map(lambda j: os.path.exists(j[1]) or subprocess.check_call(j[2] + ["-o", j[1], j[0]], cwd=os.path.dirname(j[0])), jobs))
 bad = 0
