@@ -314,6 +314,9 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                             key 19: articulated batches that would take the box-sphere kernels stepped by the contact-report kernels, mh_artic_rp*.hip, with a
                                                    NULL report (1, for batches created after it; default 0: only batches of mh_artic_batch_create_report; for A/B runs;
                                                    include/moby_hip_artic.h, "Contact report").
+                                            key 20: articulated batches that would take the contact-report kernels stepped by the per-world-parameters kernels, mh_artic_pw*.hip, with
+                                                   B images all equal to the model (1, for batches created after it; default 0: only batches of mh_artic_batch_create_params;
+                                                   for A/B runs; include/moby_hip_artic.h, "Per-world parameters").
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);
@@ -450,7 +453,8 @@ int mh_world_step_batch_statics(const mh_scene* scene, const mh_world_forces* fo
  * equal to the scene (A/B runs; no result changes).
  * NOT built: per-world parameters inside the small and wheel variants (such batches take the objects above); per-world topology (nb, geometry types,
  * enabled pairs, cp_nk, number or type of statics); per-world spoke radius or count; statics that move within a launch; per-world parameters in the
- * large-world (moby_hip_stack.h) and articulated steppers; per-world drag coefficients (mh_world_forces stays the scene's). */
+ * large-world stepper (moby_hip_stack.h; the articulated stepper has its own record, moby_hip_artic.h "Per-world parameters"); per-world drag
+ * coefficients (mh_world_forces stays the scene's). */
 /* (no existing layout changes, so MH_VERSION stays 102; a caller that needs to know tests this macro) */
 #define MH_WORLD_PARAMS 1
 typedef struct mh_world_params {

@@ -323,6 +323,78 @@ int mh_artic_batch_create_report(const mh_artic_model* model, int B, mh_artic_ba
  * report_dev != NULL on a batch not created by mh_artic_batch_create_report.  mh_artic_batch_step and _step_driven take such a batch and write no report. */
 int mh_artic_batch_step_report(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* drive, double* report_dev);
 
+/* Per-world parameters.  Every world of a batch steps its own VALUES of one shared model: a range of robots (masses, centres of mass, inertias, link
+ * lengths, joint limits, foot radii, friction, the slope of the ground, the place of the crate) in one launch.  The rule: world w of a batch created
+ * with records is stepped exactly as a batch of the model with record w written into it would step it -- state, aux record, base pose and report rows,
+ * bit for bit.  A record holds doubles only, with the model's indexing, so nothing in it can become an index.
+ * The TOPOLOGY stays the model's for every world: nj, parent, jtype, algorithm, floating_base; the counts and link indices of spheres and boxes (a
+ * static box stays static); the pair lists and kinds, sphere_no_plane; cp_nk, min_step_size, contact_dist_thresh, cstab_max_iterations, cstab_eps; and
+ * WHICH limits are finite (a bound with |value| < DBL_MAX) -- a record may move a finite limit but may not add or remove one, so the stabiliser's row
+ * count and the pose-coordinate refusal stay decisions of the model.  The impact model is chosen per world from its own cp_mu_coulomb (>= 100: no-slip,
+ * below: Drumwright-Shell), as the kernel does from the model's; worlds on either side may share a batch, and so for such a batch the friction polygon
+ * is filled from cp_nk and cp_nk is validated whatever the model's own mu, and the solver workspace is always allocated.
+ * In pose coordinates (MH_ARTIC_BASE_POSE) a record's trel[0] and Rrel[3] are NOT read by a step: the per-world pose stands in for them.
+ * mh_artic_batch_set_base_coords takes each world's start pose from its own record (p = trel[0], Q of Rrel[3]); a per-world start pose later is
+ * mh_artic_batch_set_base_pose.
+ * Such a batch steps through code objects of its own (mh_artic_pw.hip, mh_artic_pw_pose.hip: the report kernels with MH_ARTIC_PARAMS_TU, under which
+ * the step reads image w of B) whatever its geometry -- also a model with no geometry at all, the robot alone with randomised masses; the contact
+ * kernels step an empty contact list as the plain kernels do.  Report rows are written only when the batch was created with MH_ARTIC_CREATE_REPORT.
+ * fwd_dyn, link_poses, jacobian and set_base_coords read each world's own image.  Every other batch launches what it launched.  Key 20 of mh_debug_set
+ * sends batches that would take the report kernels through these objects with B images equal to the model (A/B runs; no result changes).
+ * NOT built: per-world topology; adding or removing limits; per-world cp_nk; the record in the large-world stepper (moby_hip_stack.h). */
+/* (no existing layout changes, so MH_VERSION stays as it is; a caller that needs to know tests this macro) */
+#define MH_ARTIC_PARAMS 1
+#define MH_ARTIC_CREATE_REPORT 1     /* flags of mh_artic_batch_create_params: the batch is a report batch too (mh_artic_batch_create_report) */
+typedef struct mh_artic_params {
+  double Rrel[MH_ARTIC_MAX_JOINTS][9];
+  double trel[MH_ARTIC_MAX_JOINTS][3];
+  double axis[MH_ARTIC_MAX_JOINTS][3];
+  double com[MH_ARTIC_MAX_JOINTS][3];
+  double inertia[MH_ARTIC_MAX_JOINTS][9];
+  double mass[MH_ARTIC_MAX_JOINTS];
+  double lolimit[MH_ARTIC_MAX_JOINTS];
+  double hilimit[MH_ARTIC_MAX_JOINTS];
+  double limit_restitution[MH_ARTIC_MAX_JOINTS];
+  double gravity[3];
+  double sphere_center[MH_ARTIC_MAX_SPHERES][3];
+  double sphere_radius[MH_ARTIC_MAX_SPHERES];
+  double plane_R[9];
+  double plane_o[3];
+  double cp_epsilon, cp_mu_coulomb, cp_mu_viscous, cp_compliance;
+  double box_center[MH_ARTIC_MAX_BOXES][3];
+  double box_R[MH_ARTIC_MAX_BOXES][9];
+  double box_len[MH_ARTIC_MAX_BOXES][3];
+} mh_artic_params;
+/* host only: the record that reproduces the model (every field above copied from it) */
+void mh_artic_params_from_model(const mh_artic_model* model, mh_artic_params* out);
+/* mh_artic_batch_create with a record per world (HOST pointer, B records; NULL: every record = the model); flags: MH_ARTIC_CREATE_REPORT or 0.
+ * First every refusal of mh_artic_batch_create (and of _create_report with the flag), unchanged; then every record is validated as the model's values
+ * are, through the same checks: mass >= 0 and every joint moves mass; unit axes; lolimit <= hilimit and the model's pattern of finite limits; on a
+ * floating base the virtual joints' fixed entries equal the layout; with geometry sphere radii > 0, box edges finite and > 0, box_R orthonormal, the
+ * plane's +Y column a unit vector, the four contact parameters finite and >= 0; gravity finite.  The last two are stricter than the model's own
+ * checks (mh_artic_batch_create takes an infinite cp_mu_coulomb or a non-finite gravity), and they hold for host == NULL too: such a model is then
+ * refused through its record, as world 0.  MH_ERR_INVALID_ARG with a message that names the world and the field; all of it runs before the device is
+ * looked for. */
+int mh_artic_batch_create_params(const mh_artic_model* model, const mh_artic_params* host, int B, int flags, mh_artic_batch** out);
+/* Replaces the records of worlds first .. first + count - 1 (HOST pointer, `count` records), validated as at create; synchronous (after the work in
+ * flight on the device).  MH_ERR_INVALID_ARG: a batch not created by mh_artic_batch_create_params, a range outside the batch, a refused record (none
+ * is then written). */
+int mh_artic_batch_set_params(mh_artic_batch* ab, const mh_artic_params* host, int first, int count);
+/* The same from DEVICE memory, by a small kernel on `stream` that scatters the records into the worlds' images: ordered with the launches of that
+ * stream, for a caller that randomises on the GPU between launches.  The records are NOT validated.  What a bad value does, as read from the step
+ * kernels: nothing outside the world's own memory is touched, because a record holds doubles only and no double of the image is ever converted to
+ * an index, a count or a loop bound -- every index, count and bound of the step comes from the shared topology (nj, parent, the ancestor masks, the
+ * sphere, box and pair lists, cp_nk, cstab_max_iterations) or from integers the kernel computes itself (contact and limit counts, capped by
+ * MH_NOSLIP_MAX / MH_LCP_MAX_N_WAVE, beyond which the world gets MH_WORLD_UNSUPPORTED), and every loop a non-finite value can reach ends by a cap
+ * (MH_CA_HARD_CAP in the conservative-advancement loop, the 100000 mini-step guard, the stabiliser's iteration count -- cstab_max_iterations and
+ * MH_CSTAB_HARD_CAP --, Ridders' 25 iterations, the backtracking that shrinks its step by 0.6 down to NEAR_ZERO, the solvers' pivot caps) or by a
+ * comparison that is false for NaN (h < dt, max violation < cstab_eps).  That world's state goes
+ * non-finite or it gets a status bit (MH_WORLD_STALLED, MH_WORLD_LCP_FAILED, MH_WORLD_UNSUPPORTED); the other worlds are not affected.  A record
+ * that adds or removes a finite limit is not refused here: the limit rows follow the record (the kernel tests each bound against DBL_MAX itself, and
+ * the row tables are sized for two rows per joint), but results then no longer follow the rule above for the shared model's pattern.  In pose
+ * coordinates trel[0] and Rrel[3] are not read.  MH_ERR_INVALID_ARG: a batch not created by mh_artic_batch_create_params, a range outside the batch. */
+int mh_artic_batch_set_params_dev(mh_artic_batch* ab, void* stream, const mh_artic_params* dev, int first, int count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,10 @@ SYMBOLS = {
     "mh_artic_report_slots": (_i, [_vp]),
     "mh_artic_batch_create_report": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
     "mh_artic_batch_step_report": (_i, [_vp, _vp, _d, _i, _vp, _vp]),
+    "mh_artic_params_from_model": (None, [_vp, _vp]),
+    "mh_artic_batch_create_params": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(_vp)]),
+    "mh_artic_batch_set_params": (_i, [_vp, _vp, _i, _i]),
+    "mh_artic_batch_set_params_dev": (_i, [_vp, _vp, _vp, _i, _i]),
 }
 
 _lib = None

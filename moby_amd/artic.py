@@ -78,6 +78,43 @@ def link_impulses(report, model):
     return out
 
 
+_D = ctypes.c_double
+
+
+class mh_artic_params(ctypes.Structure):
+    """One world's values of the shared model (include/moby_hip_artic.h, "Per-world parameters"): doubles only, the model's indexing"""
+    _fields_ = [("Rrel", (_D * 9) * _NJ), ("trel", (_D * 3) * _NJ), ("axis", (_D * 3) * _NJ), ("com", (_D * 3) * _NJ), ("inertia", (_D * 9) * _NJ),
+                ("mass", _D * _NJ), ("lolimit", _D * _NJ), ("hilimit", _D * _NJ), ("limit_restitution", _D * _NJ), ("gravity", _D * 3),
+                ("sphere_center", (_D * 3) * _NS), ("sphere_radius", _D * _NS), ("plane_R", _D * 9), ("plane_o", _D * 3),
+                ("cp_epsilon", _D), ("cp_mu_coulomb", _D), ("cp_mu_viscous", _D), ("cp_compliance", _D),
+                ("box_center", (_D * 3) * _NB), ("box_R", (_D * 9) * _NB), ("box_len", (_D * 3) * _NB)]
+
+
+# the same layout as a numpy record: params["mass"][w, i], params["box_len"][w, k, c], params["cp_mu_coulomb"][w]
+PARAMS_DTYPE = np.dtype([("Rrel", "f8", (_NJ, 9)), ("trel", "f8", (_NJ, 3)), ("axis", "f8", (_NJ, 3)), ("com", "f8", (_NJ, 3)), ("inertia", "f8", (_NJ, 9)),
+                         ("mass", "f8", (_NJ,)), ("lolimit", "f8", (_NJ,)), ("hilimit", "f8", (_NJ,)), ("limit_restitution", "f8", (_NJ,)), ("gravity", "f8", (3,)),
+                         ("sphere_center", "f8", (_NS, 3)), ("sphere_radius", "f8", (_NS,)), ("plane_R", "f8", (9,)), ("plane_o", "f8", (3,)),
+                         ("cp_epsilon", "f8"), ("cp_mu_coulomb", "f8"), ("cp_mu_viscous", "f8"), ("cp_compliance", "f8"),
+                         ("box_center", "f8", (_NB, 3)), ("box_R", "f8", (_NB, 9)), ("box_len", "f8", (_NB, 3))])
+PARAMS_DOUBLES = PARAMS_DTYPE.itemsize // 8      # a record as a row of doubles (a (count, PARAMS_DOUBLES) tensor for set_params_dev)
+MH_ARTIC_CREATE_REPORT = 1
+
+
+def make_params(model, B):
+    """B records, every one equal to the model (what mh_artic_params_from_model writes): the array to vary and hand to ArticBatch(params=...)"""
+    p = np.zeros(B, dtype=PARAMS_DTYPE)
+    for name in PARAMS_DTYPE.names:
+        p[name] = np.array(getattr(model, name), dtype=np.float64).reshape(PARAMS_DTYPE[name].shape)
+    return p
+
+
+def _records(params, count=None):
+    p = np.ascontiguousarray(params)
+    if p.dtype != PARAMS_DTYPE or p.ndim != 1 or (count is not None and p.shape[0] != count):
+        raise ValueError("expected %s records of artic.PARAMS_DTYPE (artic.make_params), got %r %r" % ("" if count is None else count, p.dtype, p.shape))
+    return p
+
+
 class mh_artic_drive(ctypes.Structure):
     _fields_ = [("terms", ctypes.c_int), ("rows", ctypes.c_int), ("kp", ctypes.c_void_p), ("kv", ctypes.c_void_p),
                 ("q_des", ctypes.c_void_p), ("qd_des", ctypes.c_void_p), ("tau_ff", ctypes.c_void_p)]
@@ -321,8 +358,11 @@ class ArticBatch:
     carried -- three Euler-like angles in the virtual joints, or a per-world pose (p, Q) the virtual joints are folded into after every step
     (include/moby_hip_artic.h, MH_ARTIC_BASE_POSE: no singularity at a quarter turn of the middle hinge).  "pose" folds q / qd as given."""
 
-    def __init__(self, model, q, qd, aux=None, base_coords="angles", report=False):
-        """report=True: a batch of mh_artic_batch_create_report -- it steps through the report kernels and step(..., report=tensor) fills the
+    def __init__(self, model, q, qd, aux=None, base_coords="angles", report=False, params=None):
+        """params: B records of PARAMS_DTYPE (make_params), one per world, or True for records that all equal the model -- a batch of
+        mh_artic_batch_create_params: world w steps the model with record w written into it (include/moby_hip_artic.h, "Per-world parameters");
+        set_params / set_params_dev replace records later.
+        report=True: a batch of mh_artic_batch_create_report -- it steps through the report kernels and step(..., report=tensor) fills the
         per-slot contact impulse report (include/moby_hip_artic.h, "Contact report")"""
         lib = _lib.load()
         self.model = model
@@ -333,11 +373,31 @@ class ArticBatch:
         self.handle = ctypes.c_void_p()
         self._staged = None
         self.report = bool(report)
-        _lib.check((lib.mh_artic_batch_create_report if report else lib.mh_artic_batch_create)(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
+        self.params = params is not None
+        if self.params:
+            p = None if params is True else _records(params, self.B)
+            _lib.check(lib.mh_artic_batch_create_params(ctypes.byref(model), None if p is None else p.ctypes.data, self.B, MH_ARTIC_CREATE_REPORT if report else 0, ctypes.byref(self.handle)))
+        else:
+            _lib.check((lib.mh_artic_batch_create_report if report else lib.mh_artic_batch_create)(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
         self.report_slots = report_slots(model)
         self.upload(q, qd, aux)
         if base_coords != "angles":
             self.set_base_coords(base_coords)
+
+    def set_params(self, records, first=0):
+        """Replace the records of worlds first .. first + len(records) - 1 (PARAMS_DTYPE), validated as at create; synchronous.  A refused record
+        leaves every world as it was."""
+        p = _records(records)
+        _lib.check(_lib.load().mh_artic_batch_set_params(self.handle, p.ctypes.data, int(first), int(p.shape[0])))
+
+    def set_params_dev(self, records_t, first=0, stream=None):
+        """The same from a float64 contiguous (count, PARAMS_DOUBLES) torch tensor on the batch's device -- record rows laid out as PARAMS_DTYPE --
+        scattered by a kernel on `stream`, in order with the launches of that stream.  NOT validated (include/moby_hip_artic.h says what a bad
+        value does)."""
+        import torch
+        if records_t.dtype != torch.float64 or records_t.dim() != 2:
+            raise ValueError("expected a contiguous float64 tensor of shape (count, %d) on %s, got %s %r on %s" % (PARAMS_DOUBLES, self._device(), records_t.dtype, tuple(records_t.shape), records_t.device))
+        _lib.check(_lib.load().mh_artic_batch_set_params_dev(self.handle, stream, self._tensor_ptr(records_t, (records_t.shape[0], PARAMS_DOUBLES)), int(first), int(records_t.shape[0])))
 
     def set_base_coords(self, coords):
         """"pose" (or MH_ARTIC_BASE_POSE): switch to pose coordinates -- every world's pose from the model, the resident q / qd folded into it.

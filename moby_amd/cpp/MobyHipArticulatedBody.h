@@ -106,6 +106,14 @@ class BatchedArticulatedBody {
   /// step() writes no rows).  The model needs at least one sphere, box or pair.
   static BatchedArticulatedBody* with_report(const mh_artic_model& model, int B, const double* q, const double* qd)
   { return new BatchedArticulatedBody(model, B, q, qd, true); }
+  /// A batch whose copies each step their own VALUES of the model (mh_artic_batch_create_params; include/moby_hip_artic.h, "Per-world parameters"):
+  /// params holds B records (NULL: every record = the model; mh_artic_params_from_model writes the one that reproduces a model), copy w steps as
+  /// a batch of the model with record w written into it would.  report = true makes it a report batch too (step_report).  The topology -- joints,
+  /// geometry lists, which limits are finite -- stays the model's.
+  static BatchedArticulatedBody* with_params(const mh_artic_model& model, const mh_artic_params* params, int B, const double* q, const double* qd, bool report = false)
+  { return new BatchedArticulatedBody(model, B, q, qd, report, true, params); }
+  /// Replaces the records of copies first .. first + count - 1 (HOST records, validated; a refused record leaves every copy as it was)
+  void set_params(const mh_artic_params* params, int first, int count) { if (mh_artic_batch_set_params(_ab, params, first, count) != MH_OK) throw std::runtime_error(mh_last_error()); }
   /// nspheres + nboxes + npairs of a batch made by with_report: the rows per world and step
   int report_slots() const { return _nslots; }
   /// step(dt, nsteps) with the launch's rows written to report_dev, a DEVICE array of B x nsteps x report_slots() x MH_REPORT_PAIR doubles that the
@@ -137,11 +145,14 @@ class BatchedArticulatedBody {
  private:
   BatchedArticulatedBody(const BatchedArticulatedBody&);
   BatchedArticulatedBody& operator=(const BatchedArticulatedBody&);
-  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd, bool report) : _nj(model.nj), _B(B), _ab(NULL), _dirty(false), _nslots(-1)
-  { init(model, q, qd, report); }
-  void init(const mh_artic_model& model, const double* q, const double* qd, bool report)
+  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd, bool report, bool with_records = false, const mh_artic_params* params = NULL)
+    : _nj(model.nj), _B(B), _ab(NULL), _dirty(false), _nslots(-1)
+  { init(model, q, qd, report, with_records, params); }
+  void init(const mh_artic_model& model, const double* q, const double* qd, bool report, bool with_records = false, const mh_artic_params* params = NULL)
   {
-    if ((report ? mh_artic_batch_create_report(&model, _B, &_ab) : mh_artic_batch_create(&model, _B, &_ab)) != MH_OK) throw std::runtime_error(mh_last_error());
+    const int rc = with_records ? mh_artic_batch_create_params(&model, params, _B, report ? MH_ARTIC_CREATE_REPORT : 0, &_ab)
+                                : report ? mh_artic_batch_create_report(&model, _B, &_ab) : mh_artic_batch_create(&model, _B, &_ab);
+    if (rc != MH_OK) throw std::runtime_error(mh_last_error());
     if (report) _nslots = mh_artic_report_slots(&model);
     _q.assign(q, q + (size_t)_B * _nj); _qd.assign(qd, qd + (size_t)_B * _nj); _aux.resize((size_t)_B);
     if (mh_artic_batch_upload(_ab, _q.data(), _qd.data(), NULL) != MH_OK) { mh_artic_batch_destroy(_ab); _ab = NULL; throw std::runtime_error(mh_last_error()); }

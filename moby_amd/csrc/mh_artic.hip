@@ -2,9 +2,11 @@
 // kernels without link geometry beyond spheres (mh_artic_dev.h with no switch set).
 //
 // mh_artic_batch_step launches those kernels itself, hands a batch in pose coordinates to mh_artic_pose.hip and one whose step goes through a
-// geometry family to artic_geom_step below, the one router to the eight geometry code objects (mh_artic_{box,pair,bsp,rp}[_pose].hip);
+// geometry family to artic_geom_step below, the one router to the ten geometry code objects (mh_artic_{box,pair,bsp,rp,pw}[_pose].hip);
 // mh_artic_batch_step_driven (mh_artic_drive.hip) calls the same router, and so does mh_artic_batch_step_report, with the rows.
 #include "mh_artic_dev.h"
+#include <cstdarg>
+#include <cstdio>
 
 // Every step of a batch whose family (artic_geom_family) is box, pair or box-sphere, undriven and driven: the family's checks, then the launcher
 // of that family in the batch's coordinates.  To add a family: its switch and token in two wrapper files, an enumerator, its precedence in
@@ -14,6 +16,12 @@ int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, con
   namespace ar = mh::artic;
   const bool pose = ab->base_coords == MH_ARTIC_BASE_POSE;
   const mh_artic_family fam = artic_geom_family(ab);
+  if (fam == MH_ARTIC_FAM_PW) {                                    // per-world parameters: the report kernels over B images, an LDS image of their own
+    if (!ab->d_ws || ab->ws_stride < ar::WS_PAIR) return fail(MH_ERR_INVALID_ARG, "the batch's workspace is not sized for the per-world-parameters kernels");
+    const size_t lds = pose ? artic_pw_pose_lds_bytes(ab->nj) : artic_pw_lds_bytes(ab->nj);
+    if (lds > 65536) return fail(MH_ERR_INVALID_ARG, "the per-world-parameters kernels' LDS image (%zu bytes) exceeds a workgroup's 64 KB", lds);
+    return pose ? artic_pw_pose_launch(ab, stream, dt, nsteps, D, report) : artic_pw_launch(ab, stream, dt, nsteps, D, report);
+  }
   if (fam == MH_ARTIC_FAM_RP) {                                    // the report kernels: the pair workspace, an LDS image of their own
     if (!ab->d_ws || ab->ws_stride < ar::WS_PAIR) return fail(MH_ERR_INVALID_ARG, "the batch's workspace is not sized for the report kernels");
     const size_t lds = pose ? artic_rp_pose_lds_bytes(ab->nj) : artic_rp_lds_bytes(ab->nj);
@@ -59,55 +67,74 @@ int mh_artic_report_slots(const mh_artic_model* model)
   return model->nspheres + model->nboxes + model->npairs;
 }
 
-// mh_artic_batch_create (report false) and mh_artic_batch_create_report (true): one text, the report only decides the family
-static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out, bool report)
+// A refusal of artic_check_model: the message as it is for the shared model (world < 0), with the world in front for a record
+static int refuse(int world, const char* fmt, ...)
+{
+  char buf[512];
+  va_list ap; va_start(ap, fmt); std::vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+  return world < 0 ? fail(MH_ERR_INVALID_ARG, "%s", buf) : fail(MH_ERR_INVALID_ARG, "world %d: %s", world, buf);
+}
+
+// the fields of mh_artic_params, each with the model's name, type and extent
+#define MH_ARTIC_PARAM_FIELDS(X) X(Rrel) X(trel) X(axis) X(com) X(inertia) X(mass) X(lolimit) X(hilimit) X(limit_restitution) X(gravity) \
+  X(sphere_center) X(sphere_radius) X(plane_R) X(plane_o) X(cp_epsilon) X(cp_mu_coulomb) X(cp_mu_viscous) X(cp_compliance) X(box_center) X(box_R) X(box_len)
+// record r written into model m (the topology stays m's)
+static void params_into_model(const mh_artic_params& r, mh_artic_model& m)
+{
+#define X(f) static_assert(sizeof(m.f) == sizeof(r.f), #f); std::memcpy(&m.f, &r.f, sizeof(r.f));
+  MH_ARTIC_PARAM_FIELDS(X)
+#undef X
+}
+
+struct ArticPlan { bool use_rp, use_bsp, use_pair; };   // the family decisions of the model's checks
+// Every check of mh_artic_batch_create, and the device image of a model: ONE text for the shared model (world < 0, base NULL) and for "the model
+// with record w written into it" (world = w, base = the shared model), so a record is validated as the model's values are and its image is filled
+// as the shared one is.  report: the batch is a report batch; params: it holds an image per world (mh_artic_batch_create_params), which steps
+// through the per-world-parameters family whatever its geometry, with cp_nk checked and the friction polygon filled whatever cp_mu_coulomb
+static int artic_check_model(const mh_artic_model* model, bool report, bool params, int world, const mh_artic_model* base, mh::artic::Model& hm, ArticPlan& plan)
 {
   namespace ar = mh::artic;
-  if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
-  *out = nullptr;
-  if (!model) return fail(MH_ERR_INVALID_ARG, "null model");
-  if (B <= 0) return fail(MH_ERR_INVALID_ARG, "batch must be > 0");
   const int nj = model->nj;
-  if (nj < 1 || nj > MH_ARTIC_MAX_JOINTS) return fail(MH_ERR_INVALID_ARG, "nj = %d outside [1, %d]", nj, MH_ARTIC_MAX_JOINTS);
-  ar::Model hm; std::memset(&hm, 0, sizeof(hm)); hm.m = *model;
+  if (nj < 1 || nj > MH_ARTIC_MAX_JOINTS) return refuse(world, "nj = %d outside [1, %d]", nj, MH_ARTIC_MAX_JOINTS);
+  std::memset(&hm, 0, sizeof(hm)); hm.m = *model;
   std::memset(hm.anc, 0, sizeof(hm.anc)); std::memset(hm.fcos, 0, sizeof(hm.fcos)); std::memset(hm.fsin, 0, sizeof(hm.fsin));   // (they overlay m's box block: bx holds it)
   for (int i = 0; i < nj; i++) {
     const int p = model->parent[i];
-    if (p >= i || p < -1) return fail(MH_ERR_INVALID_ARG, "joint %d: parent %d must come before it (-1 = base)", i, p);
-    if (model->jtype[i] != MH_JOINT_REVOLUTE && model->jtype[i] != MH_JOINT_PRISMATIC) return fail(MH_ERR_INVALID_ARG, "joint %d: type %d is not built (revolute, prismatic)", i, model->jtype[i]);
-    if (!(model->mass[i] >= 0.0)) return fail(MH_ERR_INVALID_ARG, "link %d: mass must be >= 0", i);
+    if (p >= i || p < -1) return refuse(world, "joint %d: parent %d must come before it (-1 = base)", i, p);
+    if (model->jtype[i] != MH_JOINT_REVOLUTE && model->jtype[i] != MH_JOINT_PRISMATIC) return refuse(world, "joint %d: type %d is not built (revolute, prismatic)", i, model->jtype[i]);
+    if (!(model->mass[i] >= 0.0)) return refuse(world, "link %d: mass must be >= 0", i);
     const double* a = model->axis[i]; const double nn = a[0]*a[0] + a[1]*a[1] + a[2]*a[2];
-    if (!(nn > 0.999999 && nn < 1.000001)) return fail(MH_ERR_INVALID_ARG, "joint %d: axis is not a unit vector", i);
-    if (!(model->lolimit[i] <= model->hilimit[i])) return fail(MH_ERR_INVALID_ARG, "joint %d: lower limit above the upper one", i);
+    if (!(nn > 0.999999 && nn < 1.000001)) return refuse(world, "joint %d: axis is not a unit vector", i);
+    if (!(model->lolimit[i] <= model->hilimit[i])) return refuse(world, "joint %d: lower limit above the upper one", i);
     hm.anc[i] = (1u << i) | (p >= 0 ? hm.anc[p] : 0u);
   }
-  if (model->floating_base != 0 && model->floating_base != 1) return fail(MH_ERR_INVALID_ARG, "floating_base = %d: 0 or 1", model->floating_base);
+  if (model->floating_base != 0 && model->floating_base != 1) return refuse(world, "floating_base = %d: 0 or 1", model->floating_base);
   if (model->floating_base) {                                        // the layout include/moby_hip_artic.h states (conservative advancement reads joints 0..2 as the base's velocity)
-    if (nj < 6) return fail(MH_ERR_INVALID_ARG, "floating_base needs the six virtual joints in front (nj = %d)", nj);
+    if (nj < 6) return refuse(world, "floating_base needs the six virtual joints in front (nj = %d)", nj);
     for (int v = 0; v < 6; v++) {
       bool ok = model->parent[v] == v - 1 && model->jtype[v] == ((v < 3) ? MH_JOINT_PRISMATIC : MH_JOINT_REVOLUTE);
       for (int k = 0; k < 3; k++) ok = ok && model->axis[v][k] == ((k == v % 3) ? 1.0 : 0.0) && model->com[v][k] == 0.0 && (v == 0 || model->trel[v][k] == 0.0);
       for (int k = 0; k < 9; k++) ok = ok && (v == 3 || model->Rrel[v][k] == ((k % 4 == 0) ? 1.0 : 0.0));
-      if (!ok) return fail(MH_ERR_INVALID_ARG, "floating_base: joint %d is not the virtual joint the layout states (sliders along global x, y, z, then hinges about the base link's x, y, z through its COM)", v);
+      if (!ok) return refuse(world, "floating_base: joint %d is not the virtual joint the layout states (sliders along global x, y, z, then hinges about the base link's x, y, z through its COM)", v);
     }
   }
   // a link may be massless (the virtual links under a floating base, mh_io_load_xml_artic) as long as every joint moves mass: the composite inertia outboard of it
   { double sub[MH_ARTIC_MAX_JOINTS];
     for (int i = 0; i < nj; i++) sub[i] = model->mass[i];
-    for (int i = nj - 1; i >= 0; i--) { if (!(sub[i] > 0.0)) return fail(MH_ERR_INVALID_ARG, "joint %d carries no mass (its link and everything outboard of it are massless)", i); if (model->parent[i] >= 0) sub[model->parent[i]] += sub[i]; } }
-  if (model->nspheres < 0 || model->nspheres > MH_ARTIC_MAX_SPHERES) return fail(MH_ERR_INVALID_ARG, "nspheres = %d outside [0, %d]", model->nspheres, MH_ARTIC_MAX_SPHERES);
+    for (int i = nj - 1; i >= 0; i--) { if (!(sub[i] > 0.0)) return refuse(world, "joint %d carries no mass (its link and everything outboard of it are massless)", i); if (model->parent[i] >= 0) sub[model->parent[i]] += sub[i]; } }
+  if (model->nspheres < 0 || model->nspheres > MH_ARTIC_MAX_SPHERES) return refuse(world, "nspheres = %d outside [0, %d]", model->nspheres, MH_ARTIC_MAX_SPHERES);
   for (int s = 0; s < model->nspheres; s++) {
-    if (model->sphere_link[s] < 0 || model->sphere_link[s] >= nj) return fail(MH_ERR_INVALID_ARG, "sphere %d: link %d outside [0, %d)", s, model->sphere_link[s], nj);
-    if (!(model->sphere_radius[s] > 0.0)) return fail(MH_ERR_INVALID_ARG, "sphere %d: radius must be > 0", s);
+    if (model->sphere_link[s] < 0 || model->sphere_link[s] >= nj) return refuse(world, "sphere %d: link %d outside [0, %d)", s, model->sphere_link[s], nj);
+    if (!(model->sphere_radius[s] > 0.0)) return refuse(world, "sphere %d: radius must be > 0", s);
   }
-  if (model->nboxes < 0 || model->nboxes > MH_ARTIC_MAX_BOXES) return fail(MH_ERR_INVALID_ARG, "nboxes = %d outside [0, %d]", model->nboxes, MH_ARTIC_MAX_BOXES);
+  if (model->nboxes < 0 || model->nboxes > MH_ARTIC_MAX_BOXES) return refuse(world, "nboxes = %d outside [0, %d]", model->nboxes, MH_ARTIC_MAX_BOXES);
   for (int k = 0; k < model->nboxes; k++) {
-    if (model->box_link[k] < -1 || model->box_link[k] >= nj) return fail(MH_ERR_INVALID_ARG, "box %d: link %d outside [-1, %d) (-1 = a static box)", k, model->box_link[k], nj);
-    for (int c = 0; c < 3; c++) if (!(model->box_len[k][c] > 0.0) || !std::isfinite(model->box_len[k][c])) return fail(MH_ERR_INVALID_ARG, "box %d: edge lengths must be finite and > 0", k);
+    if (model->box_link[k] < -1 || model->box_link[k] >= nj) return refuse(world, "box %d: link %d outside [-1, %d) (-1 = a static box)", k, model->box_link[k], nj);
+    for (int c = 0; c < 3; c++) if (!(model->box_len[k][c] > 0.0) || !std::isfinite(model->box_len[k][c])) return refuse(world, "box %d: edge lengths must be finite and > 0", k);
     const double* Rb = model->box_R[k];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {       // R R' = I
       const double d = (Rb[3*i] * Rb[3*j] + Rb[3*i+1] * Rb[3*j+1]) + Rb[3*i+2] * Rb[3*j+2];
-      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) < 1e-9)) return fail(MH_ERR_INVALID_ARG, "box %d: box_R is not orthonormal", k);
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) < 1e-9)) return refuse(world, "box %d: box_R is not orthonormal", k);
     }
     hm.bx.link[k] = model->box_link[k];
     for (int c = 0; c < 3; c++) { hm.bx.center[k][c] = model->box_center[k][c]; hm.bx.len[k][c] = model->box_len[k][c]; }
@@ -117,82 +144,124 @@ static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch
   int nstatic = 0;
   for (int k = 0; k < model->nboxes; k++) if (model->box_link[k] < 0) nstatic++;
   // sphere pairs between links
-  if (model->npairs < 0 || model->npairs > MH_ARTIC_MAX_PAIRS) return fail(MH_ERR_INVALID_ARG, "npairs = %d outside [0, %d]", model->npairs, MH_ARTIC_MAX_PAIRS);
+  if (model->npairs < 0 || model->npairs > MH_ARTIC_MAX_PAIRS) return refuse(world, "npairs = %d outside [0, %d]", model->npairs, MH_ARTIC_MAX_PAIRS);
   for (int k = 0; k < model->npairs; k++) {
     const int a = model->pair_a[k], b = model->pair_b[k], kind = model->pair_kind[k];
-    if (kind != MH_ARTIC_PAIR_SPHERES && kind != MH_ARTIC_PAIR_BOX_SPHERE) return fail(MH_ERR_INVALID_ARG, "pair %d: kind %d is not built (0 = two spheres, 1 = a box and a sphere)", k, kind);
+    if (kind != MH_ARTIC_PAIR_SPHERES && kind != MH_ARTIC_PAIR_BOX_SPHERE) return refuse(world, "pair %d: kind %d is not built (0 = two spheres, 1 = a box and a sphere)", k, kind);
     hm.pr.kind[k] = kind;
     if (kind == MH_ARTIC_PAIR_BOX_SPHERE) {
-      if (a < 0 || a >= model->nboxes) return fail(MH_ERR_INVALID_ARG, "pair %d: box %d outside the box list [0, %d)", k, a, model->nboxes);
-      if (b < 0 || b >= model->nspheres) return fail(MH_ERR_INVALID_ARG, "pair %d: sphere %d outside the sphere list [0, %d)", k, b, model->nspheres);
-      if (model->box_link[a] == model->sphere_link[b]) return fail(MH_ERR_INVALID_ARG, "pair %d: box %d and sphere %d sit on the same link %d", k, a, b, model->box_link[a]);
+      if (a < 0 || a >= model->nboxes) return refuse(world, "pair %d: box %d outside the box list [0, %d)", k, a, model->nboxes);
+      if (b < 0 || b >= model->nspheres) return refuse(world, "pair %d: sphere %d outside the sphere list [0, %d)", k, b, model->nspheres);
+      if (model->box_link[a] == model->sphere_link[b]) return refuse(world, "pair %d: box %d and sphere %d sit on the same link %d", k, a, b, model->box_link[a]);
       for (int k2 = 0; k2 < k; k2++)
-        if (model->pair_kind[k2] == kind && model->pair_a[k2] == a && model->pair_b[k2] == b) return fail(MH_ERR_INVALID_ARG, "pair %d: box %d and sphere %d are pair %d already", k, a, b, k2);
+        if (model->pair_kind[k2] == kind && model->pair_a[k2] == a && model->pair_b[k2] == b) return refuse(world, "pair %d: box %d and sphere %d are pair %d already", k, a, b, k2);
       hm.pr.a[k] = a; hm.pr.b[k] = b;
       continue;
     }
-    if (a < 0 || a >= model->nspheres || b < 0 || b >= model->nspheres) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) outside the sphere list [0, %d)", k, a, b, model->nspheres);
-    if (a == b) return fail(MH_ERR_INVALID_ARG, "pair %d: sphere %d against itself", k, a);
-    if (model->sphere_link[a] == model->sphere_link[b]) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres %d and %d sit on the same link %d", k, a, b, model->sphere_link[a]);
+    if (a < 0 || a >= model->nspheres || b < 0 || b >= model->nspheres) return refuse(world, "pair %d: spheres (%d, %d) outside the sphere list [0, %d)", k, a, b, model->nspheres);
+    if (a == b) return refuse(world, "pair %d: sphere %d against itself", k, a);
+    if (model->sphere_link[a] == model->sphere_link[b]) return refuse(world, "pair %d: spheres %d and %d sit on the same link %d", k, a, b, model->sphere_link[a]);
     for (int k2 = 0; k2 < k; k2++)
-      if (model->pair_kind[k2] == kind && ((model->pair_a[k2] == a && model->pair_b[k2] == b) || (model->pair_a[k2] == b && model->pair_b[k2] == a))) return fail(MH_ERR_INVALID_ARG, "pair %d: spheres (%d, %d) are pair %d already", k, a, b, k2);
+      if (model->pair_kind[k2] == kind && ((model->pair_a[k2] == a && model->pair_b[k2] == b) || (model->pair_a[k2] == b && model->pair_b[k2] == a))) return refuse(world, "pair %d: spheres (%d, %d) are pair %d already", k, a, b, k2);
     hm.pr.a[k] = a; hm.pr.b[k] = b;
   }
-  if (model->sphere_no_plane < 0 || (model->sphere_no_plane >> model->nspheres) != 0) return fail(MH_ERR_INVALID_ARG, "sphere_no_plane = 0x%x has bits beyond the %d spheres", (unsigned)model->sphere_no_plane, model->nspheres);
+  if (model->sphere_no_plane < 0 || (model->sphere_no_plane >> model->nspheres) != 0) return refuse(world, "sphere_no_plane = 0x%x has bits beyond the %d spheres", (unsigned)model->sphere_no_plane, model->nspheres);
   hm.pr.n = model->npairs; hm.pr.no_plane = model->sphere_no_plane; hm.pr.nstatic = nstatic;
   bool has_bsp = false;
   for (int k = 0; k < model->nboxes; k++) {
     if (model->box_link[k] >= 0) continue;
     bool paired = false;
     for (int k2 = 0; k2 < model->npairs; k2++) paired = paired || (model->pair_kind[k2] == MH_ARTIC_PAIR_BOX_SPHERE && model->pair_a[k2] == k);
-    if (!paired) return fail(MH_ERR_INVALID_ARG, "box %d is static (link -1) and appears in no box-sphere pair", k);
+    if (!paired) return refuse(world, "box %d is static (link -1) and appears in no box-sphere pair", k);
   }
   for (int k = 0; k < model->npairs; k++) has_bsp = has_bsp || model->pair_kind[k] == MH_ARTIC_PAIR_BOX_SPHERE;
   const bool has_geom = model->nspheres > 0 || model->nboxes > 0;
-  const bool use_bsp = has_bsp || nstatic > 0 || (has_geom && mh_g_debug_artic_bsp != 0);
-  const bool use_rp = report || (use_bsp && mh_g_debug_artic_rp != 0);          // the report kernels hold all the work of the box-sphere kernels
-  if (report && model->nspheres + model->nboxes + model->npairs == 0) return fail(MH_ERR_INVALID_ARG, "a contact report needs geometry: the model has no sphere, box or pair (no slot)");
-  const bool use_pair = use_rp || use_bsp || model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
-  if (use_pair && !use_rp && artic_pair_lds_bytes(nj) > 65536) return fail(MH_ERR_INVALID_ARG, "the pair kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, artic_pair_lds_bytes(nj));
-  if (use_rp) {                                                     // this family's own image, in either coordinates (the batch may be switched to poses later)
+  const bool use_bsp = plan.use_bsp = has_bsp || nstatic > 0 || (has_geom && mh_g_debug_artic_bsp != 0);
+  const bool use_rp = plan.use_rp = report || (use_bsp && mh_g_debug_artic_rp != 0);          // the report kernels hold all the work of the box-sphere kernels
+  if (report && model->nspheres + model->nboxes + model->npairs == 0) return refuse(world, "a contact report needs geometry: the model has no sphere, box or pair (no slot)");
+  const bool use_pair = plan.use_pair = params || use_rp || use_bsp || model->npairs > 0 || model->sphere_no_plane != 0 || (has_geom && mh_g_debug_artic_pair != 0);
+  if (use_pair && !use_rp && !params && artic_pair_lds_bytes(nj) > 65536) return refuse(world, "the pair kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, artic_pair_lds_bytes(nj));
+  if (params || (use_rp && mh_g_debug_artic_pw != 0)) {             // the per-world-parameters family's image, in either coordinates
+    const size_t lds = artic_pw_pose_lds_bytes(nj) > artic_pw_lds_bytes(nj) ? artic_pw_pose_lds_bytes(nj) : artic_pw_lds_bytes(nj);
+    if (lds > 65536) return refuse(world, "the per-world-parameters kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, lds);
+  } else if (use_rp) {                                              // this family's own image, in either coordinates (the batch may be switched to poses later)
     const size_t lds = artic_rp_pose_lds_bytes(nj) > artic_rp_lds_bytes(nj) ? artic_rp_pose_lds_bytes(nj) : artic_rp_lds_bytes(nj);
-    if (lds > 65536) return fail(MH_ERR_INVALID_ARG, "the report kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, lds);
+    if (lds > 65536) return refuse(world, "the report kernels' LDS image at %d joints (%zu bytes) exceeds a workgroup's 64 KB", nj, lds);
   }
-  if (model->cstab_max_iterations < 0) return fail(MH_ERR_INVALID_ARG, "cstab_max_iterations = %d < 0", model->cstab_max_iterations);
+  if (model->cstab_max_iterations < 0) return refuse(world, "cstab_max_iterations = %d < 0", model->cstab_max_iterations);
   if (model->nspheres > 0 || model->nboxes > 0) {
     const double* Rp = model->plane_R; const double nn = Rp[1]*Rp[1] + Rp[4]*Rp[4] + Rp[7]*Rp[7];
-    if (!(nn > 0.999999 && nn < 1.000001)) return fail(MH_ERR_INVALID_ARG, "plane_R is not a rotation (its +Y column is the plane normal)");
-    if (!(model->min_step_size > 0.0) || !(model->contact_dist_thresh > 0.0)) return fail(MH_ERR_INVALID_ARG, "min_step_size and contact_dist_thresh must be > 0 when spheres or boxes are present");
-    if (!(model->cp_epsilon >= 0.0) || !(model->cp_mu_coulomb >= 0.0)) return fail(MH_ERR_INVALID_ARG, "contact parameters must be >= 0");
-    if (!(model->cp_mu_coulomb >= 1e2)) {                         // the Drumwright-Shell model's parameters
+    if (!(nn > 0.999999 && nn < 1.000001)) return refuse(world, "plane_R is not a rotation (its +Y column is the plane normal)");
+    if (!(model->min_step_size > 0.0) || !(model->contact_dist_thresh > 0.0)) return refuse(world, "min_step_size and contact_dist_thresh must be > 0 when spheres or boxes are present");
+    if (!(model->cp_epsilon >= 0.0) || !(model->cp_mu_coulomb >= 0.0)) return refuse(world, "contact parameters must be >= 0");
+    if (params || !(model->cp_mu_coulomb >= 1e2)) {               // the Drumwright-Shell model's parameters (per-world parameters: worlds on either side of 100 may share the batch)
       const int nk = model->cp_nk > 0 ? model->cp_nk : 4;
-      if (nk < 4 || nk > 64 || (nk & 1)) return fail(MH_ERR_INVALID_ARG, "cp_nk = %d: friction-cone-edges must be even, in [4, 64]", nk);
-      if (!(model->cp_mu_viscous >= 0.0) || !(model->cp_compliance >= 0.0)) return fail(MH_ERR_INVALID_ARG, "contact parameters must be >= 0");
+      if (nk < 4 || nk > 64 || (nk & 1)) return refuse(world, "cp_nk = %d: friction-cone-edges must be even, in [4, 64]", nk);
+      if (!(model->cp_mu_viscous >= 0.0) || !(model->cp_compliance >= 0.0)) return refuse(world, "contact parameters must be >= 0");
       const int kh = nk / 2;
       for (int j = 0; j < kh; j++) { const double theta = (double)j / (kh - 1) * M_PI_2; hm.fcos[j] = std::cos(theta); hm.fsin[j] = std::sin(theta); }
     }
   }
+  if (base) {                                                       // a record's own rules: it moves values, never the model's decisions
+    const double INF_ = 1.7976931348623157e308;
+    for (int i = 0; i < nj; i++) {
+      if ((model->lolimit[i] > -INF_) != (base->lolimit[i] > -INF_)) return refuse(world, "joint %d: lolimit is %s where the model's is not (a record may move a finite limit, not add or remove one)", i, model->lolimit[i] > -INF_ ? "finite" : "infinite");
+      if ((model->hilimit[i] < INF_) != (base->hilimit[i] < INF_)) return refuse(world, "joint %d: hilimit is %s where the model's is not (a record may move a finite limit, not add or remove one)", i, model->hilimit[i] < INF_ ? "finite" : "infinite");
+    }
+    for (int k = 0; k < 3; k++) if (!std::isfinite(model->gravity[k])) return refuse(world, "gravity is not finite");
+    if (model->nspheres > 0 || model->nboxes > 0) {
+      const double cp[4] = { model->cp_epsilon, model->cp_mu_coulomb, model->cp_mu_viscous, model->cp_compliance };
+      for (int k = 0; k < 4; k++) if (!std::isfinite(cp[k]) || !(cp[k] >= 0.0)) return refuse(world, "contact parameters (cp_epsilon, cp_mu_coulomb, cp_mu_viscous, cp_compliance) must be finite and >= 0");
+    }
+  }
+  return MH_OK;
+}
+
+// mh_artic_batch_create (report false) and mh_artic_batch_create_report (true), and mh_artic_batch_create_params (params true; host: B records or
+// NULL = the model's): one text, the report and the records only decide the family and the number of images
+static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out, bool report, bool params = false, const mh_artic_params* host = nullptr)
+{
+  namespace ar = mh::artic;
+  if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  if (!model) return fail(MH_ERR_INVALID_ARG, "null model");
+  if (B <= 0) return fail(MH_ERR_INVALID_ARG, "batch must be > 0");
+  ar::Model hm; ArticPlan plan;
+  { const int rc = artic_check_model(model, report, false, -1, nullptr, hm, plan); if (rc != MH_OK) return rc; }    // every refusal of mh_artic_batch_create, unchanged
+  const bool pw20 = !params && plan.use_rp && mh_g_debug_artic_pw != 0;      // mh_debug_set(20, 1): B images, all the model's
+  std::vector<ar::Model> images;
+  if (params) {
+    images.resize((size_t)B);
+    for (int w = 0; w < B; w++) {
+      mh_artic_model mw = *model;
+      if (host) params_into_model(host[w], mw);
+      const int rc = artic_check_model(&mw, report, true, w, model, images[w], plan); if (rc != MH_OK) return rc;
+    }
+  } else if (pw20) images.assign((size_t)B, hm);
+  const size_t nimg = images.empty() ? 1 : (size_t)B;
+  const int nj = model->nj;
+  const bool use_rp = plan.use_rp, use_bsp = plan.use_bsp, use_pair = plan.use_pair, use_pw = params || pw20;
   if (mh_device_count() <= 0) return fail(MH_ERR_NO_DEVICE, "no HIP device visible");
   { const int rc = init_pow10(); if (rc != MH_OK) return rc; }             // this code object's powers of ten, before its first launch on the device
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
-  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->family = use_rp ? MH_ARTIC_FAM_RP : use_bsp ? MH_ARTIC_FAM_BSP : use_pair ? MH_ARTIC_FAM_PAIR : model->nboxes > 0 ? MH_ARTIC_FAM_BOX : MH_ARTIC_FAM_NONE; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
-  ab->report = report ? 1 : 0;
+  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->family = use_pw ? MH_ARTIC_FAM_PW : use_rp ? MH_ARTIC_FAM_RP : use_bsp ? MH_ARTIC_FAM_BSP : use_pair ? MH_ARTIC_FAM_PAIR : model->nboxes > 0 ? MH_ARTIC_FAM_BOX : MH_ARTIC_FAM_NONE; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->report = report ? 1 : 0; ab->params = params ? 1 : pw20 ? 2 : 0; ab->model = *model;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;
-  bool ok = hipMalloc((void**)&ab->d_model, sizeof(ar::Model)) == hipSuccess && hipMalloc((void**)&ab->d_q, sB * nj * 8) == hipSuccess
+  bool ok = hipMalloc((void**)&ab->d_model, nimg * sizeof(ar::Model)) == hipSuccess && hipMalloc((void**)&ab->d_q, sB * nj * 8) == hipSuccess
          && hipMalloc((void**)&ab->d_qd, sB * nj * 8) == hipSuccess && hipMalloc((void**)&ab->d_aux, sB * sizeof(mh_world_aux)) == hipSuccess;
   // the box kernels' layout for a model with boxes, and for a sphere model created while mh_debug_set(12, 1) sends it to those kernels
   // (and the pair kernels' for a batch that steps through those)
   ab->ws_stride = use_pair ? ar::WS_PAIR : (model->nboxes > 0 || (model->nspheres > 0 && mh_g_debug_artic_box != 0)) ? ar::WS_BOX : 2 * MH_LCP_MAX_N_WAVE * MH_LCP_MAX_N_WAVE;
-  if (ok && (model->nspheres > 0 || model->nboxes > 0) && (use_pair || !(model->cp_mu_coulomb >= 1e2) || model->cstab_max_iterations != 0))   // (the stabiliser's LCP with contact AND limit rows lives there too)
+  if (ok && (use_pw || model->nspheres > 0 || model->nboxes > 0) && (use_pair || !(model->cp_mu_coulomb >= 1e2) || model->cstab_max_iterations != 0))   // (the stabiliser's LCP with contact AND limit rows lives there too)
     ok = hipMalloc((void**)&ab->d_ws, sB * ab->ws_stride * sizeof(double)) == hipSuccess;
   if (ok) {
     std::vector<mh_world_aux> a(sB);
     mh_world_aux_init(&a[0], 1);
     for (int b = 1; b < B; b++) a[b] = a[0];
-    ok = hipMemcpy(ab->d_model, &hm, sizeof(hm), hipMemcpyHostToDevice) == hipSuccess
+    ok = hipMemcpy(ab->d_model, images.empty() ? &hm : images.data(), nimg * sizeof(hm), hipMemcpyHostToDevice) == hipSuccess
       && hipMemset(ab->d_q, 0, sB * nj * 8) == hipSuccess && hipMemset(ab->d_qd, 0, sB * nj * 8) == hipSuccess
       && hipMemcpy(ab->d_aux, a.data(), sB * sizeof(mh_world_aux), hipMemcpyHostToDevice) == hipSuccess;
   }
@@ -203,6 +272,58 @@ static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch
 
 int mh_artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out) { return artic_batch_create(model, B, out, false); }
 int mh_artic_batch_create_report(const mh_artic_model* model, int B, mh_artic_batch** out) { return artic_batch_create(model, B, out, true); }
+
+void mh_artic_params_from_model(const mh_artic_model* model, mh_artic_params* out)
+{
+  if (!model || !out) return;
+#define X(f) std::memcpy(&out->f, &model->f, sizeof(out->f));
+  MH_ARTIC_PARAM_FIELDS(X)
+#undef X
+}
+
+int mh_artic_batch_create_params(const mh_artic_model* model, const mh_artic_params* host, int B, int flags, mh_artic_batch** out)
+{
+  if (out) *out = nullptr;
+  if (flags & ~MH_ARTIC_CREATE_REPORT) return fail(MH_ERR_INVALID_ARG, "unknown bits 0x%x in flags (MH_ARTIC_CREATE_REPORT or 0)", flags & ~MH_ARTIC_CREATE_REPORT);
+  return artic_batch_create(model, B, out, (flags & MH_ARTIC_CREATE_REPORT) != 0, true, host);
+}
+
+// the checks the two record setters share
+static int check_params_range(const mh_artic_batch* ab, const void* rec, int first, int count)
+{
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  if (ab->params != 1) return fail(MH_ERR_INVALID_ARG, "the batch was not created by mh_artic_batch_create_params: it has no records");
+  if (!rec) return fail(MH_ERR_INVALID_ARG, "null records");
+  if (first < 0 || count < 0 || first > ab->B || count > ab->B - first) return fail(MH_ERR_INVALID_ARG, "worlds [%d, %d + %d) outside the batch's [0, %d)", first, first, count, ab->B);
+  return MH_OK;
+}
+
+int mh_artic_batch_set_params(mh_artic_batch* ab, const mh_artic_params* host, int first, int count)
+{
+  namespace ar = mh::artic;
+  { const int rc = check_params_range(ab, host, first, count); if (rc != MH_OK) return rc; }
+  std::vector<ar::Model> images((size_t)count);
+  ArticPlan plan;
+  for (int r = 0; r < count; r++) {                                  // every record before any is written
+    mh_artic_model mw = ab->model;
+    params_into_model(host[r], mw);
+    const int rc = artic_check_model(&mw, ab->report != 0, true, first + r, &ab->model, images[r], plan); if (rc != MH_OK) return rc;
+  }
+  if (count == 0) return MH_OK;
+  MH_ON_DEVICE(ab);
+  MH_HIP(hipDeviceSynchronize());                              // a step may be reading the images on a caller's stream
+  MH_HIP(hipMemcpy(ab->d_model + first, images.data(), (size_t)count * sizeof(ar::Model), hipMemcpyHostToDevice));
+  return MH_OK;
+}
+
+int mh_artic_batch_set_params_dev(mh_artic_batch* ab, void* stream, const mh_artic_params* dev, int first, int count)
+{
+  { const int rc = check_params_range(ab, dev, first, count); if (rc != MH_OK) return rc; }
+  if (count == 0) return MH_OK;
+  MH_ON_DEVICE(ab);
+  MH_HIP(artic_pw_scatter_launch(ab, stream, dev, first, count));
+  return MH_OK;
+}
 
 int mh_artic_batch_upload(mh_artic_batch* ab, const double* q, const double* qd, const mh_world_aux* aux)
 {
@@ -319,7 +440,8 @@ int mh_artic_batch_fwd_dyn(mh_artic_batch* ab, const double* tau, double* qdd_ou
   if (ok && H_out) ok = hipMalloc((void**)&d_H, B * nj * nj * 8) == hipSuccess;
   if (!ok) { cleanup(); return fail(MH_ERR_HIP, "device allocation failed"); }
   hipError_t e = hipSuccess;
-  if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok);
+  if (ab->params) e = ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok) : artic_pw_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok);   // each world's own image
+  else if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok);
   else hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
                           (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)d_tau, d_qdd, d_H, (double*)nullptr, d_ok);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -343,7 +465,8 @@ int mh_artic_batch_link_poses(mh_artic_batch* ab, double* poses)
   double* d_p = nullptr;
   MH_HIP(hipMalloc((void**)&d_p, bytes));
   hipError_t e = hipSuccess;
-  if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr);
+  if (ab->params) e = ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr) : artic_pw_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr);
+  else if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr);
   else hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
                           (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)nullptr, (double*)nullptr, (double*)nullptr, d_p, (int*)nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -366,7 +489,8 @@ int mh_artic_batch_jacobian(mh_artic_batch* ab, int link, const double* points, 
   hipError_t e = hipMalloc((void**)&d_J, jb);
   if (e == hipSuccess) e = hipMemcpy(d_p, points, pb, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_jacobian_launch(ab, link, d_p, d_J);
+    if (ab->params) e = ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_jacobian_launch(ab, link, d_p, d_J) : artic_pw_jacobian_launch(ab, link, d_p, d_J);
+    else if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_jacobian_launch(ab, link, d_p, d_J);
     else hipLaunchKernelGGL(ar::k_artic_jacobian, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
                             (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, link, (const double*)d_p, d_J);
     if (e == hipSuccess) e = hipDeviceSynchronize();

@@ -1467,7 +1467,11 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
   extern __shared__ double g[];
   const int b = blockIdx.x;
   if (b >= B) return;
+#ifdef MH_ARTIC_PARAMS_TU
+  const Model& M = Mg[b];                                          // per-world parameters: world b's own image of B
+#else
   const Model& M = *Mg;
+#endif
   const int nj = M.m.nj, lane = lane_id();
   const Lay Y(nj);
   const LayC Z(Y.total, nj, Y.I6, 60 * nj + 12);

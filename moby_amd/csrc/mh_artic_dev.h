@@ -1,10 +1,10 @@
 // mh_artic_dev.h -- many-worlds stepper for fixed-base articulated bodies (include/moby_hip_artic.h; BASELINE config 5): the device code and
 // the host declarations every articulated translation unit shares.
 //
-// Each of the eleven articulated .hip files sets its switches (MH_ARTIC_DRIVE_TU, MH_ARTIC_POSE_TU, MH_ARTIC_BOX_TU, MH_ARTIC_PAIR_TU,
-// MH_ARTIC_BSP_TU, MH_ARTIC_REPORT_TU; a geometry file also its family token MH_ARTIC_GEOM) and includes this header once: the switches pick the
+// Each of the thirteen articulated .hip files sets its switches (MH_ARTIC_DRIVE_TU, MH_ARTIC_POSE_TU, MH_ARTIC_BOX_TU, MH_ARTIC_PAIR_TU,
+// MH_ARTIC_BSP_TU, MH_ARTIC_REPORT_TU, MH_ARTIC_PARAMS_TU; a geometry file also its family token MH_ARTIC_GEOM) and includes this header once: the switches pick the
 // kernels of that code object.  mh_artic.hip (no switch) holds the C entry points and the router to the geometry kernels, mh_artic_drive.hip and
-// mh_artic_pose.hip their own entry points; a geometry file (mh_artic_{box,pair,bsp,rp}[_pose].hip) holds nothing else: its launcher is stamped at
+// mh_artic_pose.hip their own entry points; a geometry file (mh_artic_{box,pair,bsp,rp,pw}[_pose].hip) holds nothing else (mh_artic_pw.hip: the record scatter): its launcher is stamped at
 // the end of this header.
 //
 // One wavefront per world. Per step (TimeSteppingSimulator::do_mini_step with no collision geometry, TSS:114-222):
@@ -921,9 +921,18 @@ void k_artic_step_stab(const Model* __restrict__ Mg, int B, double dt, int nstep
                        mh_world_aux* __restrict__ auxg) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg); }
 #endif
 
-#if !defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_BOX_TU)
+#if (!defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_BOX_TU)) || defined(MH_ARTIC_PARAMS_TU)
 // k_artic_fwd_dyn / k_artic_jacobian, and in pose coordinates k_artic_fwd_dyn_pose / k_artic_jacobian_pose: one more argument, the B x 7 poses
-#ifdef MH_ARTIC_POSE_TU
+// (MH_ARTIC_PARAMS_TU: k_artic_fwd_dyn_pw[_pose] / k_artic_jacobian_pw[_pose], which read world b's own image of B)
+#if defined(MH_ARTIC_PARAMS_TU) && defined(MH_ARTIC_POSE_TU)
+#define MH_POSE_KERNEL(name) name##_pw_pose
+#define MH_POSE_ARG , const double* __restrict__ poseg
+#define MH_POSE_LOAD() pose_load(Y, g, poseg + 7 * (size_t)b)
+#elif defined(MH_ARTIC_PARAMS_TU)
+#define MH_POSE_KERNEL(name) name##_pw
+#define MH_POSE_ARG
+#define MH_POSE_LOAD() ((void)0)
+#elif defined(MH_ARTIC_POSE_TU)
 #define MH_POSE_KERNEL(name) name##_pose
 #define MH_POSE_ARG , const double* __restrict__ poseg
 #define MH_POSE_LOAD() pose_load(Y, g, poseg + 7 * (size_t)b)
@@ -941,7 +950,11 @@ void MH_POSE_KERNEL(k_artic_fwd_dyn)(const Model* __restrict__ Mg, int B, const 
   extern __shared__ double g[];
   const int b = blockIdx.x;
   if (b >= B) return;
+#ifdef MH_ARTIC_PARAMS_TU
+  const Model& M = Mg[b];
+#else
   const Model& M = *Mg;
+#endif
   const int nj = M.m.nj, lane = lane_id();
   const Lay Y(nj);
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = qdg[(size_t)b * nj + lane]; }
@@ -971,7 +984,11 @@ void MH_POSE_KERNEL(k_artic_jacobian)(const Model* __restrict__ Mg, int B, const
   extern __shared__ double g[];
   const int b = blockIdx.x;
   if (b >= B) return;
+#ifdef MH_ARTIC_PARAMS_TU
+  const Model& M = Mg[b];
+#else
   const Model& M = *Mg;
+#endif
   const int nj = M.m.nj, lane = lane_id();
   const Lay Y(nj);
   if (lane < nj) { g[Y.q + lane] = qg[(size_t)b * nj + lane]; g[Y.qd + lane] = 0.0; }
@@ -1047,13 +1064,17 @@ enum mh_artic_family { MH_ARTIC_FAM_NONE = 0,  // no geometry, or spheres agains
                        MH_ARTIC_FAM_BOX,       // box primitives (mh_artic_box.hip)
                        MH_ARTIC_FAM_PAIR,      // sphere pairs between links or a plane mask (mh_artic_pair.hip), and every model with geometry created under mh_debug_set(13, 1)
                        MH_ARTIC_FAM_BSP,       // a box-sphere pair or a static box (mh_artic_bsp.hip), and every model with geometry created under mh_debug_set(14, 1)
-                       MH_ARTIC_FAM_RP };      // the contact report (mh_artic_rp.hip): every batch of mh_artic_batch_create_report, and one that would take BSP created under mh_debug_set(19, 1)
+                       MH_ARTIC_FAM_RP,        // the contact report (mh_artic_rp.hip): every batch of mh_artic_batch_create_report, and one that would take BSP created under mh_debug_set(19, 1)
+                       MH_ARTIC_FAM_PW };      // per-world parameters (mh_artic_pw.hip): every batch of mh_artic_batch_create_params, and one that would take RP created under mh_debug_set(20, 1)
 
 struct mh_artic_batch {
   int device;                // the HIP device the batch lives on (current at create); every entry point runs there (MH_ON_DEVICE)
   int B, nj, nspheres, cstab, algorithm;
   mh_artic_family family;    // fixed at create, and with it the workspace layout (artic_geom_family: what a step goes through)
   int report;                // created by mh_artic_batch_create_report: mh_artic_batch_step_report may hand it rows to write
+  int params;                // d_model holds B images, one per world, and the step goes through MH_ARTIC_FAM_PW: 1 = created by mh_artic_batch_create_params
+                             // (the setters take it), 2 = created under mh_debug_set(20, 1) with every image the model's; 0 = one shared image
+  mh_artic_model model;      // the shared model as it was handed to create: the topology every record is written into and validated against
   mh::artic::Model* d_model;
   double* d_q; double* d_qd; mh_world_aux* d_aux;
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
@@ -1094,6 +1115,17 @@ size_t artic_pair_lds_bytes(int nj);
 MH_ARTIC_REPORT_LAUNCHER(artic_rp_launch); MH_ARTIC_REPORT_LAUNCHER(artic_rp_pose_launch);
 size_t artic_rp_lds_bytes(int nj);
 size_t artic_rp_pose_lds_bytes(int nj);
+// the per-world-parameters family (mh_artic_pw.hip, mh_artic_pw_pose.hip): the report family's launchers and image sizes over B images, the
+// kernels of mh_artic_batch_fwd_dyn / link_poses / jacobian that read world b's image (null stream, as the pose forms above), and the scatter of
+// mh_artic_batch_set_params_dev (records rec[0 .. count) into images first ..; the launch's hipGetLastError)
+MH_ARTIC_REPORT_LAUNCHER(artic_pw_launch); MH_ARTIC_REPORT_LAUNCHER(artic_pw_pose_launch);
+size_t artic_pw_lds_bytes(int nj);
+size_t artic_pw_pose_lds_bytes(int nj);
+hipError_t artic_pw_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
+hipError_t artic_pw_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
+hipError_t artic_pw_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
+hipError_t artic_pw_pose_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
+hipError_t artic_pw_scatter_launch(mh_artic_batch* ab, void* stream, const mh_artic_params* dev, int first, int count);
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
 static int check_drive(const mh_artic_drive* d, int nsteps)
@@ -1157,7 +1189,33 @@ MH_ARTIC_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
 #if defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_BSP_TU) && !defined(MH_ARTIC_POSE_TU)
 size_t artic_pair_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
 #endif
-#if defined(MH_ARTIC_REPORT_TU) && defined(MH_ARTIC_POSE_TU)
+#if defined(MH_ARTIC_PARAMS_TU)
+// the per-world-parameters code objects: their image size, and the launches of their fwd_dyn / jacobian kernels
+#ifdef MH_ARTIC_POSE_TU
+#define MH_PW_NAME(stem) artic_pw_pose_##stem
+#define MH_PW_KERNEL(name) name##_pw_pose
+#define MH_PW_POSE_PTR , (const double*)ab->d_pose
+#else
+#define MH_PW_NAME(stem) artic_pw_##stem
+#define MH_PW_KERNEL(name) name##_pw
+#define MH_PW_POSE_PTR
+#endif
+size_t MH_PW_NAME(lds_bytes)(int nj) { return mh::artic::lds_bytes_contacts(nj); }
+hipError_t MH_PW_NAME(fwd_dyn_launch)(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok)
+{
+  namespace ar = mh::artic;
+  hipLaunchKernelGGL(ar::MH_PW_KERNEL(k_artic_fwd_dyn), dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+                     (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, d_tau, d_qdd, d_H, d_poses, d_ok MH_PW_POSE_PTR);
+  return hipGetLastError();
+}
+hipError_t MH_PW_NAME(jacobian_launch)(mh_artic_batch* ab, int link, const double* d_p, double* d_J)
+{
+  namespace ar = mh::artic;
+  hipLaunchKernelGGL(ar::MH_PW_KERNEL(k_artic_jacobian), dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+                     (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, link, d_p, d_J MH_PW_POSE_PTR);
+  return hipGetLastError();
+}
+#elif defined(MH_ARTIC_REPORT_TU) && defined(MH_ARTIC_POSE_TU)
 size_t artic_rp_pose_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
 #elif defined(MH_ARTIC_REPORT_TU)
 size_t artic_rp_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }

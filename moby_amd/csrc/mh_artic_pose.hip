@@ -94,6 +94,11 @@ int mh_artic_batch_set_base_coords(mh_artic_batch* ab, int coords)
   const size_t B = (size_t)ab->B;
   std::vector<double> h(7 * B);
   for (size_t b = 0; b < B; b++) for (int k = 0; k < 7; k++) h[7 * b + k] = P0[k];
+  if (ab->params) {                                            // per-world parameters: every world's pose from its own image (the topology checked above is shared)
+    std::vector<ar::Model> images(B);
+    MH_HIP(hipMemcpy(images.data(), ab->d_model, B * sizeof(ar::Model), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; b++) { for (int k = 0; k < 3; k++) h[7 * b + k] = images[b].m.trel[0][k]; quat_of_R(images[b].m.Rrel[3], h.data() + 7 * b + 3); }
+  }
   double* d = nullptr;
   MH_HIP(hipMalloc((void**)&d, 7 * B * sizeof(double)));
   hipError_t e = hipMemcpy(d, h.data(), 7 * B * sizeof(double), hipMemcpyHostToDevice);
