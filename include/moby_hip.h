@@ -317,6 +317,9 @@ int  mh_debug_set(int key, int value);   /* key 2: block LCP solver (n > 64) thr
                                             key 20: articulated batches that would take the contact-report kernels stepped by the per-world-parameters kernels, mh_artic_pw*.hip, with
                                                    B images all equal to the model (1, for batches created after it; default 0: only batches of mh_artic_batch_create_params;
                                                    for A/B runs; include/moby_hip_artic.h, "Per-world parameters").
+                                            key 21: articulated batches that would take the per-world-parameters kernels stepped by the link-wrench kernels, mh_artic_wr*.hip, with a
+                                                   NULL wrench (1, for batches created after it; default 0: only batches of mh_artic_batch_create_wrench; for A/B runs;
+                                                   include/moby_hip_artic.h, "Link wrenches").
                                             None of the switches changes a result */
 void mh_scene_defaults(mh_scene* s);   /* zero + the reference's default tolerances */
 void mh_world_aux_init(mh_world_aux* a, uint32_t seed);

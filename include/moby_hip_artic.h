@@ -395,6 +395,59 @@ int mh_artic_batch_set_params(mh_artic_batch* ab, const mh_artic_params* host, i
  * coordinates trel[0] and Rrel[3] are not read.  MH_ERR_INVALID_ARG: a batch not created by mh_artic_batch_create_params, a range outside the batch. */
 int mh_artic_batch_set_params_dev(mh_artic_batch* ab, void* stream, const mh_artic_params* dev, int first, int count);
 
+/* Link wrenches.  A force that acts on a LINK, inside the step: a shove against the torso, a rotor's thrust in the axes of the arm that carries it, a
+ * tether's tug, velocity-proportional damping of the links -- what a controller of the reference does with link->add_force(...) and what
+ * DampingForce::add_force does for an articulated body (DampingForce.cpp:32-51 and its articulated branch), both inside precalc_fwd_dyn, once per
+ * mini-step.  The wrench is evaluated once per mini-step inside the forward dynamics, immediately after the link frames of that mini-step's q exist:
+ * q has been advanced by the position update, qd is still the mini-step's starting velocity, the drive's tau is already evaluated.  Every operation
+ * is rounded on its own, three-term sums are (a + b) + c, and an absent term is left out, not added as zero.  It enters the dynamics as a generalized
+ * force and nowhere else: compute_X, the impact handler, restitution, conservative advancement and the stabiliser never read it (nor the drive).
+ * For world w, schedule row r and link i (R_i, x_i the link frame; S_j the motion subspaces about the model origin, [angular; linear];
+ * c_i = x_i + R_i com_i the link's COM in the model frame; V_i = [w_i; v_i] the link's spatial velocity about the model origin):
+ *   damping (MH_LINK_DAMPING)   vc = v_i + w_i x c_i;  vi = R_i' vc, wi = R_i' w_i;  fb = vi * (-(kl + |vi| klsq)), tb = wi * (-(ka + |wi| kasq)),
+ *                               |a| = sqrt((a0^2 + a1^2) + a2^2);  F = R_i fb, T = R_i tb
+ *   the caller's (MH_LINK_WRENCH)  (f, n) = entry ((r B + w) nj + i) 6 of w: f acts at the link's COM, n is a free torque, model axes; with
+ *                               MH_LINK_WRENCH_LINK_AXES both are rotated first, f <- R_i f, n <- R_i n.  F = F + f, T = T + n (F = f, T = n without damping)
+ *   F6_i = [T + c_i x F; F]     (the cross product first, then the sum)
+ *   tau_x[j] = sum of dot6(S_j, F6_i) over the links i, in increasing i, on whose path to the base joint j lies (i itself included), from 0.0
+ *   tau_j = tau_drive_j + tau_x[j], or tau_x[j] alone in an undriven launch
+ * and H qdd = tau - C is solved as ever, by either algorithm.  The virtual links of a floating base are links like any other: a caller zeroes their
+ * coefficients, and a wrench on link 5 is a wrench on the base.  Gains kl, ka, klsq, kasq are per world and link (B x nj each).
+ * A batch that takes wrenches is one of mh_artic_batch_create_wrench: a per-world-parameters batch (every rule of "Per-world parameters" holds for it:
+ * set_params, set_params_dev, pose coordinates, drives, the report) that steps through code objects of its own (mh_artic_wr.hip, mh_artic_wr_pose.hip:
+ * the per-world-parameters kernels with MH_ARTIC_WRENCH_TU).  The LDS image of a world does not grow: F6 lives in the bias forces' region, which the
+ * bias pass rewrites afterwards, and tau_x is added into the slot the drive writes.  Coefficients and schedule rows are read from global memory at
+ * every mini-step.  Every other batch launches what it launched.  Key 21 of mh_debug_set sends batches that would take the per-world-parameters
+ * kernels through these objects with a NULL wrench (A/B runs; no result changes).
+ * NOT built: StokesDragForce on articulated bodies (the reference's articulated branch dereferences a null pointer, StokesDragForce.cpp:55-62: there
+ * is no behaviour to reproduce); <DampingForce> read from scene files by mh_io_load_xml_artic; a force at a point other than the COM (the caller adds
+ * r x f to n); wrenches in mh_artic_batch_fwd_dyn; a wrench form of the plain, non-contact kernels (the family inherits the per-world-parameters
+ * family's measured 6.9x on a robot without geometry); the large-world stepper (moby_hip_stack.h). */
+/* (no existing layout changes, so MH_VERSION stays as it is; a caller that needs to know tests this macro) */
+#define MH_ARTIC_WRENCH 1
+#define MH_LINK_WRENCH            1
+#define MH_LINK_DAMPING           2
+#define MH_LINK_WRENCH_LINK_AXES  4   /* only with MH_LINK_WRENCH */
+typedef struct mh_artic_wrench {
+  int terms;                  /* MH_LINK_* bits; 0 = none: nothing else is read */
+  int rows;                   /* as mh_artic_drive.rows: 1 = held, >= nsteps = row s for all mini-steps of step s */
+  const double* w;            /* DEVICE, rows x B x nj x 6: fx fy fz nx ny nz */
+  const double* kl;           /* DEVICE, B x nj each: linear, angular, quadratic linear, quadratic angular damping */
+  const double* ka;
+  const double* klsq;
+  const double* kasq;
+} mh_artic_wrench;
+/* mh_artic_batch_create_params with every one of its refusals (flags: MH_ARTIC_CREATE_REPORT or 0); the batch it returns also takes wrenches. */
+int mh_artic_batch_create_wrench(const mh_artic_model* model, const mh_artic_params* host, int B, int flags, mh_artic_batch** out);
+/* mh_artic_batch_step_report plus the wrench (DEVICE pointers on the batch's device, read in stream order).  wrench == NULL or terms == 0: the same
+ * kernels with no force, results equal to the per-world-parameters batch bit for bit.  MH_ERR_INVALID_ARG, with a message that names the field, all
+ * checked before the device is looked for: a wrench on a batch not created by mh_artic_batch_create_wrench, unknown bits in terms,
+ * MH_LINK_WRENCH_LINK_AXES without MH_LINK_WRENCH, a NULL pointer for a requested term (kl, ka, klsq and kasq are all four required for damping),
+ * rows < 1 or 1 < rows < nsteps, report_dev on a batch without the report flag.  mh_artic_batch_step, _step_driven and _step_report take such a
+ * batch and apply no wrench. */
+int mh_artic_batch_step_wrench(mh_artic_batch* ab, void* stream, double dt, int nsteps,
+                               const mh_artic_drive* drive, const mh_artic_wrench* wrench, double* report_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,8 @@ SYMBOLS = {
     "mh_artic_batch_create_params": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(_vp)]),
     "mh_artic_batch_set_params": (_i, [_vp, _vp, _i, _i]),
     "mh_artic_batch_set_params_dev": (_i, [_vp, _vp, _vp, _i, _i]),
+    "mh_artic_batch_create_wrench": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(_vp)]),
+    "mh_artic_batch_step_wrench": (_i, [_vp, _vp, _d, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

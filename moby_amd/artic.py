@@ -153,6 +153,42 @@ def _is_tensor(a):
     return type(a).__module__.startswith("torch")
 
 
+MH_LINK_WRENCH, MH_LINK_DAMPING, MH_LINK_WRENCH_LINK_AXES = 1, 2, 4
+
+
+class mh_artic_wrench(ctypes.Structure):
+    _fields_ = [("terms", ctypes.c_int), ("rows", ctypes.c_int), ("w", ctypes.c_void_p), ("kl", ctypes.c_void_p), ("ka", ctypes.c_void_p),
+                ("klsq", ctypes.c_void_p), ("kasq", ctypes.c_void_p)]
+
+
+class LinkWrench:
+    """Forces on links evaluated inside the step, once per mini-step (include/moby_hip_artic.h, "Link wrenches", mh_artic_wrench).
+    w: (B, nj, 6) held for the whole launch, or (R, B, nj, 6) whose row s acts during step s (R >= nsteps): fx fy fz at the link's COM and a free
+    torque nx ny nz, in model axes, or in the link's own axes with link_axes=True.  kl, ka, klsq, kasq: (B, nj) each, all four or none -- the
+    links' linear, angular and quadratic damping.  The terms are independent; an absent one is not in the sum.  float64 contiguous torch tensors
+    on the batch's device, for a batch created with wrench=True."""
+    _DAMP = ("kl", "ka", "klsq", "kasq")
+
+    def __init__(self, w=None, kl=None, ka=None, klsq=None, kasq=None, link_axes=False):
+        self.arrays = dict(w=w, kl=kl, ka=ka, klsq=klsq, kasq=kasq)
+        given = [self.arrays[k] is not None for k in self._DAMP]
+        if any(given) and not all(given):
+            raise ValueError("LinkWrench: damping needs kl, ka, klsq and kasq")
+        if link_axes and w is None:
+            raise ValueError("LinkWrench: link_axes without w")
+        self.terms = (MH_LINK_WRENCH if w is not None else 0) | (MH_LINK_DAMPING if all(given) else 0) | (MH_LINK_WRENCH_LINK_AXES if link_axes else 0)
+        self.shapes = {k: tuple(a.shape) for k, a in self.arrays.items() if a is not None}
+        self.rows = self.shapes["w"][0] if len(self.shapes.get("w", ())) == 4 else 1
+
+    def check(self, B, nj, nsteps):
+        for k, sh in self.shapes.items():
+            want = [(B, nj, 6), (self.rows, B, nj, 6)] if k == "w" else [(B, nj)]
+            if sh not in want:
+                raise ValueError("LinkWrench.%s: shape %r, expected %s" % (k, sh, " or ".join(map(str, want))))
+        if 1 < self.rows < nsteps:
+            raise ValueError("LinkWrench.w: %d schedule rows for %d steps (one held row, or at least one per step)" % (self.rows, nsteps))
+
+
 class mh_io_artic(ctypes.Structure):
     _fields_ = [("model", mh_artic_model), ("link_id", (ctypes.c_char * mio.MH_IO_ID_LEN) * _NJ),
                 ("joint_id", (ctypes.c_char * mio.MH_IO_ID_LEN) * _NJ)]
@@ -358,8 +394,10 @@ class ArticBatch:
     carried -- three Euler-like angles in the virtual joints, or a per-world pose (p, Q) the virtual joints are folded into after every step
     (include/moby_hip_artic.h, MH_ARTIC_BASE_POSE: no singularity at a quarter turn of the middle hinge).  "pose" folds q / qd as given."""
 
-    def __init__(self, model, q, qd, aux=None, base_coords="angles", report=False, params=None):
-        """params: B records of PARAMS_DTYPE (make_params), one per world, or True for records that all equal the model -- a batch of
+    def __init__(self, model, q, qd, aux=None, base_coords="angles", report=False, params=None, wrench=False):
+        """wrench=True: a batch of mh_artic_batch_create_wrench -- a params batch (records from params=, or all equal to the model) that also takes
+        step(..., wrench=LinkWrench(...)) (include/moby_hip_artic.h, "Link wrenches").
+        params: B records of PARAMS_DTYPE (make_params), one per world, or True for records that all equal the model -- a batch of
         mh_artic_batch_create_params: world w steps the model with record w written into it (include/moby_hip_artic.h, "Per-world parameters");
         set_params / set_params_dev replace records later.
         report=True: a batch of mh_artic_batch_create_report -- it steps through the report kernels and step(..., report=tensor) fills the
@@ -373,10 +411,11 @@ class ArticBatch:
         self.handle = ctypes.c_void_p()
         self._staged = None
         self.report = bool(report)
-        self.params = params is not None
+        self.wrench = bool(wrench)
+        self.params = params is not None or self.wrench
         if self.params:
-            p = None if params is True else _records(params, self.B)
-            _lib.check(lib.mh_artic_batch_create_params(ctypes.byref(model), None if p is None else p.ctypes.data, self.B, MH_ARTIC_CREATE_REPORT if report else 0, ctypes.byref(self.handle)))
+            p = None if params is True or params is None else _records(params, self.B)
+            _lib.check((lib.mh_artic_batch_create_wrench if self.wrench else lib.mh_artic_batch_create_params)(ctypes.byref(model), None if p is None else p.ctypes.data, self.B, MH_ARTIC_CREATE_REPORT if report else 0, ctypes.byref(self.handle)))
         else:
             _lib.check((lib.mh_artic_batch_create_report if report else lib.mh_artic_batch_create)(ctypes.byref(model), self.B, ctypes.byref(self.handle)))
         self.report_slots = report_slots(model)
@@ -441,12 +480,13 @@ class ArticBatch:
             raise ValueError("expected a contiguous float64 tensor of shape %r on %s, got %s %r on %s" % (tuple(shape), self._device(), t.dtype, tuple(t.shape), t.device))
         return t.data_ptr()
 
-    def step(self, dt, nsteps=1, stream=None, drive=None, report=None):
+    def step(self, dt, nsteps=1, stream=None, drive=None, report=None, wrench=None):
         """nsteps x TimeSteppingSimulator::step(dt) in one launch on `stream` (a raw HIP stream handle; None = the null stream).
         drive: a Drive for this launch; None = the drive stored by set_drive (none: undriven).  A torch loop passes
         torch.cuda.current_stream().cuda_stream here and to state_into, so that both run in order with its own kernels.
         report: a float64 contiguous (B, nsteps, report_slots, 8) torch tensor on the batch's device that receives the launch's contact report
-        (a batch created with report=True only); None = nothing is written."""
+        (a batch created with report=True only); None = nothing is written.
+        wrench: a LinkWrench of device tensors for this launch (a batch created with wrench=True only); None = no force on the links."""
         lib = _lib.load()
         rp = None
         if report is not None:
@@ -471,7 +511,16 @@ class ArticBatch:
                     staged.append(a)
                 setattr(d, k, self._tensor_ptr(a, a.shape))
             self._staged = staged or None
-        if self.report:
+        if wrench is not None:
+            if not self.wrench:
+                raise ValueError("a wrench needs a batch created with wrench=True")
+            wrench.check(self.B, self.nj, int(nsteps))
+            w = mh_artic_wrench(terms=wrench.terms, rows=wrench.rows)
+            for k, a in wrench.arrays.items():
+                if a is not None:
+                    setattr(w, k, self._tensor_ptr(a, a.shape))
+            _lib.check(lib.mh_artic_batch_step_wrench(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d), ctypes.byref(w), rp))
+        elif self.report:
             _lib.check(lib.mh_artic_batch_step_report(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d), rp))
         else:
             _lib.check(lib.mh_artic_batch_step_driven(self.handle, stream, float(dt), int(nsteps), None if d is None else ctypes.byref(d)))

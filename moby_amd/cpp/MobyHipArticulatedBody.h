@@ -114,6 +114,16 @@ class BatchedArticulatedBody {
   { return new BatchedArticulatedBody(model, B, q, qd, report, true, params); }
   /// Replaces the records of copies first .. first + count - 1 (HOST records, validated; a refused record leaves every copy as it was)
   void set_params(const mh_artic_params* params, int first, int count) { if (mh_artic_batch_set_params(_ab, params, first, count) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  /// A with_params batch that also takes forces on its links (mh_artic_batch_create_wrench; include/moby_hip_artic.h, "Link wrenches"): what a
+  /// controller of the reference does with link->add_force(...), and DampingForce on an articulated body.  params NULL: every record = the model.
+  static BatchedArticulatedBody* with_wrench(const mh_artic_model& model, const mh_artic_params* params, int B, const double* q, const double* qd, bool report = false)
+  { return new BatchedArticulatedBody(model, B, q, qd, report, true, params, true); }
+  /// step(dt, nsteps) with the wrench applied inside every mini-step: its pointers are DEVICE arrays the caller owns (this header knows no HIP),
+  /// read in the order of the null stream; report_dev as step_report's, or NULL.  With the drive of set_drive when one is set.
+  double step_wrench(double dt, int nsteps, const mh_artic_wrench& wrench, double* report_dev = NULL) {
+    if (mh_artic_batch_step_wrench(_ab, NULL, dt, nsteps, NULL, &wrench, report_dev) != MH_OK) throw std::runtime_error(mh_last_error());
+    _dirty = true; return dt;
+  }
   /// nspheres + nboxes + npairs of a batch made by with_report: the rows per world and step
   int report_slots() const { return _nslots; }
   /// step(dt, nsteps) with the launch's rows written to report_dev, a DEVICE array of B x nsteps x report_slots() x MH_REPORT_PAIR doubles that the
@@ -145,12 +155,13 @@ class BatchedArticulatedBody {
  private:
   BatchedArticulatedBody(const BatchedArticulatedBody&);
   BatchedArticulatedBody& operator=(const BatchedArticulatedBody&);
-  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd, bool report, bool with_records = false, const mh_artic_params* params = NULL)
+  BatchedArticulatedBody(const mh_artic_model& model, int B, const double* q, const double* qd, bool report, bool with_records = false, const mh_artic_params* params = NULL, bool wrench = false)
     : _nj(model.nj), _B(B), _ab(NULL), _dirty(false), _nslots(-1)
-  { init(model, q, qd, report, with_records, params); }
-  void init(const mh_artic_model& model, const double* q, const double* qd, bool report, bool with_records = false, const mh_artic_params* params = NULL)
+  { init(model, q, qd, report, with_records, params, wrench); }
+  void init(const mh_artic_model& model, const double* q, const double* qd, bool report, bool with_records = false, const mh_artic_params* params = NULL, bool wrench = false)
   {
-    const int rc = with_records ? mh_artic_batch_create_params(&model, params, _B, report ? MH_ARTIC_CREATE_REPORT : 0, &_ab)
+    const int rc = wrench ? mh_artic_batch_create_wrench(&model, params, _B, report ? MH_ARTIC_CREATE_REPORT : 0, &_ab)
+                 : with_records ? mh_artic_batch_create_params(&model, params, _B, report ? MH_ARTIC_CREATE_REPORT : 0, &_ab)
                                 : report ? mh_artic_batch_create_report(&model, _B, &_ab) : mh_artic_batch_create(&model, _B, &_ab);
     if (rc != MH_OK) throw std::runtime_error(mh_last_error());
     if (report) _nslots = mh_artic_report_slots(&model);

@@ -2,8 +2,8 @@
 // kernels without link geometry beyond spheres (mh_artic_dev.h with no switch set).
 //
 // mh_artic_batch_step launches those kernels itself, hands a batch in pose coordinates to mh_artic_pose.hip and one whose step goes through a
-// geometry family to artic_geom_step below, the one router to the ten geometry code objects (mh_artic_{box,pair,bsp,rp,pw}[_pose].hip);
-// mh_artic_batch_step_driven (mh_artic_drive.hip) calls the same router, and so does mh_artic_batch_step_report, with the rows.
+// geometry family to artic_geom_step below, the one router to the twelve geometry code objects (mh_artic_{box,pair,bsp,rp,pw,wr}[_pose].hip);
+// mh_artic_batch_step_driven (mh_artic_drive.hip) calls the same router, and so do mh_artic_batch_step_report, with the rows, and mh_artic_batch_step_wrench, with the wrench.
 #include "mh_artic_dev.h"
 #include <cstdarg>
 #include <cstdio>
@@ -11,11 +11,17 @@
 // Every step of a batch whose family (artic_geom_family) is box, pair or box-sphere, undriven and driven: the family's checks, then the launcher
 // of that family in the batch's coordinates.  To add a family: its switch and token in two wrapper files, an enumerator, its precedence in
 // mh_artic_batch_create, and a case here.
-int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report)
+int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report, const mh_artic_wrench* wrench)
 {
   namespace ar = mh::artic;
   const bool pose = ab->base_coords == MH_ARTIC_BASE_POSE;
   const mh_artic_family fam = artic_geom_family(ab);
+  if (fam == MH_ARTIC_FAM_WR) {                                    // link wrenches: the per-world-parameters kernels with the wrench, the same workspace and image
+    if (!ab->d_ws || ab->ws_stride < ar::WS_PAIR) return fail(MH_ERR_INVALID_ARG, "the batch's workspace is not sized for the link-wrench kernels");
+    const size_t lds = pose ? artic_wr_pose_lds_bytes(ab->nj) : artic_wr_lds_bytes(ab->nj);
+    if (lds > 65536) return fail(MH_ERR_INVALID_ARG, "the link-wrench kernels' LDS image (%zu bytes) exceeds a workgroup's 64 KB", lds);
+    return pose ? artic_wr_pose_launch(ab, stream, dt, nsteps, D, report, wrench) : artic_wr_launch(ab, stream, dt, nsteps, D, report, wrench);
+  }
   if (fam == MH_ARTIC_FAM_PW) {                                    // per-world parameters: the report kernels over B images, an LDS image of their own
     if (!ab->d_ws || ab->ws_stride < ar::WS_PAIR) return fail(MH_ERR_INVALID_ARG, "the batch's workspace is not sized for the per-world-parameters kernels");
     const size_t lds = pose ? artic_pw_pose_lds_bytes(ab->nj) : artic_pw_lds_bytes(ab->nj);
@@ -219,7 +225,8 @@ static int artic_check_model(const mh_artic_model* model, bool report, bool para
 
 // mh_artic_batch_create (report false) and mh_artic_batch_create_report (true), and mh_artic_batch_create_params (params true; host: B records or
 // NULL = the model's): one text, the report and the records only decide the family and the number of images
-static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out, bool report, bool params = false, const mh_artic_params* host = nullptr)
+// (wrench: mh_artic_batch_create_wrench, a params batch whose step goes through the link-wrench family)
+static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch** out, bool report, bool params = false, const mh_artic_params* host = nullptr, bool wrench = false)
 {
   namespace ar = mh::artic;
   if (!out) return fail(MH_ERR_INVALID_ARG, "null out");
@@ -241,12 +248,13 @@ static int artic_batch_create(const mh_artic_model* model, int B, mh_artic_batch
   const size_t nimg = images.empty() ? 1 : (size_t)B;
   const int nj = model->nj;
   const bool use_rp = plan.use_rp, use_bsp = plan.use_bsp, use_pair = plan.use_pair, use_pw = params || pw20;
+  const bool use_wr = wrench || (use_pw && mh_g_debug_artic_wr != 0);           // mh_debug_set(21, 1): the link-wrench kernels with a NULL wrench
   if (mh_device_count() <= 0) return fail(MH_ERR_NO_DEVICE, "no HIP device visible");
   { const int rc = init_pow10(); if (rc != MH_OK) return rc; }             // this code object's powers of ten, before its first launch on the device
   mh_artic_batch* ab = new mh_artic_batch();
   if (hipGetDevice(&ab->device) != hipSuccess) { delete ab; return fail(MH_ERR_HIP, "hipGetDevice failed"); }
-  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->family = use_pw ? MH_ARTIC_FAM_PW : use_rp ? MH_ARTIC_FAM_RP : use_bsp ? MH_ARTIC_FAM_BSP : use_pair ? MH_ARTIC_FAM_PAIR : model->nboxes > 0 ? MH_ARTIC_FAM_BOX : MH_ARTIC_FAM_NONE; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
-  ab->report = report ? 1 : 0; ab->params = params ? 1 : pw20 ? 2 : 0; ab->model = *model;
+  ab->B = B; ab->nj = nj; ab->algorithm = model->algorithm; ab->nspheres = model->nspheres; ab->family = use_wr ? MH_ARTIC_FAM_WR : use_pw ? MH_ARTIC_FAM_PW : use_rp ? MH_ARTIC_FAM_RP : use_bsp ? MH_ARTIC_FAM_BSP : use_pair ? MH_ARTIC_FAM_PAIR : model->nboxes > 0 ? MH_ARTIC_FAM_BOX : MH_ARTIC_FAM_NONE; ab->cstab = model->cstab_max_iterations != 0 ? 1 : 0; ab->d_model = nullptr; ab->d_q = nullptr; ab->d_qd = nullptr; ab->d_aux = nullptr; ab->d_ws = nullptr;
+  ab->report = report ? 1 : 0; ab->params = params ? 1 : pw20 ? 2 : 0; ab->model = *model; ab->wrench = wrench ? 1 : 0;
   std::memset(&ab->drive, 0, sizeof(ab->drive)); ab->d_drive = nullptr;
   ab->base_coords = MH_ARTIC_BASE_ANGLES; ab->d_pose = nullptr;
   const size_t sB = (size_t)B;
@@ -286,6 +294,13 @@ int mh_artic_batch_create_params(const mh_artic_model* model, const mh_artic_par
   if (out) *out = nullptr;
   if (flags & ~MH_ARTIC_CREATE_REPORT) return fail(MH_ERR_INVALID_ARG, "unknown bits 0x%x in flags (MH_ARTIC_CREATE_REPORT or 0)", flags & ~MH_ARTIC_CREATE_REPORT);
   return artic_batch_create(model, B, out, (flags & MH_ARTIC_CREATE_REPORT) != 0, true, host);
+}
+
+int mh_artic_batch_create_wrench(const mh_artic_model* model, const mh_artic_params* host, int B, int flags, mh_artic_batch** out)
+{
+  if (out) *out = nullptr;
+  if (flags & ~MH_ARTIC_CREATE_REPORT) return fail(MH_ERR_INVALID_ARG, "unknown bits 0x%x in flags (MH_ARTIC_CREATE_REPORT or 0)", flags & ~MH_ARTIC_CREATE_REPORT);
+  return artic_batch_create(model, B, out, (flags & MH_ARTIC_CREATE_REPORT) != 0, true, host, true);
 }
 
 // the checks the two record setters share
@@ -388,6 +403,39 @@ int mh_artic_batch_step_report(mh_artic_batch* ab, void* stream, double dt, int 
   if (nsteps == 0) return MH_OK;
   if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
   return artic_geom_step(ab, stream, dt, nsteps, D.terms != 0 ? &D : nullptr, report_dev);
+}
+
+// the checks of a wrench that need no batch (nsteps as check_drive's)
+static int check_wrench(const mh_artic_wrench* w, int nsteps)
+{
+  const int known = MH_LINK_WRENCH | MH_LINK_DAMPING | MH_LINK_WRENCH_LINK_AXES;
+  if (w->terms & ~known) return fail(MH_ERR_INVALID_ARG, "wrench: unknown bits 0x%x in terms", w->terms & ~known);
+  if ((w->terms & MH_LINK_WRENCH_LINK_AXES) && !(w->terms & MH_LINK_WRENCH)) return fail(MH_ERR_INVALID_ARG, "wrench: terms has MH_LINK_WRENCH_LINK_AXES without MH_LINK_WRENCH");
+  if ((w->terms & MH_LINK_WRENCH) && !w->w) return fail(MH_ERR_INVALID_ARG, "wrench: MH_LINK_WRENCH with a NULL w");
+  if (w->terms & MH_LINK_DAMPING) {
+    const char* name = !w->kl ? "kl" : !w->ka ? "ka" : !w->klsq ? "klsq" : !w->kasq ? "kasq" : nullptr;
+    if (name) return fail(MH_ERR_INVALID_ARG, "wrench: MH_LINK_DAMPING with a NULL %s (kl, ka, klsq and kasq are all required)", name);
+  }
+  if (w->rows < 1) return fail(MH_ERR_INVALID_ARG, "wrench: rows = %d < 1", w->rows);
+  if (nsteps >= 0 && w->rows > 1 && w->rows < nsteps) return fail(MH_ERR_INVALID_ARG, "wrench: %d schedule rows for %d steps (1 = held, or at least one per step)", w->rows, nsteps);
+  return MH_OK;
+}
+
+int mh_artic_batch_step_wrench(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* drive, const mh_artic_wrench* wrench, double* report_dev)
+{
+  const bool has = wrench && wrench->terms != 0;
+  if (has) { const int rc = check_wrench(wrench, nsteps); if (rc != MH_OK) return rc; }       // what needs no batch first, so that it is refused without one
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  if (has && !ab->wrench) return fail(MH_ERR_INVALID_ARG, "wrench: the batch was not created by mh_artic_batch_create_wrench");
+  if (report_dev && !ab->report) return fail(MH_ERR_INVALID_ARG, "report_dev: a report needs a batch created with MH_ARTIC_CREATE_REPORT (or by mh_artic_batch_create_report)");
+  if (!has) return mh_artic_batch_step_report(ab, stream, dt, nsteps, drive, report_dev);       // the same kernels, a NULL wrench
+  const mh_artic_drive& D = drive ? *drive : ab->drive;
+  if (nsteps < 0) return fail(MH_ERR_INVALID_ARG, "negative step count");
+  if (D.terms != 0) { const int rc = check_drive(&D, nsteps); if (rc != MH_OK) return rc; }
+  if (nsteps == 0) return MH_OK;
+  if (!(dt > 0.0)) return fail(MH_ERR_INVALID_ARG, "dt must be > 0");
+  MH_ON_DEVICE(ab);
+  return artic_geom_step(ab, stream, dt, nsteps, D.terms != 0 ? &D : nullptr, report_dev, wrench);
 }
 
 int mh_artic_batch_set_drive(mh_artic_batch* ab, const mh_artic_drive* host_drive)

@@ -981,6 +981,9 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #ifdef MH_ARTIC_REPORT_TU
                            , double* rep                        // this world's rows of step s in the caller's report, or NULL
 #endif
+#ifdef MH_ARTIC_WRENCH_TU
+                           , const mh_artic_wrench* Wp          // the link wrench (mh_artic_wr.hip), or NULL: evaluated inside the forward dynamics, after kin_inertia
+#endif
                            )
 {
   const mh_artic_model& m = M.m;
@@ -1022,7 +1025,11 @@ MH_DEV double do_mini_step(const Model& M, const Lay& Y, const LayC& Z, double* 
 #elif defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
   if (Dp) drive_tau(*Dp, B, b, s, Y, g);
   const double* tw = Dp ? g + Y.qdd : nullptr;
+#ifdef MH_ARTIC_WRENCH_TU
+  const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, tw, Wp, B, b, s) : dynamics(M, Y, g, tw, Wp, B, b, s);
+#else
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, tw) : dynamics(M, Y, g, tw);
+#endif
 #else
   const bool ok = (m.algorithm == MH_ARTIC_FSAB) ? dynamics_aba(M, Y, g, nullptr) : dynamics(M, Y, g, nullptr);
 #endif
@@ -1462,6 +1469,9 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #ifdef MH_ARTIC_REPORT_TU
                                 , double* __restrict__ report   // B x nsteps x nslots x MH_REPORT_PAIR rows, or NULL: nothing is written, the steps are the same
 #endif
+#ifdef MH_ARTIC_WRENCH_TU
+                                , const mh_artic_wrench* Wp     // the link wrench of the launch, or NULL: no force, the steps of the per-world-parameters kernels
+#endif
                                 )
 {
   extern __shared__ double g[];
@@ -1512,7 +1522,9 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #ifdef MH_ARTIC_DRIVE_TU
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, D, B, b, s));
 #elif defined(MH_ARTIC_POSE_TU) || defined(MH_ARTIC_BOX_TU)
-#ifdef MH_ARTIC_REPORT_TU
+#ifdef MH_ARTIC_WRENCH_TU
+      const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s, rep, Wp));
+#elif defined(MH_ARTIC_REPORT_TU)
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s, rep));
 #else
       const double hh = uni(do_mini_step(M, Y, Z, g, ws, aux, rng, dt - h, kin_ok, status, solves, rows, pivs, bytes, Dp, B, b, s));
@@ -1576,7 +1588,11 @@ MH_DEV void artic_contacts_body(const Model* __restrict__ Mg, int B, double dt, 
 #define MH_GEOM_POSE_PARAM
 #define MH_GEOM_POSE_ARG
 #endif
-#ifdef MH_ARTIC_REPORT_TU
+#ifdef MH_ARTIC_WRENCH_TU
+// (the wrench travels by value behind the rows, as the drive does; terms 0 = the body's NULL)
+#define MH_GEOM_REPORT_PARAM , double* __restrict__ report, mh_artic_wrench W
+#define MH_GEOM_REPORT_ARG , report, (W.terms != 0 ? &W : nullptr)
+#elif defined(MH_ARTIC_REPORT_TU)
 #define MH_GEOM_REPORT_PARAM , double* __restrict__ report
 #define MH_GEOM_REPORT_ARG , report
 #else

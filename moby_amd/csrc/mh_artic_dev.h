@@ -1,10 +1,10 @@
 // mh_artic_dev.h -- many-worlds stepper for fixed-base articulated bodies (include/moby_hip_artic.h; BASELINE config 5): the device code and
 // the host declarations every articulated translation unit shares.
 //
-// Each of the thirteen articulated .hip files sets its switches (MH_ARTIC_DRIVE_TU, MH_ARTIC_POSE_TU, MH_ARTIC_BOX_TU, MH_ARTIC_PAIR_TU,
-// MH_ARTIC_BSP_TU, MH_ARTIC_REPORT_TU, MH_ARTIC_PARAMS_TU; a geometry file also its family token MH_ARTIC_GEOM) and includes this header once: the switches pick the
+// Each of the fifteen articulated .hip files sets its switches (MH_ARTIC_DRIVE_TU, MH_ARTIC_POSE_TU, MH_ARTIC_BOX_TU, MH_ARTIC_PAIR_TU,
+// MH_ARTIC_BSP_TU, MH_ARTIC_REPORT_TU, MH_ARTIC_PARAMS_TU, MH_ARTIC_WRENCH_TU; a geometry file also its family token MH_ARTIC_GEOM) and includes this header once: the switches pick the
 // kernels of that code object.  mh_artic.hip (no switch) holds the C entry points and the router to the geometry kernels, mh_artic_drive.hip and
-// mh_artic_pose.hip their own entry points; a geometry file (mh_artic_{box,pair,bsp,rp,pw}[_pose].hip) holds nothing else (mh_artic_pw.hip: the record scatter): its launcher is stamped at
+// mh_artic_pose.hip their own entry points; a geometry file (mh_artic_{box,pair,bsp,rp,pw,wr}[_pose].hip) holds nothing else (mh_artic_pw.hip: the record scatter): its launcher is stamped at
 // the end of this header.
 //
 // One wavefront per world. Per step (TimeSteppingSimulator::do_mini_step with no collision geometry, TSS:114-222):
@@ -231,14 +231,79 @@ MH_DEV void kin_inertia(const Model& M, const Lay& Y, double* g)
   wave_sync();
 }
 
+#ifdef MH_ARTIC_WRENCH_TU
+// Link wrenches (moby_hip_artic.h, mh_artic_wrench; operation order = tests/native/artic_wrench_ref.cpp, bit for bit): called by the forward
+// dynamics right after kin_inertia, when R, x, S of the mini-step's q are in LDS and nothing of the bias pass has been written.  Lane i < nj forms
+// link i's velocity V_i (link_velocities' sum), its damping and the caller's wrench of schedule row s (world b of B) in registers and leaves
+// F6_i = [T + c x F; F] in the bias forces' region `f`, which the bias pass rewrites afterwards; then lane j sums S_j . F6_i over the links outboard
+// of joint j into the tau slot the drive writes (the qdd slot, see drive_tau), on top of the drive's tau_w[j] when there is one.  No LDS of its own;
+// gains and schedule rows come from global memory at every mini-step, as the drive's.  Returns the tau the dynamics reads.
+MH_DEV const double* link_wrench(const Model& M, const Lay& Y, double* g, const double* tau_w, const mh_artic_wrench& W, int B, int b, int s)
+{
+  const mh_artic_model& m = M.m;
+  const int nj = Y.nj, lane = lane_id();
+  if (lane < nj) {
+    const int i = lane;
+    double R[9], c[3], rc[3], F[3], T[3];
+    for (int k = 0; k < 9; k++) R[k] = g[Y.R + 9 * i + k];
+    mat3vec(R, m.com[i], rc);
+    for (int k = 0; k < 3; k++) c[k] = g[Y.x + 3 * i + k] + rc[k];
+    const bool damp = (W.terms & MH_LINK_DAMPING) != 0;
+    if (damp) {
+      const size_t o = (size_t)b * nj + i;
+      double V[6];
+      for (int k = 0; k < 6; k++) {
+        double acc = 0.0; bool first = true;
+        for (int j = 0; j <= i; j++) if ((M.anc[i] >> j) & 1u) { const double vj = g[Y.S + 6 * j + k] * g[Y.qd + j]; acc = first ? vj : acc + vj; first = false; }
+        V[k] = acc;
+      }
+      double wxc[3], vc[3], vi[3], wi[3], fb[3], tb[3];
+      cross3(V, c, wxc);
+      for (int k = 0; k < 3; k++) vc[k] = V[3 + k] + wxc[k];
+      for (int k = 0; k < 3; k++) { vi[k] = (R[k] * vc[0] + R[3 + k] * vc[1]) + R[6 + k] * vc[2]; wi[k] = (R[k] * V[0] + R[3 + k] * V[1]) + R[6 + k] * V[2]; }
+      const double nv = sqrt((vi[0] * vi[0] + vi[1] * vi[1]) + vi[2] * vi[2]), nw = sqrt((wi[0] * wi[0] + wi[1] * wi[1]) + wi[2] * wi[2]);
+      const double cl = -(W.kl[o] + nv * W.klsq[o]), ca = -(W.ka[o] + nw * W.kasq[o]);
+      for (int k = 0; k < 3; k++) { fb[k] = vi[k] * cl; tb[k] = wi[k] * ca; }
+      mat3vec(R, fb, F); mat3vec(R, tb, T);
+    }
+    if (W.terms & MH_LINK_WRENCH) {
+      const double* e = W.w + (((size_t)(W.rows == 1 ? 0 : s) * (size_t)B + (size_t)b) * nj + i) * 6;
+      double f[3] = { e[0], e[1], e[2] }, n[3] = { e[3], e[4], e[5] };
+      if (W.terms & MH_LINK_WRENCH_LINK_AXES) { double t[3]; mat3vec(R, f, t); for (int k = 0; k < 3; k++) f[k] = t[k]; mat3vec(R, n, t); for (int k = 0; k < 3; k++) n[k] = t[k]; }
+      for (int k = 0; k < 3; k++) { F[k] = damp ? F[k] + f[k] : f[k]; T[k] = damp ? T[k] + n[k] : n[k]; }
+    }
+    double cxF[3]; cross3(c, F, cxF);
+    for (int k = 0; k < 3; k++) { g[Y.f + 6 * i + k] = T[k] + cxF[k]; g[Y.f + 6 * i + 3 + k] = F[k]; }
+  }
+  wave_sync();
+  if (lane < nj) {
+    const int j = lane;
+    double acc = 0.0;
+    for (int i = j; i < nj; i++) if ((M.anc[i] >> j) & 1u) acc = acc + dot6(g + Y.S + 6 * j, g + Y.f + 6 * i);   // (a link outboard of joint j has an index >= j)
+    g[Y.qdd + j] = tau_w ? tau_w[j] + acc : acc;
+  }
+  wave_sync();
+  return g + Y.qdd;
+}
+#endif
+
 // kinematics + spatial inertias + bias + H + Cholesky + qdd for the q / qd in LDS.  Returns false if H is not PD.
+// (MH_ARTIC_WRENCH_TU: Wp not NULL = the step's own call, with world wb of wB at schedule row ws: link_wrench adds to tau_w)
 template <int PACK = 1>
-MH_DEV bool dynamics(const Model& M, const Lay& Y, double* g, const double* tau_w)
+MH_DEV bool dynamics(const Model& M, const Lay& Y, double* g, const double* tau_w
+#ifdef MH_ARTIC_WRENCH_TU
+                     , const mh_artic_wrench* Wp = nullptr, int wB = 0, int wb = 0, int ws = 0
+#endif
+                     )
 {
   const mh_artic_model& m = M.m;
   constexpr int STR = 64 / PACK;
   const int nj = Y.nj, lane = (PACK == 1) ? lane_id() : (lane_id() & (STR - 1));
   kin_inertia<PACK>(M, Y, g);
+#ifdef MH_ARTIC_WRENCH_TU
+  static_assert(PACK == 1, "link_wrench works on one world per wavefront (whole-wave lanes and barriers): no packed form in a wrench code object");
+  if (Wp) tau_w = link_wrench(M, Y, g, tau_w, *Wp, wB, wb, ws);
+#endif
   // recursive Newton-Euler with qdd = 0 (the links' OWN inertias): lanes 0..5 = spatial components
   for (int i = 0; i < nj; i++) {
     const int p = m.parent[i];
@@ -341,11 +406,18 @@ MH_DEV bool dynamics(const Model& M, const Lay& Y, double* g, const double* tau_
 // world origin (oracle Artic::fwd_dyn_aba, same operation order).  In place: I6 becomes the articulated inertias, `a` holds the
 // bias accelerations c_i and then the accelerations, `f` the bias forces, `F` the U_i; d_i and u_i sit in the (unused) H region.
 // Returns false when some d_i = S' IA S is not positive.
-MH_DEV bool dynamics_aba(const Model& M, const Lay& Y, double* g, const double* tau_w)
+MH_DEV bool dynamics_aba(const Model& M, const Lay& Y, double* g, const double* tau_w
+#ifdef MH_ARTIC_WRENCH_TU
+                         , const mh_artic_wrench* Wp = nullptr, int wB = 0, int wb = 0, int ws = 0
+#endif
+                         )
 {
   const mh_artic_model& m = M.m;
   const int nj = Y.nj, lane = lane_id();
   kin_inertia(M, Y, g);
+#ifdef MH_ARTIC_WRENCH_TU
+  if (Wp) tau_w = link_wrench(M, Y, g, tau_w, *Wp, wB, wb, ws);
+#endif
   double* dd = g + Y.H; double* uu = g + Y.H + nj;
   for (int i = 0; i < nj; i++) {                          // pass 1, outward
     const int p = m.parent[i];
@@ -921,7 +993,7 @@ void k_artic_step_stab(const Model* __restrict__ Mg, int B, double dt, int nstep
                        mh_world_aux* __restrict__ auxg) { artic_step_body<true>(Mg, B, dt, nsteps, qg, qdg, auxg); }
 #endif
 
-#if (!defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_BOX_TU)) || defined(MH_ARTIC_PARAMS_TU)
+#if (!defined(MH_ARTIC_DRIVE_TU) && !defined(MH_ARTIC_BOX_TU)) || (defined(MH_ARTIC_PARAMS_TU) && !defined(MH_ARTIC_WRENCH_TU))   // (a wrench batch's queries go through mh_artic_pw[_pose].hip)
 // k_artic_fwd_dyn / k_artic_jacobian, and in pose coordinates k_artic_fwd_dyn_pose / k_artic_jacobian_pose: one more argument, the B x 7 poses
 // (MH_ARTIC_PARAMS_TU: k_artic_fwd_dyn_pw[_pose] / k_artic_jacobian_pw[_pose], which read world b's own image of B)
 #if defined(MH_ARTIC_PARAMS_TU) && defined(MH_ARTIC_POSE_TU)
@@ -1065,7 +1137,8 @@ enum mh_artic_family { MH_ARTIC_FAM_NONE = 0,  // no geometry, or spheres agains
                        MH_ARTIC_FAM_PAIR,      // sphere pairs between links or a plane mask (mh_artic_pair.hip), and every model with geometry created under mh_debug_set(13, 1)
                        MH_ARTIC_FAM_BSP,       // a box-sphere pair or a static box (mh_artic_bsp.hip), and every model with geometry created under mh_debug_set(14, 1)
                        MH_ARTIC_FAM_RP,        // the contact report (mh_artic_rp.hip): every batch of mh_artic_batch_create_report, and one that would take BSP created under mh_debug_set(19, 1)
-                       MH_ARTIC_FAM_PW };      // per-world parameters (mh_artic_pw.hip): every batch of mh_artic_batch_create_params, and one that would take RP created under mh_debug_set(20, 1)
+                       MH_ARTIC_FAM_PW,        // per-world parameters (mh_artic_pw.hip): every batch of mh_artic_batch_create_params, and one that would take RP created under mh_debug_set(20, 1)
+                       MH_ARTIC_FAM_WR };      // link wrenches (mh_artic_wr.hip): every batch of mh_artic_batch_create_wrench, and one that would take PW created under mh_debug_set(21, 1)
 
 struct mh_artic_batch {
   int device;                // the HIP device the batch lives on (current at create); every entry point runs there (MH_ON_DEVICE)
@@ -1075,6 +1148,7 @@ struct mh_artic_batch {
   int params;                // d_model holds B images, one per world, and the step goes through MH_ARTIC_FAM_PW: 1 = created by mh_artic_batch_create_params
                              // (the setters take it), 2 = created under mh_debug_set(20, 1) with every image the model's; 0 = one shared image
   mh_artic_model model;      // the shared model as it was handed to create: the topology every record is written into and validated against
+  int wrench;                // created by mh_artic_batch_create_wrench: mh_artic_batch_step_wrench may hand it a wrench (the step goes through MH_ARTIC_FAM_WR)
   mh::artic::Model* d_model;
   double* d_q; double* d_qd; mh_world_aux* d_aux;
   double* d_ws;           // link contacts with the Drumwright-Shell model: _MM + LU workspace, 2 x 64 x 64 doubles per world
@@ -1100,7 +1174,8 @@ static inline mh_artic_family artic_geom_family(const mh_artic_batch* ab)
 // the router (mh_artic.hip): every step of a batch whose family is not MH_ARTIC_FAM_NONE -- the family's workspace and LDS checks, then the
 // launcher of that family and of the batch's coordinates; D as artic_pose_step's
 // report: the rows a batch of the report family writes (NULL: none; every other family ignores it)
-int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report = nullptr);
+// wrench: the link wrench a batch of the wrench family applies (NULL or terms 0: none; every other family ignores it)
+int artic_geom_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report = nullptr, const mh_artic_wrench* wrench = nullptr);
 // the launchers, one per geometry code object (stamped at the end of this header): nothing but the launch of one of its four kernels
 #define MH_ARTIC_LAUNCHER(name) int name(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D)
 MH_ARTIC_LAUNCHER(artic_box_launch);  MH_ARTIC_LAUNCHER(artic_box_pose_launch);
@@ -1126,6 +1201,12 @@ hipError_t artic_pw_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau,
 hipError_t artic_pw_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
 hipError_t artic_pw_pose_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
 hipError_t artic_pw_scatter_launch(mh_artic_batch* ab, void* stream, const mh_artic_params* dev, int first, int count);
+// the wrench family (mh_artic_wr.hip, mh_artic_wr_pose.hip): the per-world-parameters family's step launchers with the wrench (NULL or terms 0: none),
+// and its image sizes -- the per-world-parameters family's, the wrench lives in regions the image already has
+#define MH_ARTIC_WRENCH_LAUNCHER(name) int name(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report, const mh_artic_wrench* W)
+MH_ARTIC_WRENCH_LAUNCHER(artic_wr_launch); MH_ARTIC_WRENCH_LAUNCHER(artic_wr_pose_launch);
+size_t artic_wr_lds_bytes(int nj);
+size_t artic_wr_pose_lds_bytes(int nj);
 
 // the checks mh_artic_batch_step_driven (mh_artic_drive.hip) and mh_artic_batch_set_drive share (nsteps < 0: no schedule length to check against)
 static int check_drive(const mh_artic_drive* d, int nsteps)
@@ -1166,7 +1247,10 @@ static int init_pow10()
 #define MH_GEOM_POSE_PTR
 #endif
 #define MH_GEOM_LAUNCHER(fam) MH_GEOM_LAUNCHER_(fam)
-#ifdef MH_ARTIC_REPORT_TU
+#ifdef MH_ARTIC_WRENCH_TU
+#define MH_GEOM_REPORT_PTR , report, wv
+MH_ARTIC_WRENCH_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
+#elif defined(MH_ARTIC_REPORT_TU)
 #define MH_GEOM_REPORT_PTR , report
 MH_ARTIC_REPORT_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
 #else
@@ -1179,6 +1263,9 @@ MH_ARTIC_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
   const ar::Model* M = ab->d_model;
   const size_t lds = ar::lds_bytes_contacts(ab->nj);
   const hipStream_t st = (hipStream_t)stream;
+#ifdef MH_ARTIC_WRENCH_TU
+  mh_artic_wrench wv; std::memset(&wv, 0, sizeof(wv)); if (W && W->terms != 0) wv = *W;      // by value, as the drive; terms 0 = the kernel's NULL
+#endif
   if (D && D->terms != 0) hipLaunchKernelGGL(ab->cstab ? ar::MH_GEOM_KERNEL(_stab, _drive) : ar::MH_GEOM_KERNEL(, _drive), dim3(ab->B), dim3(64), lds, st,
                                              M, ab->B, dt, nsteps, ab->d_q, ab->d_qd, ab->d_aux, ab->d_ws MH_GEOM_POSE_PTR, *D MH_GEOM_REPORT_PTR);
   else hipLaunchKernelGGL(ab->cstab ? ar::MH_GEOM_KERNEL(_stab, ) : ar::MH_GEOM_KERNEL(, ), dim3(ab->B), dim3(64), lds, st,
@@ -1189,7 +1276,11 @@ MH_ARTIC_LAUNCHER(MH_GEOM_LAUNCHER(MH_ARTIC_GEOM))
 #if defined(MH_ARTIC_PAIR_TU) && !defined(MH_ARTIC_BSP_TU) && !defined(MH_ARTIC_POSE_TU)
 size_t artic_pair_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
 #endif
-#if defined(MH_ARTIC_PARAMS_TU)
+#if defined(MH_ARTIC_WRENCH_TU) && defined(MH_ARTIC_POSE_TU)
+size_t artic_wr_pose_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
+#elif defined(MH_ARTIC_WRENCH_TU)
+size_t artic_wr_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
+#elif defined(MH_ARTIC_PARAMS_TU)
 // the per-world-parameters code objects: their image size, and the launches of their fwd_dyn / jacobian kernels
 #ifdef MH_ARTIC_POSE_TU
 #define MH_PW_NAME(stem) artic_pw_pose_##stem

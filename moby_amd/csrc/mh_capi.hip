@@ -186,6 +186,7 @@ int mh_g_debug_artic_pair = 0;
 int mh_g_debug_artic_bsp = 0;
 int mh_g_debug_artic_rp = 0;   // mh_debug_set(19, v): 1 = an articulated batch that would take the box-sphere kernels, created after the call, launches mh_artic_rp*.hip instead, with a NULL report (A/B runs)
 int mh_g_debug_artic_pw = 0;   // mh_debug_set(20, v): 1 = an articulated batch that would take the report kernels, created after the call, launches mh_artic_pw*.hip instead, with B images equal to the model (A/B runs)
+int mh_g_debug_artic_wr = 0;   // mh_debug_set(21, v): 1 = an articulated batch that would take the per-world-parameters kernels, created after the call, launches mh_artic_wr*.hip instead, with a NULL wrench (A/B runs)
 int mh_g_debug_world_st = 0;   // mh_debug_set(16, v): 1 = a batch that would take the box-sphere build, created after the call, launches mh_world_large_st*.hip instead (A/B runs)
 int mh_g_debug_world_pw = 0;   // mh_debug_set(17, v): 1 = a batch that would take the statics build, created after the call, launches mh_world_large_pw*.hip instead, every record = the scene (A/B runs)
 int mh_g_debug_world_rp = 0;   // mh_debug_set(18, v): 1 = a batch that would take the per-world-parameters build, created after the call, launches mh_world_large_rp*.hip instead, with a NULL report (A/B runs)
@@ -371,6 +372,7 @@ extern "C" int mh_debug_set(int key, int value)
   if (key == 18) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "world contact-report-kernel switch outside {0, 1}"); mh_g_debug_world_rp = value; return MH_OK; }
   if (key == 19) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "articulated contact-report-kernel switch outside {0, 1}"); mh_g_debug_artic_rp = value; return MH_OK; }
   if (key == 20) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "articulated per-world-parameters-kernel switch outside {0, 1}"); mh_g_debug_artic_pw = value; return MH_OK; }
+  if (key == 21) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "articulated link-wrench-kernel switch outside {0, 1}"); mh_g_debug_artic_wr = value; return MH_OK; }
   if (key == 9) { if (value < 0 || value > 1) return fail(MH_ERR_INVALID_ARG, "articulated packing outside {0, 1}"); mh_g_debug_artic_pack = value; return MH_OK; }
   if (key == 8) { if (value < 0 || value > 4) return fail(MH_ERR_INVALID_ARG, "lcp_fast geometry outside {0 .. 4}"); mh_g_debug_fastgeom = value; return MH_OK; }
   if (key == 2) { if (value < 0 || value > 5) return fail(MH_ERR_INVALID_ARG, "block solver geometry outside {0 .. 5}"); mh_g_debug_blk = value; return MH_OK; }

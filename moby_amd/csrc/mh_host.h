@@ -141,5 +141,6 @@ extern MH_HIDDEN int mh_g_debug_world_pw;            // mh_debug_set(17, v): bat
 extern MH_HIDDEN int mh_g_debug_world_rp;            // mh_debug_set(18, v): batches that would take the per-world-parameters build through the report build
 extern MH_HIDDEN int mh_g_debug_artic_rp;            // mh_debug_set(19, v): articulated batches that would take the box-sphere kernels through the report kernels (mh_artic_rp.hip)
 extern MH_HIDDEN int mh_g_debug_artic_pw;            // mh_debug_set(20, v): articulated batches that would take the report kernels through the per-world-parameters kernels (mh_artic_pw.hip)
+extern MH_HIDDEN int mh_g_debug_artic_wr;            // mh_debug_set(21, v): articulated batches that would take the per-world-parameters kernels through the link-wrench kernels (mh_artic_wr.hip)
 
 }  // extern "C"
