@@ -448,6 +448,46 @@ int mh_artic_batch_create_wrench(const mh_artic_model* model, const mh_artic_par
 int mh_artic_batch_step_wrench(mh_artic_batch* ab, void* stream, double dt, int nsteps,
                                const mh_artic_drive* drive, const mh_artic_wrench* wrench, double* report_dev);
 
+/* Episodes on the device.  What a learning or sampling loop needs between two launches without a host round trip: a new episode in the worlds that
+ * ended (reset_dev), which worlds have ended (status_dev), and where the links are (link_poses_dev: a tip position is what a reward or a termination
+ * test reads).  All pointers are DEVICE pointers on the batch's device; every call is ordered on `stream` with the launches of that stream; none
+ * synchronises the device, allocates or frees device memory, or copies through the host.  They work on every batch -- of mh_artic_batch_create,
+ * _create_report, _create_params and _create_wrench, every geometry family, both coordinate kinds.
+ *
+ * mh_artic_batch_reset_dev: world w is reset iff mask_dev[w] != 0 (B ints: a policy's `done` vector as it is; NULL = every world).  q_src, qd_src
+ * (B x nj each) and pose_src (B x 7: px py pz qw qx qy qz) hold a row per world; only the rows of reset worlds are read; a NULL source leaves that
+ * array as it is, as mh_artic_batch_upload does.  The quaternion is normalised on the device with the arithmetic of mh_artic_batch_set_base_pose --
+ * n = sqrt(((w*w + x*x) + y*y) + z*z), every component divided by n, no contraction -- so the stored pose is bit-equal to the host setter's.
+ * A reset world's mh_world_aux becomes the record of a freshly created batch, what mh_world_aux_init(&a, 1) gives: rand() at srand(1), time 0,
+ * status 0, the warm starts _zlast / _z / _v empty, every counter 0 -- whatever sources were given, so a world that carried MH_WORLD_LCP_FAILED,
+ * MH_WORLD_STALLED or MH_WORLD_UNSUPPORTED lives again.  Nothing else of it changes: not its parameter record, the stored drive, or the batch's
+ * coordinates.  A world whose mask is 0 is not touched: not one byte of its q, qd, pose or aux is written.
+ * The rule: after a reset, world w steps exactly as world w of a batch would after mh_artic_batch_upload and mh_artic_batch_set_base_pose had
+ * written the same values and a fresh aux record into it -- state, aux record, base pose and report rows, bit for bit.  (q, qd, the pose and the
+ * aux record are all that a world carries from one launch to the next: the solver workspace of a batch is scratch that every mini-step writes
+ * before it reads.)
+ * The values are NOT validated, as those of mh_artic_batch_set_params_dev are not.  A zero quaternion stores NaN in all four components (0 / 0), a
+ * non-finite one NaN or, for an infinite component against finite ones, zeros and NaN; a non-finite p, q or qd is stored as it is.  What such a
+ * world then does is what the step does with any non-finite state: no double of the state becomes an index, a count or a loop bound, so nothing
+ * outside the world's own memory is touched; its state goes non-finite or it gets a status bit, and the other worlds are not affected.  The host
+ * setter mh_artic_batch_set_base_pose is the validated route.
+ * MH_ERR_INVALID_ARG: a NULL batch; a non-NULL pose_src on a batch in angle coordinates.
+ *
+ * mh_artic_batch_status_dev: aux[w].status into status_dst[w] (B ints) and aux[w].time into time_dst[w] (B doubles); either may be NULL.
+ * MH_ERR_INVALID_ARG: a NULL batch; both NULL.
+ *
+ * mh_artic_batch_link_poses_dev: mh_artic_batch_link_poses into a caller buffer (B x nj x 12) on `stream`: the same kernels, so bit-equal to the
+ * host call, in all four forms (the shared image or per-world images, angles or pose).  MH_ERR_INVALID_ARG: a NULL batch or buffer.
+ * NOT built: a reset inside a multi-step launch (a world that ends mid-launch waits for the launch's end); a per-world seed (every reset world
+ * restarts rand() at srand(1), as every created one does); validation on the device; link velocities; any of this in the large-world stepper
+ * (moby_hip_stack.h). */
+/* (no existing layout changes, so MH_VERSION stays as it is; a caller that needs to know tests this macro) */
+#define MH_ARTIC_EPISODES 1
+int mh_artic_batch_reset_dev(mh_artic_batch* ab, void* stream, const int* mask_dev,
+                             const double* q_src, const double* qd_src, const double* pose_src);
+int mh_artic_batch_status_dev(mh_artic_batch* ab, void* stream, int* status_dst, double* time_dst);
+int mh_artic_batch_link_poses_dev(mh_artic_batch* ab, void* stream, double* poses_dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,9 @@ SYMBOLS = {
     "mh_artic_batch_set_params_dev": (_i, [_vp, _vp, _vp, _i, _i]),
     "mh_artic_batch_create_wrench": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(_vp)]),
     "mh_artic_batch_step_wrench": (_i, [_vp, _vp, _d, _i, _vp, _vp, _vp]),
+    "mh_artic_batch_reset_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mh_artic_batch_status_dev": (_i, [_vp, _vp, _vp, _vp]),
+    "mh_artic_batch_link_poses_dev": (_i, [_vp, _vp, _vp]),
 }
 
 _lib = None

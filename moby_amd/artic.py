@@ -474,11 +474,40 @@ class ArticBatch:
         import torch
         return torch.device("cuda", _lib.load().mh_artic_batch_device(self.handle))
 
-    def _tensor_ptr(self, t, shape):
+    def _tensor_ptr(self, t, shape, dtype=None):
+        """dtype: the tensor's torch dtype (None = torch.float64)"""
         import torch
-        if t.dtype != torch.float64 or not t.is_contiguous() or t.device != self._device() or tuple(t.shape) != tuple(shape):
-            raise ValueError("expected a contiguous float64 tensor of shape %r on %s, got %s %r on %s" % (tuple(shape), self._device(), t.dtype, tuple(t.shape), t.device))
+        dtype = torch.float64 if dtype is None else dtype
+        if t.dtype != dtype or not t.is_contiguous() or t.device != self._device() or tuple(t.shape) != tuple(shape):
+            raise ValueError("expected a contiguous %s tensor of shape %r on %s, got %s %r on %s" % (str(dtype).replace("torch.", ""), tuple(shape), self._device(), t.dtype, tuple(t.shape), t.device))
         return t.data_ptr()
+
+    def reset(self, mask=None, q=None, qd=None, pose=None, stream=None):
+        """A new episode in some worlds, on `stream`, with no host synchronisation (mh_artic_batch_reset_dev; include/moby_hip_artic.h, "Episodes on
+        the device").  mask: a contiguous torch.int32 (B,) tensor on the batch's device, world w is reset iff mask[w] != 0; None = every world.
+        q, qd: float64 (B, nj); pose: float64 (B, 7), pose coordinates only -- only the rows of reset worlds are read, None leaves that array as it
+        is.  A reset world's aux record becomes a fresh one (rand() at srand(1), time, status, warm starts and counters 0) whatever was given; a
+        world that is not reset is not touched.  The values are NOT validated."""
+        import torch
+        if mask is not None and (not _is_tensor(mask) or mask.dtype != torch.int32):
+            raise ValueError("reset: mask must be a torch.int32 tensor of shape (%d,) on the batch's device, got %s -- convert it (torch.as_tensor(done, dtype=torch.int32, device=...))"
+                             % (self.B, mask.dtype if _is_tensor(mask) else type(mask).__name__))
+        P = lambda t, shape: None if t is None else self._tensor_ptr(t, shape)
+        mp = None if mask is None else self._tensor_ptr(mask, (self.B,), torch.int32)
+        _lib.check(_lib.load().mh_artic_batch_reset_dev(self.handle, stream, mp, P(q, (self.B, self.nj)), P(qd, (self.B, self.nj)), P(pose, (self.B, 7))))
+
+    def status_into(self, status_t=None, time_t=None, stream=None):
+        """Every world's status bits into an int32 (B,) tensor and its time into a float64 (B,) tensor on the batch's device (either may be None, not
+        both), stream-ordered (no host sync): which worlds have ended."""
+        import torch
+        sp = None if status_t is None else self._tensor_ptr(status_t, (self.B,), torch.int32)
+        tp = None if time_t is None else self._tensor_ptr(time_t, (self.B,))
+        _lib.check(_lib.load().mh_artic_batch_status_dev(self.handle, stream, sp, tp))
+
+    def link_poses_into(self, poses_t, stream=None):
+        """link_poses() into a float64 contiguous (B, nj, 12) torch tensor on the batch's device, stream-ordered (no host sync, no allocation): the
+        same kernels, bit-equal to the host call."""
+        _lib.check(_lib.load().mh_artic_batch_link_poses_dev(self.handle, stream, self._tensor_ptr(poses_t, (self.B, self.nj, 12))))
 
     def step(self, dt, nsteps=1, stream=None, drive=None, report=None, wrench=None):
         """nsteps x TimeSteppingSimulator::step(dt) in one launch on `stream` (a raw HIP stream handle; None = the null stream).

@@ -27,6 +27,11 @@
 //   double* rows_dev;  hipMalloc(&rows_dev, sizeof(double) * B * n * r->report_slots() * MH_REPORT_PAIR);   // the caller owns the device array
 //   r->step_report(1e-3, n, rows_dev);             // row of world w, step s, slot k at rows_dev + ((w * n + s) * report_slots() + k) * MH_REPORT_PAIR
 //
+// Episodes on the device (include/moby_hip_artic.h, "Episodes on the device": device arrays of the caller, stream-ordered, no host round trip):
+//   robots.link_poses_dev(poses_dev);              // B x nj x 12: where the tip is -- the caller's kernel fills done_dev (B ints) from it
+//   robots.reset_dev(done_dev, q0_dev, qd0_dev);   // a new episode in the copies whose done_dev is nonzero; the others are not touched
+//   robots.status_dev(status_dev);                 // B ints: which copies carry MH_WORLD_LCP_FAILED / _STALLED / _UNSUPPORTED
+//
 // Generalized coordinates / velocities are the joint positions / velocities in the model's joint order (parents first),
 // as get_generalized_coordinates_euler / get_generalized_velocity return them for a fixed-base RCArticulatedBody.
 #ifndef MOBY_HIP_ARTICULATED_ADAPTER_H
@@ -124,6 +129,17 @@ class BatchedArticulatedBody {
     if (mh_artic_batch_step_wrench(_ab, NULL, dt, nsteps, NULL, &wrench, report_dev) != MH_OK) throw std::runtime_error(mh_last_error());
     _dirty = true; return dt;
   }
+  /// Episodes on the device (include/moby_hip_artic.h, "Episodes on the device"): DEVICE arrays the caller owns, ordered on `stream` (NULL: the
+  /// null stream), no synchronisation.  reset_dev: copy w starts a new episode iff mask_dev[w] != 0 (NULL: every copy) from its rows of q_src,
+  /// qd_src (B x nj) and pose_src (B x 7, pose coordinates only), NULL leaving that array; its aux record becomes a fresh one.  NOT validated.
+  void reset_dev(const int* mask_dev, const double* q_src, const double* qd_src, const double* pose_src = NULL, void* stream = NULL) {
+    if (mh_artic_batch_reset_dev(_ab, stream, mask_dev, q_src, qd_src, pose_src) != MH_OK) throw std::runtime_error(mh_last_error());
+    _dirty = true;
+  }
+  /// every copy's status bits (B ints) and time (B doubles) into device arrays; either may be NULL
+  void status_dev(int* status_dst, double* time_dst = NULL, void* stream = NULL) { if (mh_artic_batch_status_dev(_ab, stream, status_dst, time_dst) != MH_OK) throw std::runtime_error(mh_last_error()); }
+  /// the link poses of the resident states (B x nj x 12: row-major R, origin; model frame) into a device array
+  void link_poses_dev(double* poses_dst, void* stream = NULL) { if (mh_artic_batch_link_poses_dev(_ab, stream, poses_dst) != MH_OK) throw std::runtime_error(mh_last_error()); }
   /// nspheres + nboxes + npairs of a batch made by with_report: the rows per world and step
   int report_slots() const { return _nslots; }
   /// step(dt, nsteps) with the launch's rows written to report_dev, a DEVICE array of B x nsteps x report_slots() x MH_REPORT_PAIR doubles that the

@@ -474,6 +474,18 @@ int mh_artic_batch_state_dev(mh_artic_batch* ab, void* stream, double* q_dst, do
   return MH_OK;
 }
 
+// the link poses of the resident states into d_p (device, B x nj x 12) on `stream`: the forward-dynamics kernel of the batch's form -- per-world
+// images or the shared one, pose or angle coordinates -- with only the poses asked for.  mh_artic_batch_link_poses and _link_poses_dev share it
+static hipError_t link_poses_launch(mh_artic_batch* ab, void* stream, double* d_p)
+{
+  namespace ar = mh::artic;
+  if (ab->params) return ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_fwd_dyn_launch(ab, stream, nullptr, nullptr, nullptr, d_p, nullptr) : artic_pw_fwd_dyn_launch(ab, stream, nullptr, nullptr, nullptr, d_p, nullptr);
+  if (ab->base_coords == MH_ARTIC_BASE_POSE) return artic_pose_fwd_dyn_launch(ab, stream, nullptr, nullptr, nullptr, d_p, nullptr);
+  hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)stream,
+                     (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)nullptr, (double*)nullptr, (double*)nullptr, d_p, (int*)nullptr);
+  return hipGetLastError();
+}
+
 int mh_artic_batch_fwd_dyn(mh_artic_batch* ab, const double* tau, double* qdd_out, double* H_out)
 {
   namespace ar = mh::artic;
@@ -488,8 +500,8 @@ int mh_artic_batch_fwd_dyn(mh_artic_batch* ab, const double* tau, double* qdd_ou
   if (ok && H_out) ok = hipMalloc((void**)&d_H, B * nj * nj * 8) == hipSuccess;
   if (!ok) { cleanup(); return fail(MH_ERR_HIP, "device allocation failed"); }
   hipError_t e = hipSuccess;
-  if (ab->params) e = ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok) : artic_pw_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok);   // each world's own image
-  else if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, d_tau, d_qdd, d_H, nullptr, d_ok);
+  if (ab->params) e = ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_fwd_dyn_launch(ab, nullptr, d_tau, d_qdd, d_H, nullptr, d_ok) : artic_pw_fwd_dyn_launch(ab, nullptr, d_tau, d_qdd, d_H, nullptr, d_ok);   // each world's own image
+  else if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, nullptr, d_tau, d_qdd, d_H, nullptr, d_ok);
   else hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
                           (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)d_tau, d_qdd, d_H, (double*)nullptr, d_ok);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -505,22 +517,44 @@ int mh_artic_batch_fwd_dyn(mh_artic_batch* ab, const double* tau, double* qdd_ou
 
 int mh_artic_batch_link_poses(mh_artic_batch* ab, double* poses)
 {
-  namespace ar = mh::artic;
   if (!ab || !poses) return fail(MH_ERR_INVALID_ARG, "null batch / buffer");
   MH_ON_DEVICE(ab);
   MH_HIP(hipDeviceSynchronize());                              // a step may be in flight on a caller's non-blocking stream
   const size_t bytes = (size_t)ab->B * ab->nj * 12 * 8;
   double* d_p = nullptr;
   MH_HIP(hipMalloc((void**)&d_p, bytes));
-  hipError_t e = hipSuccess;
-  if (ab->params) e = ab->base_coords == MH_ARTIC_BASE_POSE ? artic_pw_pose_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr) : artic_pw_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr);
-  else if (ab->base_coords == MH_ARTIC_BASE_POSE) e = artic_pose_fwd_dyn_launch(ab, nullptr, nullptr, nullptr, d_p, nullptr);
-  else hipLaunchKernelGGL(ar::k_artic_fwd_dyn, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
-                          (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, (const double*)nullptr, (double*)nullptr, (double*)nullptr, d_p, (int*)nullptr);
+  hipError_t e = link_poses_launch(ab, nullptr, d_p);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(poses, d_p, bytes, hipMemcpyDeviceToHost);
   (void)hipFree(d_p);
   if (e != hipSuccess) return fail(MH_ERR_HIP, "link pose launch failed: %s", hipGetErrorString(e));
+  return MH_OK;
+}
+
+// Episodes on the device (include/moby_hip_artic.h): three launches on the caller's stream -- no synchronisation, no allocation, no host copy
+int mh_artic_batch_reset_dev(mh_artic_batch* ab, void* stream, const int* mask_dev, const double* q_src, const double* qd_src, const double* pose_src)
+{
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  if (pose_src && ab->base_coords != MH_ARTIC_BASE_POSE) return fail(MH_ERR_INVALID_ARG, "pose_src: the batch is in angle coordinates: no base pose to reset");
+  MH_ON_DEVICE(ab);
+  MH_HIP(artic_reset_launch(stream, ab->B, ab->nj, mask_dev, q_src, qd_src, pose_src, ab->d_q, ab->d_qd, ab->d_pose, ab->d_aux));
+  return MH_OK;
+}
+
+int mh_artic_batch_status_dev(mh_artic_batch* ab, void* stream, int* status_dst, double* time_dst)
+{
+  if (!ab) return fail(MH_ERR_INVALID_ARG, "null batch");
+  if (!status_dst && !time_dst) return fail(MH_ERR_INVALID_ARG, "status_dst and time_dst are both NULL: nothing to write");
+  MH_ON_DEVICE(ab);
+  MH_HIP(artic_status_launch(stream, ab->B, ab->d_aux, status_dst, time_dst));
+  return MH_OK;
+}
+
+int mh_artic_batch_link_poses_dev(mh_artic_batch* ab, void* stream, double* poses_dst)
+{
+  if (!ab || !poses_dst) return fail(MH_ERR_INVALID_ARG, "null batch / buffer");
+  MH_ON_DEVICE(ab);
+  MH_HIP(link_poses_launch(ab, stream, poses_dst));
   return MH_OK;
 }
 

@@ -1160,9 +1160,10 @@ struct mh_artic_batch {
 };
 
 // the pose-coordinate launches (mh_artic_pose.hip): the step (D NULL or terms 0 = undriven; arguments checked by the caller), and the
-// kernels of mh_artic_batch_fwd_dyn / link_poses / jacobian on the null stream
+// kernels of mh_artic_batch_fwd_dyn / link_poses (on `stream`: the host entries pass the null stream, mh_artic_batch_link_poses_dev the caller's) /
+// jacobian (the null stream)
 int artic_pose_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D);
-hipError_t artic_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
+hipError_t artic_pose_fwd_dyn_launch(mh_artic_batch* ab, void* stream, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
 hipError_t artic_pose_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
 
 // the family a step of the batch goes through: the one fixed at create, except that mh_debug_set(12, 1) sends a sphere-only batch through the box
@@ -1191,16 +1192,21 @@ MH_ARTIC_REPORT_LAUNCHER(artic_rp_launch); MH_ARTIC_REPORT_LAUNCHER(artic_rp_pos
 size_t artic_rp_lds_bytes(int nj);
 size_t artic_rp_pose_lds_bytes(int nj);
 // the per-world-parameters family (mh_artic_pw.hip, mh_artic_pw_pose.hip): the report family's launchers and image sizes over B images, the
-// kernels of mh_artic_batch_fwd_dyn / link_poses / jacobian that read world b's image (null stream, as the pose forms above), and the scatter of
+// kernels of mh_artic_batch_fwd_dyn / link_poses / jacobian that read world b's image (streams as the pose forms above), and the scatter of
 // mh_artic_batch_set_params_dev (records rec[0 .. count) into images first ..; the launch's hipGetLastError)
 MH_ARTIC_REPORT_LAUNCHER(artic_pw_launch); MH_ARTIC_REPORT_LAUNCHER(artic_pw_pose_launch);
 size_t artic_pw_lds_bytes(int nj);
 size_t artic_pw_pose_lds_bytes(int nj);
-hipError_t artic_pw_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
-hipError_t artic_pw_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
+hipError_t artic_pw_fwd_dyn_launch(mh_artic_batch* ab, void* stream, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
+hipError_t artic_pw_pose_fwd_dyn_launch(mh_artic_batch* ab, void* stream, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok);
 hipError_t artic_pw_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
 hipError_t artic_pw_pose_jacobian_launch(mh_artic_batch* ab, int link, const double* d_p, double* d_J);
 hipError_t artic_pw_scatter_launch(mh_artic_batch* ab, void* stream, const mh_artic_params* dev, int first, int count);
+// episodes on the device (mh_artic_reset.hip: a code object of two small kernels that knows nothing of the model): the launches of
+// mh_artic_batch_reset_dev and mh_artic_batch_status_dev on `stream`, raw pointers into the batch's arrays; the launch's hipGetLastError
+hipError_t artic_reset_launch(void* stream, int B, int nj, const int* mask, const double* q_src, const double* qd_src, const double* pose_src,
+                              double* q, double* qd, double* pose, mh_world_aux* aux);
+hipError_t artic_status_launch(void* stream, int B, const mh_world_aux* aux, int* status_dst, double* time_dst);
 // the wrench family (mh_artic_wr.hip, mh_artic_wr_pose.hip): the per-world-parameters family's step launchers with the wrench (NULL or terms 0: none),
 // and its image sizes -- the per-world-parameters family's, the wrench lives in regions the image already has
 #define MH_ARTIC_WRENCH_LAUNCHER(name) int name(mh_artic_batch* ab, void* stream, double dt, int nsteps, const mh_artic_drive* D, double* report, const mh_artic_wrench* W)
@@ -1292,10 +1298,10 @@ size_t artic_wr_lds_bytes(int nj) { return mh::artic::lds_bytes_contacts(nj); }
 #define MH_PW_POSE_PTR
 #endif
 size_t MH_PW_NAME(lds_bytes)(int nj) { return mh::artic::lds_bytes_contacts(nj); }
-hipError_t MH_PW_NAME(fwd_dyn_launch)(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok)
+hipError_t MH_PW_NAME(fwd_dyn_launch)(mh_artic_batch* ab, void* stream, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok)
 {
   namespace ar = mh::artic;
-  hipLaunchKernelGGL(ar::MH_PW_KERNEL(k_artic_fwd_dyn), dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+  hipLaunchKernelGGL(ar::MH_PW_KERNEL(k_artic_fwd_dyn), dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)stream,
                      (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, d_tau, d_qdd, d_H, d_poses, d_ok MH_PW_POSE_PTR);
   return hipGetLastError();
 }

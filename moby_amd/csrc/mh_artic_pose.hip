@@ -33,10 +33,10 @@ int artic_pose_step(mh_artic_batch* ab, void* stream, double dt, int nsteps, con
   return MH_OK;
 }
 
-hipError_t artic_pose_fwd_dyn_launch(mh_artic_batch* ab, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok)
+hipError_t artic_pose_fwd_dyn_launch(mh_artic_batch* ab, void* stream, const double* d_tau, double* d_qdd, double* d_H, double* d_poses, int* d_ok)
 {
   namespace ar = mh::artic;
-  hipLaunchKernelGGL(ar::k_artic_fwd_dyn_pose, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)nullptr,
+  hipLaunchKernelGGL(ar::k_artic_fwd_dyn_pose, dim3(ab->B), dim3(64), ar::lds_bytes(ab->nj), (hipStream_t)stream,
                      (const ar::Model*)ab->d_model, ab->B, (const double*)ab->d_q, (const double*)ab->d_qd, d_tau, d_qdd, d_H, d_poses, d_ok, (const double*)ab->d_pose);
   return hipGetLastError();
 }
